@@ -23,7 +23,15 @@ Extra objects in the line:
   roofline_hbm -- the dominant HBM-bound hand-written kernel (space-mode divided attention forward,
                   lvl_divided_attn_fwd): algorithmic bytes per launch / average duration against 8 TB/s.
   cpu_baseline -- the CPU oracle (oracle/oracle.py, kind "port") timed on this box's host cores on a bounded
-                  sample (one fwd+loss+bwd of a small batch of the same shapes), rank 0 at N=1 only.
+                  sample (one fwd+loss+bwd of a small batch of the same shapes), rank 0 at N=1 only (`--full`).
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line. `--full` adds the measurements that take
+runs of their own after the timed region: the CPU baseline and the variant records of `config` (`text_trim_off`,
+`device_readback`, `full_last_block`, `graphed_step`); without it those fields are null.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 `.npy` files under DIR (rank 0): the loss, the
+two embeddings and the logit scale the model returned, and a fixed, seeded sample of every parameter and of AdamW's first
+moment after the step. The inputs and weights are seeded, so the same arguments give the same inputs in every run.
 
 `--workload narrator` (not part of the driver contract; default stays the metric above) prints the same kind of line for
 BASELINE configs[4]: captions/s of VCLM_OPENAI_TIMESFORMER_BASE_GPT2 (encode_image + generate), with the decode step's
@@ -75,10 +83,15 @@ def parse():
     p.add_argument('--length', type=int, default=77, help='narrator: caption length in tokens')
     p.add_argument('--graph-only', action='store_true',
                    help='internal: run only the graphed-step variant (lavila_amd/graph_step.py) and print its record; the '
-                        'default run spawns this in a child process so that nothing in it can touch the headline')
+                        '--full run spawns this in a child process so that nothing in it can touch the headline')
     p.add_argument('--checkpoint', action='store_true',
                    help='use_checkpoint=True (main_pretrain.py:100,491-495: activation checkpointing per block, '
                         'timesformer.py:175-187) -- for shapes whose activations do not fit, e.g. 16 frames at local batch 256')
+    p.add_argument('--full', action='store_true',
+                   help='also run what takes runs of its own after the timed region: CPU baseline, trim-off / device '
+                        'read-back / full-last-block / graphed-step variants (a plain run skips them)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step computed as DIR/<name>.npy (float32, rank 0)')
     p.add_argument('--reuse-tokens', action='store_true',
                    help='feed the SAME token tensor object every step (A/B only: the caption-length read-back of the '
                         'text tower is memoised per tensor object; the default hands over a new tensor per step, as a '
@@ -324,6 +337,33 @@ def narrator_main(args, world, rank, device):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 4096      # elements sampled per parameter tensor by dump_outputs (fixed seed: the same indices every run)
+
+
+def dump_outputs(path, loss, out, model, opt):
+    """What the last timed step computed, as float32 `.npy` files: the loss, the model's outputs (embeddings, logit
+    scale) and -- the step's update -- a seeded sample of DUMP_SAMPLE elements of every parameter and of AdamW's first
+    moment (a running average of the gradients), concatenated in named_parameters() order. About 7 MB for TSF-B."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': loss.detach().reshape(1)}
+    for k in ('image_embed', 'text_embed', 'logit_scale'):
+        arrays[k] = out[k].detach()
+    g = torch.Generator().manual_seed(0)
+    params, moments = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = torch.randperm(n, generator=g)[:DUMP_SAMPLE].to(p.device) if n > DUMP_SAMPLE else None
+        st = opt.state.get(p, {})
+        m = st.get('exp_avg', torch.zeros_like(p))
+        params.append(p.detach().reshape(-1) if idx is None else p.detach().reshape(-1)[idx])
+        moments.append(m.reshape(-1) if idx is None else m.reshape(-1)[idx])
+    arrays['params_sample'] = torch.cat([t.float() for t in params])
+    arrays['adam_exp_avg_sample'] = torch.cat([t.float() for t in moments])
+    for k, t in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), t.float().cpu().numpy())
+
+
 def _self_launch(args):
     """`python bench.py --gpus N` without a launcher: run the same command line under torch.distributed.run (one process
     per GPU, rendezvous on 127.0.0.1 and a free port) and hand its exit status back. Rank 0 of the child job prints the
@@ -460,6 +500,8 @@ def main():
             rehearsal += '; ranks share a device: both towers on one stream (LAVILA_TEXT_STREAM=0)'
 
     if args.workload == 'narrator':
+        if args.dump_outputs:
+            raise SystemExit('bench.py: --dump-outputs covers the pretraining step (--workload pretrain) only')
         if args.batch == 256:
             args.batch = 64                # main_infer_narrator.py:48
         return narrator_main(args, world, rank, device)
@@ -527,6 +569,8 @@ def main():
     host_bound_default = (os.environ.get('LAVILA_BENCH_DEVICE_READBACK') != '1' and
                           os.environ.get('LAVILA_TEXT_TRIM', '1') != '0')
 
+    last_out = {}                  # what the latest step's model call returned (--dump-outputs)
+
     def step(host_bound=None):
         # a training loop receives a NEW token tensor every iteration (main_pretrain.py:489-498)
         toks = tokens if args.reuse_tokens else tokens.clone()
@@ -535,6 +579,7 @@ def main():
             with torch.autocast('cuda', dtype=amp, enabled=amp is not None):
                 out = net(video, toks, use_checkpoint=args.checkpoint, norm_embed=True)
                 loss = crit(out)['loss']
+        last_out['out'] = out
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
@@ -585,11 +630,13 @@ def main():
     # device memory of the timed region (the caching allocator's own high-water marks; HBM3E per MI355X: 288 GB)
     peak_alloc_gb = round(torch.cuda.max_memory_allocated(device) / 1e9, 2)
     peak_reserved_gb = round(torch.cuda.max_memory_reserved(device) / 1e9, 2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_out['out'], model, opt)
 
     # the cost of the text tower's per-step caption-length read-back, made visible: the same step with the trim (and
     # with it the host read) switched off -- all 77 positions computed, the host free to run ahead
     no_trim = None
-    if os.environ.get('LAVILA_TEXT_TRIM', '1') != '0' and not args.no_events:
+    if args.full and os.environ.get('LAVILA_TEXT_TRIM', '1') != '0' and not args.no_events:
         from lavila_amd import models as _m
         _m._TEXT_TRIM = False
         step(host_bound=False)
@@ -606,7 +653,7 @@ def main():
 
     # the unmodified reference loop: the caption length read back from the device inside the text tower, every step
     readback = None
-    if host_bound_default and not args.no_events:
+    if args.full and host_bound_default and not args.no_events:
         step(host_bound=False)
         fence()
         n4, h4, t4 = max(2, min(4, args.steps)), 0.0, time.perf_counter()
@@ -621,7 +668,7 @@ def main():
     # the same step with the LAST block of both towers computed on every row, as the reference does (the default computes
     # only the rows that reach the output -- cls / EOT -- which is exact: DESIGN.md section 4, "Last block")
     full_last = None
-    if os.environ.get('LAVILA_CLS_LAST', '1') != '0' and not args.no_events:
+    if args.full and os.environ.get('LAVILA_CLS_LAST', '1') != '0' and not args.no_events:
         from lavila_amd import timesformer as _t
         _t.CLS_ONLY_LAST_BLOCK = False
         step()
@@ -636,8 +683,8 @@ def main():
     # the same iteration captured as one hipGraph per caption-length bucket and replayed (lavila_amd/graph_step.py), in a
     # child process (its own model, optimizer and allocator: nothing in it can touch the numbers above)
     graphed = None
-    if (os.environ.get('LAVILA_BENCH_GRAPH', '1') != '0' and world == 1 and not force_group and not args.no_events
-            and amp is not None and rank == 0):
+    if (args.full and os.environ.get('LAVILA_BENCH_GRAPH', '1') != '0' and world == 1 and not force_group
+            and not args.no_events and amp is not None and rank == 0):
         try:
             graphed = _graphed_child(args)
         except Exception as exc:                # a variant record must never take the headline down
@@ -739,6 +786,7 @@ def main():
                        'linear_gemms': 'lvl_linear_tn / lvl_linear_wgrad (hand-written MFMA; no library GEMM on the path)',
                        'peak_mem_gb': peak_alloc_gb, 'peak_mem_reserved_gb': peak_reserved_gb,
                        'use_checkpoint': bool(args.checkpoint),
+                       'full': bool(args.full),
                        # wall time the host spends INSIDE step() -- not host work: once the launch queue is full every call
                        # blocks until the device has drained a step's worth (back-pressure; the `device_readback` record's
                        # also includes the text tower's caption-length read-back). `host_work_ms_per_step` is the smallest
@@ -776,7 +824,7 @@ def main():
         }
         if rehearsal:
             line['config']['note'] = rehearsal
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args, model, img)
         print(json.dumps(line), flush=True)
     if world > 1 or force_group:

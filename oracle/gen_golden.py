@@ -572,6 +572,106 @@ def run_narrator_beam_golden():
     torch.save(out, os.path.join(GOLDEN, 'narrator_beam.pt'))
 
 
+def _tensor_digest(t):
+    """sha256 of a tensor's dtype, shape and bytes: equality with the reference's tensor without storing it."""
+    import hashlib
+    t = t.detach().cpu().contiguous()
+    h = hashlib.sha256(f'{t.dtype}|{tuple(t.shape)}|'.encode())
+    h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()
+
+
+def run_reference_boundary_golden(ref):
+    """What tests/test_boundary_cpu.py and tests/test_narrator_host_cpu.py compare the drop-in's host side with, taken
+    from the unmodified reference: state_dict names / shapes of the TSF-L/14 constructors and of the gated GPT-2, the
+    checkpoint helpers' outputs on seeded inputs, and the named constructor's result after importing seeded OpenAI-CLIP
+    weights (per-tensor digests + requires_grad flags; the CLIP state_dict's names / shapes let the test rebuild the
+    same seeded weights)."""
+    import contextlib
+    import io
+    out = {'large_state_dict': {}, 'pretrained_clip': {}, 'gpt2_state_dict': {}}
+    for ctor, frames in (('CLIP_OPENAI_TIMESFORMER_LARGE', 4), ('CLIP_OPENAI_TIMESFORMER_LARGE_336PX', 16)):
+        size = 336 if '336' in ctor else 224
+        with contextlib.redirect_stdout(io.StringIO()):
+            rv = ref.timesformer.SpaceTimeTransformer(
+                img_size=size, patch_size=14, embed_dim=1024, depth=24, num_heads=16, num_frames=frames,
+                time_init='zeros', attention_style='frozen-in-time', ln_pre=True, act_layer=ref.openai_model.QuickGELU,
+                is_tanh_gating=False)
+            rv.head = nn.Identity()
+            rv.pre_logits = nn.Identity()
+            rv.fc = nn.Identity()
+            theirs = ref.models.CLIP(embed_dim=256, vision_width=1024, vision_model=rv, context_length=77,
+                                     vocab_size=49408, transformer_width=768, transformer_heads=12, transformer_layers=12,
+                                     tempearture_init=0.07)
+        out['large_state_dict'][f'{ctor}-{frames}'] = [(k, tuple(v.shape)) for k, v in theirs.state_dict().items()]
+        del theirs, rv
+
+    # checkpoint helpers (utils.py): remap_keys of a two-layer CLIP-shaped dict, inflate_positional_embeds per case
+    g = torch.Generator().manual_seed(3)
+    clip = {'class_embedding': torch.randn(8, generator=g), 'positional_embedding': torch.randn(5, 8, generator=g),
+            'conv1.weight': torch.randn(8, 3, 2, 2, generator=g), 'ln_pre.weight': torch.randn(8, generator=g),
+            'ln_pre.bias': torch.randn(8, generator=g), 'ln_post.weight': torch.randn(8, generator=g),
+            'ln_post.bias': torch.randn(8, generator=g), 'proj': torch.randn(8, 4, generator=g)}
+    for layer in range(2):
+        for leaf, shp in [('attn.in_proj_weight', (24, 8)), ('attn.in_proj_bias', (24,)),
+                          ('attn.out_proj.weight', (8, 8)), ('attn.out_proj.bias', (8,)), ('ln_1.weight', (8,)),
+                          ('ln_1.bias', (8,)), ('mlp.c_fc.weight', (32, 8)), ('mlp.c_fc.bias', (32,)),
+                          ('mlp.c_proj.weight', (8, 32)), ('mlp.c_proj.bias', (8,)), ('ln_2.weight', (8,)),
+                          ('ln_2.bias', (8,))]:
+            clip[f'transformer.resblocks.{layer}.{leaf}'] = torch.randn(*shp, generator=g)
+    inflate = []
+    for have, want, fix in [(4, 8, 'bilinear'), (8, 4, 'bilinear'), (4, 6, 'zeros'), (4, 7, 'interp'), (4, 4, 'bilinear')]:
+        cur = {'visual.temporal_embed': torch.zeros(1, want, 8), 'visual.pos_embed': torch.zeros(1, 5, 8)}
+        new = {'visual.temporal_embed': torch.randn(1, have, 8, generator=g), 'visual.pos_embed': torch.zeros(1, 5, 8)}
+        b = ref.utils.inflate_positional_embeds(cur, dict(new), num_frames=want, load_temporal_fix=fix)
+        inflate.append({'have': have, 'want': want, 'fix': fix, 'new': new['visual.temporal_embed'].clone(),
+                        'out': b['visual.temporal_embed'].clone()})
+    out['checkpoint_helpers'] = {'clip': clip, 'remap_keys': list(ref.utils.remap_keys(dict(clip), transformer_layers=2).items()),
+                                 'inflate': inflate}
+
+    # the named constructor importing seeded OpenAI-CLIP weights (models.py:329-370), as the test builds them
+    torch.manual_seed(11)
+    with contextlib.redirect_stdout(io.StringIO()):
+        cl = ref.openai_model.CLIP(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768,
+                                   vision_patch_size=16, context_length=77, vocab_size=49408, transformer_width=512,
+                                   transformer_heads=8, transformer_layers=12)
+    assert [k for k, _ in cl.named_parameters()] == list(cl.state_dict()), 'CLIP state_dict is not its parameter list'
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(12)
+        for p in cl.parameters():
+            p.copy_(torch.randn(p.shape, generator=g) * 0.05)
+    out['clip_vit_b16_shapes'] = [(k, tuple(v.shape)) for k, v in cl.state_dict().items()]
+    saved = ref.models.load_openai_clip
+    ref.models.load_openai_clip = lambda name, device='cpu': (cl, None)
+    try:
+        for embed, freeze in ((512, True), (256, False)):
+            with contextlib.redirect_stdout(io.StringIO()):
+                theirs = ref.models.CLIP_OPENAI_TIMESFORMER_BASE(num_frames=4, timesformer_freeze_space=freeze,
+                                                                 project_embed_dim=embed, temperature_init=0.07)
+            out['pretrained_clip'][f'{embed}-{freeze}'] = {
+                'keys': list(theirs.state_dict()),
+                'digest': {k: _tensor_digest(v) for k, v in theirs.state_dict().items()},
+                'requires_grad': {k: p.requires_grad for k, p in theirs.named_parameters()}}
+            del theirs
+    finally:
+        ref.models.load_openai_clip = saved
+
+    # the narrator's gated GPT-2 (gpt2_gated.py): every key / shape / dtype, the constant attention buffers in full
+    from transformers import GPT2Config
+    from oracle.ref_import import load_reference_narrator
+    rn = load_reference_narrator()
+    for freq, gated in ((1, True), (2, False), (3, True)):
+        base = GPT2Config(vocab_size=97, n_positions=24, n_embd=128, n_layer=4, n_head=2, use_cache=False,
+                          bos_token_id=96, eos_token_id=96)
+        sd = rn.gpt2_gated.GPT2LMHeadModel(rn.gpt2_gated.augment_gpt2_config(base, cross_attn_freq=freq,
+                                                                           gated_xattn=gated)).state_dict()
+        out['gpt2_state_dict'][f'{freq}-{gated}'] = {
+            k: (tuple(v.shape), v.dtype,
+                v.clone() if (k.endswith('.bias') and v.dtype == torch.uint8 or k.endswith('masked_bias')) else None)
+            for k, v in sd.items()}
+    torch.save(out, os.path.join(GOLDEN, 'reference_boundary.pt'))
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     torch.set_num_threads(8)
@@ -594,6 +694,8 @@ def main():
         run_narrator_decoder_golden()
     if not only or 'beam' in only:
         run_narrator_beam_golden()
+    if not only or 'boundary' in only:
+        run_reference_boundary_golden(ref)
 
 
 if __name__ == '__main__':

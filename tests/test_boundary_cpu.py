@@ -9,7 +9,6 @@ import torch
 
 from conftest import ROOT, load_golden
 from helpers import build_model
-from oracle.ref_import import reference_available
 
 MODELS = ['tiny_p16', 'tiny_p14_gated', 'config1_tsfb_112']
 
@@ -86,31 +85,18 @@ def test_named_constructor_swallows_driver_kwargs_and_matches_survey_counts():
         models.get_loss('VCLM_OPENAI_TIMESFORMER_BASE_GPT2', args)
 
 
-@pytest.mark.skipif(not reference_available(), reason='reference only exists in the build container')
 @pytest.mark.parametrize('ctor,frames', [('CLIP_OPENAI_TIMESFORMER_LARGE', 4), ('CLIP_OPENAI_TIMESFORMER_LARGE_336PX', 16)])
 def test_large_constructors_match_reference_state_dict(ctor, frames):
-    """models.py:374-491: TSF-L/14 at 224 (N=256) and 336 (N=576): parameter names, shapes, order, and the freeze-space
-    error behaviour when no CLIP weights are present."""
+    """models.py:374-491: TSF-L/14 at 224 (N=256) and 336 (N=576): parameter names, shapes, order (the reference's, from
+    tests/golden/reference_boundary.pt), and the freeze-space error behaviour when no CLIP weights are present."""
     import contextlib
     import io
     from lavila.models import models
-    from oracle.ref_import import load_reference
-    import torch.nn as nn
-    ref = load_reference()
+    size = 336 if '336' in ctor else 224
     with contextlib.redirect_stdout(io.StringIO()):
         ours = getattr(models, ctor)(num_frames=frames, pretrained=False, project_embed_dim=256)
-        size = 336 if '336' in ctor else 224
-        rv = ref.timesformer.SpaceTimeTransformer(
-            img_size=size, patch_size=14, embed_dim=1024, depth=24, num_heads=16, num_frames=frames, time_init='zeros',
-            attention_style='frozen-in-time', ln_pre=True, act_layer=ref.openai_model.QuickGELU, is_tanh_gating=False)
-        rv.head = nn.Identity()
-        rv.pre_logits = nn.Identity()
-        rv.fc = nn.Identity()
-        theirs = ref.models.CLIP(embed_dim=256, vision_width=1024, vision_model=rv, context_length=77, vocab_size=49408,
-                                 transformer_width=768, transformer_heads=12, transformer_layers=12, tempearture_init=0.07)
-    a = {k: tuple(v.shape) for k, v in ours.state_dict().items()}
-    b = {k: tuple(v.shape) for k, v in theirs.state_dict().items()}
-    assert list(a) == list(b) and a == b
+    theirs = load_golden('reference_boundary.pt')['large_state_dict'][f'{ctor}-{frames}']
+    assert [(k, tuple(v.shape)) for k, v in ours.state_dict().items()] == theirs
     assert ours.visual.patches_per_frame == (size // 14) ** 2
     with pytest.raises(RuntimeError):      # nothing would be frozen without the pretrained weights: say so
         with contextlib.redirect_stdout(io.StringIO()):
@@ -141,45 +127,46 @@ def test_reference_error_behaviour():
                                 'logit_scale': torch.tensor(1.0)})
 
 
-@pytest.mark.skipif(not reference_available(), reason='reference only exists in the build container')
 def test_checkpoint_helpers_match_reference():
-    from oracle.ref_import import load_reference
+    """remap_keys / inflate_positional_embeds (utils.py) against the reference's outputs on the same seeded inputs
+    (tests/golden/reference_boundary.pt)."""
     from lavila.models.utils import inflate_positional_embeds, remap_keys
-    ref = load_reference()
-    g = torch.Generator().manual_seed(3)
-    clip = {'class_embedding': torch.randn(8, generator=g), 'positional_embedding': torch.randn(5, 8, generator=g),
-            'conv1.weight': torch.randn(8, 3, 2, 2, generator=g), 'ln_pre.weight': torch.randn(8, generator=g),
-            'ln_pre.bias': torch.randn(8, generator=g), 'ln_post.weight': torch.randn(8, generator=g),
-            'ln_post.bias': torch.randn(8, generator=g), 'proj': torch.randn(8, 4, generator=g)}
-    for layer in range(2):
-        for leaf, shp in [('attn.in_proj_weight', (24, 8)), ('attn.in_proj_bias', (24,)),
-                          ('attn.out_proj.weight', (8, 8)), ('attn.out_proj.bias', (8,)), ('ln_1.weight', (8,)),
-                          ('ln_1.bias', (8,)), ('mlp.c_fc.weight', (32, 8)), ('mlp.c_fc.bias', (32,)),
-                          ('mlp.c_proj.weight', (8, 32)), ('mlp.c_proj.bias', (8,)), ('ln_2.weight', (8,)),
-                          ('ln_2.bias', (8,))]:
-            clip[f'transformer.resblocks.{layer}.{leaf}'] = torch.randn(*shp, generator=g)
+    fx = load_golden('reference_boundary.pt')['checkpoint_helpers']
+    clip = fx['clip']
+    assert len(clip) == 8 + 2 * 12
     ours = remap_keys(dict(clip), transformer_layers=2)
-    theirs = ref.utils.remap_keys(dict(clip), transformer_layers=2)
-    assert list(ours.keys()) == list(theirs.keys())
-    for k in ours:
-        assert torch.equal(ours[k], theirs[k]), k
-    for have, want, fix in [(4, 8, 'bilinear'), (8, 4, 'bilinear'), (4, 6, 'zeros'), (4, 7, 'interp'), (4, 4, 'bilinear')]:
+    theirs = fx['remap_keys']
+    assert list(ours.keys()) == [k for k, _ in theirs]
+    for k, v in theirs:
+        assert torch.equal(ours[k], v), k
+    assert [(c['have'], c['want'], c['fix']) for c in fx['inflate']] == \
+        [(4, 8, 'bilinear'), (8, 4, 'bilinear'), (4, 6, 'zeros'), (4, 7, 'interp'), (4, 4, 'bilinear')]
+    for c in fx['inflate']:
+        have, want, fix = c['have'], c['want'], c['fix']
         cur = {'visual.temporal_embed': torch.zeros(1, want, 8), 'visual.pos_embed': torch.zeros(1, 5, 8)}
-        new = {'visual.temporal_embed': torch.randn(1, have, 8, generator=g), 'visual.pos_embed': torch.zeros(1, 5, 8)}
+        new = {'visual.temporal_embed': c['new'].clone(), 'visual.pos_embed': torch.zeros(1, 5, 8)}
+        assert tuple(new['visual.temporal_embed'].shape) == (1, have, 8)
         a = inflate_positional_embeds(cur, dict(new), num_frames=want, load_temporal_fix=fix)
-        b = ref.utils.inflate_positional_embeds(cur, dict(new), num_frames=want, load_temporal_fix=fix)
-        assert torch.equal(a['visual.temporal_embed'], b['visual.temporal_embed'])
+        assert torch.equal(a['visual.temporal_embed'], c['out']), (have, want, fix)
     with pytest.raises(NotImplementedError):
         inflate_positional_embeds({'visual.pos_embed': torch.zeros(1, 5, 8)}, {'visual.pos_embed': torch.zeros(1, 10, 8)})
 
 
-@pytest.mark.skipif(not reference_available(), reason='reference only exists in the build container')
-def test_drop_in_coexists_with_reference_tree():
+def test_drop_in_coexists_with_reference_tree(tmp_path):
     """With this repo ahead of the reference on sys.path, the hot-path modules resolve to lavila_amd while every
-    other reference module (meters, schedulers, ...) still comes from the reference tree."""
+    other reference module (meters, schedulers, ...) still comes from the reference tree. The
+    reference tree is stood in for by its layout: `lavila/` without `__init__.py` files (namespace packages, as
+    upstream), the model modules the drop-in replaces and the utils modules it does not, each file a marker only."""
     import subprocess
     import sys
-    from oracle.ref_import import REFERENCE_ROOT
+    REFERENCE_ROOT = str(tmp_path / 'reference')
+    for sub, names in (('models', ('models', 'loss', 'timesformer', 'openai_model', 'utils', 'distributed_utils',
+                                   'coca', 'narrator', 'gpt2_gated', 'openai_clip', 'tokenizer')),
+                       ('utils', ('meter', 'scheduler', 'distributed', 'random', 'preprocess'))):
+        os.makedirs(os.path.join(REFERENCE_ROOT, 'lavila', sub))
+        for n in names:
+            with open(os.path.join(REFERENCE_ROOT, 'lavila', sub, n + '.py'), 'w') as f:
+                f.write('STAND_IN = True\n')
     code = (
         "import sys; sys.path[:0] = [%r, %r]\n"
         "import lavila.models.models as m, lavila.models.loss as l, lavila.models.timesformer as t\n"
@@ -193,53 +180,50 @@ def test_drop_in_coexists_with_reference_tree():
     assert out.returncode == 0 and 'ok' in out.stdout, out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not reference_available(), reason='reference only exists in the build container')
 @pytest.mark.parametrize('embed,freeze', [(512, True), (256, False)])
 def test_pretrained_clip_import_matches_reference_constructor(tmp_path, monkeypatch, embed, freeze):
     """models.py:329-370: the named constructor imports OpenAI-CLIP weights (vision tower through remap_keys with
     strict=False, text tower / embeddings / ln_final verbatim, the two projections + logit_scale only when
     project_embed_dim equals CLIP's 512) and optionally freezes what it imported. No network here: a seeded-random
-    `openai_model.CLIP` of the ViT-B/16 shape stands in for the download on BOTH sides -- the reference constructor
-    gets it through a monkey-patched `load_openai_clip`, ours reads the same state_dict from LAVILA_CLIP_WEIGHTS_DIR --
-    and every tensor of the two resulting models must be equal, requires_grad flags included."""
+    state_dict of `openai_model.CLIP`'s ViT-B/16 names and shapes stands in for the download on BOTH sides -- the
+    reference constructor got it through a monkey-patched `load_openai_clip` (oracle/gen_golden.py), ours reads it from
+    LAVILA_CLIP_WEIGHTS_DIR -- and every tensor of the two resulting models must be equal (the reference's as sha256
+    digests in tests/golden/reference_boundary.pt), requires_grad flags included."""
     import contextlib
+    import hashlib
     import io
     from lavila.models import models
-    from oracle.ref_import import load_reference
-    ref = load_reference()
-    torch.manual_seed(11)
-    with contextlib.redirect_stdout(io.StringIO()):
-        clip = ref.openai_model.CLIP(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768,
-                                     vision_patch_size=16, context_length=77, vocab_size=49408, transformer_width=512,
-                                     transformer_heads=8, transformer_layers=12)
-    with torch.no_grad():       # make every imported tensor distinguishable from any default initialisation
-        g = torch.Generator().manual_seed(12)
-        for p in clip.parameters():
-            p.copy_(torch.randn(p.shape, generator=g) * 0.05)
-    torch.save(clip.state_dict(), tmp_path / 'ViT-B-16.pt')
+    fx = load_golden('reference_boundary.pt')
+    g = torch.Generator().manual_seed(12)      # every imported tensor distinguishable from any default initialisation
+    clip = {k: torch.randn(shp, generator=g) * 0.05 for k, shp in fx['clip_vit_b16_shapes']}
+    torch.save(clip, tmp_path / 'ViT-B-16.pt')
     monkeypatch.setenv('LAVILA_CLIP_WEIGHTS_DIR', str(tmp_path))
-    monkeypatch.setattr(ref.models, 'load_openai_clip', lambda name, device='cpu': (clip, None))
     kw = dict(num_frames=4, timesformer_freeze_space=freeze, project_embed_dim=embed, temperature_init=0.07)
     with contextlib.redirect_stdout(io.StringIO()):
-        theirs = ref.models.CLIP_OPENAI_TIMESFORMER_BASE(**kw)
         ours = models.CLIP_OPENAI_TIMESFORMER_BASE(**kw)
-    a, b = ours.state_dict(), theirs.state_dict()
-    assert list(a) == list(b)
+    theirs = fx['pretrained_clip'][f'{embed}-{freeze}']
+
+    def digest(t):                             # oracle/gen_golden.py:_tensor_digest
+        t = t.detach().cpu().contiguous()
+        h = hashlib.sha256(f'{t.dtype}|{tuple(t.shape)}|'.encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+        return h.hexdigest()
+
+    a = ours.state_dict()
+    assert list(a) == theirs['keys']
     random_init = set() if embed == 512 else {'image_projection', 'text_projection'}    # normal_() draws, not imports
     for k in a:
         if k in random_init:
-            assert a[k].shape == b[k].shape
             continue
-        assert torch.equal(a[k], b[k]), k
+        assert digest(a[k]) == theirs['digest'][k], k
     if embed == 512:
-        assert torch.equal(a['logit_scale'], clip.logit_scale.data) and torch.equal(a['image_projection'], clip.visual.proj.data)
+        assert torch.equal(a['logit_scale'], clip['logit_scale']) and torch.equal(a['image_projection'], clip['visual.proj'])
     else:
         assert abs(float(a['logit_scale']) - float(torch.log(torch.tensor(1 / 0.07)))) < 1e-6
-    assert torch.equal(a['visual.blocks.3.attn.qkv.weight'], clip.visual.transformer.resblocks[3].attn.in_proj_weight.data)
-    assert torch.equal(a['transformer.resblocks.5.mlp.c_fc.weight'], clip.transformer.resblocks[5].mlp.c_fc.weight.data)
+    assert torch.equal(a['visual.blocks.3.attn.qkv.weight'], clip['visual.transformer.resblocks.3.attn.in_proj_weight'])
+    assert torch.equal(a['transformer.resblocks.5.mlp.c_fc.weight'], clip['transformer.resblocks.5.mlp.c_fc.weight'])
     flags_a = {k: p.requires_grad for k, p in ours.named_parameters()}
-    flags_b = {k: p.requires_grad for k, p in theirs.named_parameters()}
-    assert flags_a == flags_b
+    assert flags_a == theirs['requires_grad']
     if freeze:
         assert not flags_a['visual.blocks.0.attn.qkv.weight'] and flags_a['visual.blocks.0.timeattn.qkv.weight'] \
             and flags_a['visual.cls_token'] and flags_a['visual.temporal_embed']

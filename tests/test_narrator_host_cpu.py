@@ -134,24 +134,22 @@ def test_decoder_plan_and_generate_bookkeeping(variant, monkeypatch):
 
 def test_reference_state_dict_names_and_shapes():
     """Every key / shape / dtype of the reference's gated GPT2LMHeadModel (gpt2_gated.py, imported unmodified) exists in
-    lavila_amd.gpt2_gated.GPT2LMHeadModel and vice versa, for both cross-attention layouts."""
-    from oracle.ref_import import load_reference_narrator, reference_available
-    if not reference_available():
-        pytest.skip('reference not mounted')
+    lavila_amd.gpt2_gated.GPT2LMHeadModel and vice versa, for both cross-attention layouts (the reference's from
+    tests/golden/reference_boundary.pt)."""
     from transformers import GPT2Config
     from lavila_amd.gpt2_gated import GPT2LMHeadModel, augment_gpt2_config
-    ref = load_reference_narrator()
+    golden = load_golden('reference_boundary.pt')
     for freq, gated in ((1, True), (2, False), (3, True)):
         base = GPT2Config(vocab_size=97, n_positions=24, n_embd=128, n_layer=4, n_head=2, use_cache=False,
                           bos_token_id=96, eos_token_id=96)
-        theirs = ref.gpt2_gated.GPT2LMHeadModel(ref.gpt2_gated.augment_gpt2_config(base, cross_attn_freq=freq,
-                                                                                   gated_xattn=gated)).state_dict()
+        theirs = golden['gpt2_state_dict'][f'{freq}-{gated}']
         ours = GPT2LMHeadModel(augment_gpt2_config(base, cross_attn_freq=freq, gated_xattn=gated)).state_dict()
         assert set(ours) == set(theirs)
         for k in ours:
-            assert ours[k].shape == theirs[k].shape and ours[k].dtype == theirs[k].dtype, k
+            shape, dtype, value = theirs[k]
+            assert tuple(ours[k].shape) == shape and ours[k].dtype == dtype, k
             if k.endswith('.bias') and ours[k].dtype == torch.uint8 or k.endswith('masked_bias'):
-                assert torch.equal(ours[k], theirs[k]), k
+                assert torch.equal(ours[k], value), k
 
 
 def test_vclm_constructors_and_cpu_is_loud():
