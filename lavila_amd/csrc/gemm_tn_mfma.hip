@@ -160,6 +160,23 @@ __device__ __forceinline__ void gm_store16(void* p, uint4 v) {
 #define GM_EXP 0
 #endif
 
+// GM_AUDIT (debug build only, tests/test_gpu_gemm_tails.py): every wave counts the vector-memory stores its epilogue
+// ISSUES, at the issue sites, and records them with the vmcnt allowance the next tile's first K blocks use (see NS below).
+// Per lane: byte j of gm_aud_st = stores issued in row group j while the lane was live, gm_aud_cp = column-partial stores.
+#ifdef GM_AUDIT
+#define GM_AUD_STORE(j) (gm_aud_st += 1u << (8 * (j)))
+#define GM_AUD_COLPART() (++gm_aud_cp)
+constexpr int GM_AUDIT_CAP = 255;      // records per wave (one per tile boundary)
+__device__ __forceinline__ int gm_wave_max(int v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
+  return v;
+}
+#else
+#define GM_AUD_STORE(j) ((void)0)
+#define GM_AUD_COLPART() ((void)0)
+#endif
+
 // build-time shape of the aux_in epilogues (see `epilogue`): row groups requested up front, re-read of xA / wA
 #ifndef GM_UPFRONT_RES
 #define GM_UPFRONT_RES 4
@@ -379,6 +396,9 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 
   uint4 xA[8], xB[8], wA[4], wB[4];      // operand fragments of the K loop (declared here: the epilogue re-reads xA / wA)
   int par = 0;                            // ring half (slot offset 0 / 4) of the K block being multiplied
+#ifdef GM_AUDIT
+  uint32_t gm_aud_st = 0, gm_aud_cp = 0;
+#endif
 
   auto epilogue = [&](int tm, int tn, int ti) {
     const int64_t m0 = (int64_t)tm * TM;
@@ -415,7 +435,10 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = a16[4 * rq + e];
             if (EPI == 1) {
-              if (valid) *reinterpret_cast<float4*>(aux_out + o) = make_float4(v[0], v[1], v[2], v[3]);
+              if (valid) {
+                *reinterpret_cast<float4*>(aux_out + o) = make_float4(v[0], v[1], v[2], v[3]);
+                GM_AUD_STORE(j);
+              }
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
             }
@@ -437,7 +460,10 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
                 for (int e = 0; e < 4; ++e) csum[i * 16 + rq * 4 + e] += v[e];
               }
             }
-            if (valid) *reinterpret_cast<float4*>(Y + o) = make_float4(v[0], v[1], v[2], v[3]);
+            if (valid) {
+              *reinterpret_cast<float4*>(Y + o) = make_float4(v[0], v[1], v[2], v[3]);
+              GM_AUD_STORE(j);
+            }
           }
         }
       }
@@ -486,7 +512,11 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
           for (int jj = 0; jj < 2; ++jj) {
             const int64_t o = m * (int64_t)N + n0 + wn * 64 + i * 32 + 16 * jj + 8 * hi;
             gm_store16(Y + o, y4[i][jj]);
-            if (TWO_OUT && !(GM_EXP & 4)) gm_store16(aux_out + o, uv[i][jj]);      // (GM_EXP 4: timing experiment)
+            GM_AUD_STORE(j);
+            if (TWO_OUT && !(GM_EXP & 4)) {      // (GM_EXP 4: timing experiment)
+              gm_store16(aux_out + o, uv[i][jj]);
+              GM_AUD_STORE(j);
+            }
           }
       }
     };
@@ -599,6 +629,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       const int c = r5;
       const int col = (c >> 4) * 32 + ((c >> 2) & 3) * 8 + 4 * hi + (c & 3);
       colpart[(size_t)(tm * 2 + wm) * N + n0 + wn * 64 + col] = cs[0];
+      GM_AUD_COLPART();
     }
   };
 
@@ -617,6 +648,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   } while (0)
 #else
 #define GM_STAMP() do { } while (0)
+#endif
+#ifdef GM_AUDIT
+  // [gridDim.x][8 waves][1 + GM_AUDIT_CAP][4] ints behind the column partials (as GM_TRACE): a header {records} and, for
+  // every tile ordinal i >= 1, {tm, tn of tile i-1, stores the wave issued in tile i-1's epilogue, allowance used}
+  int* const audit = reinterpret_cast<int*>(colpart + ((EPI == 2 || EPI == 5) ? (size_t)2 * (ntiles / tiles_n) * N : 0)) +
+                     ((size_t)bid * 8 + wave) * (1 + GM_AUDIT_CAP) * 4;
+  int aud_n = 0, aud_rec[4] = {0, 0, 0, 0};
 #endif
   if (late) {
     my_tiles = 0;                               // as if the queues were drained
@@ -684,9 +722,16 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   init_acc(0);
   // One K block = four phases. A0 / A1 are added to the vmcnt allowance of the barriers in front of P0,P1 / P2,P3:
   // vector-memory operations retire in issue order, so in the first block(s) after an epilogue -- while the slot a
-  // barrier waits for was still filled BEFORE that epilogue -- the epilogue's NS result stores sit between the
-  // awaited fills and the newer ones and may stay in flight (waiting for them to be acknowledged would cost every
-  // tile ~2 us of idle matrix pipe).
+  // barrier waits for was still filled BEFORE that epilogue -- the epilogue's result stores sit between the awaited
+  // fills and the newer ones and may stay in flight (waiting for them to be acknowledged would cost every tile ~2 us of
+  // idle matrix pipe).
+  // INVARIANT: the allowance a wave uses after an epilogue is at most the number of vector-memory stores THAT WAVE
+  // issued in it (otherwise "all but the newest 10 + NS" lets some of the awaited fills still be in flight when the
+  // barrier opens and all eight waves read the slot). A full tile issues NS per wave (epilogues 2 / 5: 16 + the column
+  // partial). In a TAIL tile (m0 + TM > M) the stores of a 32-row group wholly at or behind M are skipped (`m < M`): a
+  // wave may issue fewer than NS, or none. So after a tail tile's epilogue every wave drains (vmcnt(0)) and the
+  // allowance is 0 -- one store drain per tail tile, only there. The GM_AUDIT build records, per wave and tile boundary,
+  // the stores counted at the issue sites and the allowance used (tests/test_gpu_gemm_tails.py checks slack <= issued).
   // (f32-class mode: its 32 / 64 wider stores would overflow the 6-bit vmcnt field together with the fills -- no
   // allowance there: the first blocks of the next tile also wait for the previous tile's stores)
   constexpr int NS = F32O ? 0 : (EPI == 1 || EPI == 4 ? 32 : 16);
@@ -730,6 +775,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   for (int i = 0; i < my_tiles; ++i) {
     int j = 0;
     if (i > 0) {                     // the slots read here were filled before the previous tile's epilogue
+#ifdef GM_AUDIT
+      if (lane == 0 && aud_n < GM_AUDIT_CAP) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) audit[4 * (1 + aud_n) + q] = aud_rec[q];
+      }
+      ++aud_n;
+#endif
       k_block(IS{}, IS{});
       if (nb > 1) k_block(IS{}, I0{});
       j = 2;
@@ -756,6 +808,21 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     int tm, tn;
     decode_tile(pair, tm, tn);
     epilogue(tm, tn, i);
+    // a tail tile's epilogue may have issued fewer than NS stores in this wave: no allowance after it (see NS above)
+    const bool tail = NS > 0 && __builtin_amdgcn_readfirstlane((int64_t)tm * TM + TM > M ? 1 : 0);
+    if (tail) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef GM_AUDIT
+    {
+      int issued = gm_wave_max((int)gm_aud_cp);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) issued += gm_wave_max((int)((gm_aud_st >> (8 * q)) & 255u));
+      aud_rec[0] = tm;
+      aud_rec[1] = tn;
+      aud_rec[2] = issued;
+      aud_rec[3] = tail ? 0 : NS;
+      gm_aud_st = gm_aud_cp = 0;
+    }
+#endif
     GM_STAMP();
     init_acc(i + 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -764,6 +831,9 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #undef GM_BAR
 #undef GM_PHASE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // drain the run-ahead fills before this workgroup's LDS is freed
+#ifdef GM_AUDIT
+  if (lane == 0) audit[0] = aud_n;
+#endif
   // the last pull's reply is never consumed: keep its register reserved until the drain above has delivered it
   asm volatile("" ::"v"(pend));
   if (dyn && wave == 0 && lane == 0) {
@@ -820,6 +890,37 @@ extern "C" int lvl_linear_tn_trace_epi(const void* x, const void* w, const float
     case 3: return launch_tn<3>(x, w, bias, y, nullptr, aux_in, (float*)trace, M, N, K, nullptr, st);
     case 4: return launch_tn<4>(x, w, bias, y, aux_out, nullptr, (float*)trace, M, N, K, nullptr, st);
     case 5: return launch_tn<5>(x, w, nullptr, y, nullptr, aux_in, (float*)trace, M, N, K, nullptr, st);
+  }
+  return -1;
+}
+#endif
+
+#ifdef GM_AUDIT
+// lvl_linear_tn's launch (bf16 epilogues 0-5, f32-class 0-3, static or dynamic schedule) with the store-count records of
+// every wave in `audit` (layout at the kernel's GM_AUDIT block; epilogues 2 / 5: behind their [2 * tiles_m][N] column
+// partials, which are left unreduced)
+extern "C" int lvl_linear_tn_audit_cap() { return GM_AUDIT_CAP; }
+extern "C" int lvl_linear_tn_audit(const void* x, const void* w, const float* bias, void* y, void* aux_out,
+                                   const void* aux_in, void* audit, uint32_t* sched, int64_t M, int N, int K, int epilogue,
+                                   int dtype, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  float* a = (float*)audit;
+  if (dtype == LVL_F32) {
+    switch (epilogue) {
+      case 0: return launch_tn<0, true>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
+      case 1: return launch_tn<1, true>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
+      case 2: return launch_tn<2, true>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
+      case 3: return launch_tn<3, true>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
+    }
+    return -1;
+  }
+  switch (epilogue) {
+    case 0: return launch_tn<0>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
+    case 1: return launch_tn<1>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
+    case 2: return launch_tn<2>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
+    case 3: return launch_tn<3>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
+    case 4: return launch_tn<4>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
+    case 5: return launch_tn<5>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
   }
   return -1;
 }
