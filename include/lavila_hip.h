@@ -169,8 +169,9 @@ int lvl_debug_f32_generic(int on);
  * kernels (csrc/attn_space_stream.hip: a workgroup owns 128 queries -- or keys, in the dK/dV kernel -- and streams the
  * other side through double-buffered 64-row LDS images; online softmax forward, lse-recomputed P backward) instead of
  * keeping the whole group LDS-resident with one workgroup per compute unit. Test / measurement hook: mode 1 = streaming
- * kernels for EVERY space group, -1 = never (the LDS-resident kernels up to 592 keys, as in round 3), 0 = the shipped
- * choice. Results agree to rounding (bf16) / f32 summation order. */
+ * kernels for EVERY space group, -1 = never (the LDS-resident kernels as in round 3: forward up to 592 keys, backward up
+ * to 577, larger groups on the generic kernels), 0 = the shipped choice. Results agree to rounding (bf16) / f32
+ * summation order. */
 int lvl_debug_space_stream(int mode);
 /* Measurement hook, bf16 streaming kernels: bit 0 = the forward's 3-workgroup cut with a three-stage LDS-DMA ring (default:
  * 4 workgroups per compute unit, two stages); bit 2 = register staging instead of the LDS-DMA rings (all three kernels;
