@@ -653,24 +653,37 @@ _LN_EXACT_PROBE = r"""
 import sys, torch
 from lavila_amd import ops
 torch.manual_seed(0)
-cols = int(sys.argv[2])
-x = torch.randn(3001, cols, device='cuda').bfloat16(); y = torch.randn_like(x)
+cols, rows = int(sys.argv[2]), int(sys.argv[3])
+x = torch.randn(rows, cols, device='cuda').bfloat16(); y = torch.randn_like(x)
 g = torch.randn(cols, device='cuda'); b = torch.randn(cols, device='cuda'); yb = torch.randn(cols, device='cuda')
 dy = torch.randn_like(x); dadd = torch.randn_like(x)
+def rec(t):
+    # up to 4 M elements the tensor itself; beyond, two position-weighted int64 sums of its bit patterns (odd weights:
+    # any single differing element changes both), so that 200 960-row outputs need not leave the device
+    if t.numel() <= 1 << 22:
+        return t.cpu()
+    v = t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32).flatten().long()
+    i = torch.arange(v.numel(), device=t.device)
+    return (tuple(t.shape), int((v * (2 * i + 1)).sum()), int((v * ((i * 2654435761) % (1 << 31) | 1)).sum()))
 outs = []
-h, _, mean, rstd = ops.layernorm_fwd_raw(x, None, None, g, b, 1e-5, False); outs += [h, mean, rstd]
-h2, _, m2, r2 = ops.layernorm_fwd_raw(x, y, yb, g, b, 1e-5, False); outs += [h2, m2, r2]
-h3, _, m3, r3 = ops.layernorm_fwd_raw(x, y, None, g, b, 1e-5, False); outs += [h3, m3, r3]
-outs += [t for t in ops.layernorm_bwd_raw(dy, x, None, None, g, mean, rstd, None, False) if t is not None]
-outs += [t for t in ops.layernorm_bwd_raw(dy, x, None, None, g, mean, rstd, dadd, True) if t is not None]
-outs += [t for t in ops.layernorm_bwd_raw(dy, x, y, yb, g, m2, r2, None, True) if t is not None]
-outs += [t for t in ops.layernorm_bwd_raw(dy, x, y, yb, g, m2, r2, dadd, True, True) if t is not None]
-torch.save([o.cpu() for o in outs], sys.argv[1])
+def keep(ts):
+    outs.extend(rec(t) for t in ts if t is not None)
+h, _, mean, rstd = ops.layernorm_fwd_raw(x, None, None, g, b, 1e-5, False); keep([h, mean, rstd])
+h2, _, m2, r2 = ops.layernorm_fwd_raw(x, y, yb, g, b, 1e-5, False); keep([h2, m2, r2])
+h3, _, m3, r3 = ops.layernorm_fwd_raw(x, y, None, g, b, 1e-5, False); keep([h3, m3, r3])
+keep(ops.layernorm_bwd_raw(dy, x, None, None, g, mean, rstd, None, False))
+keep(ops.layernorm_bwd_raw(dy, x, None, None, g, mean, rstd, dadd, True))
+keep(ops.layernorm_bwd_raw(dy, x, y, yb, g, m2, r2, None, True))
+keep(ops.layernorm_bwd_raw(dy, x, y, yb, g, m2, r2, dadd, True, True))
+torch.save(outs, sys.argv[1])
 """
 
 
+# 3001 rows: one pass of the backward's 768 workgroups; 12 289: one row past the two-operand forward's cap, four passes of
+# the backward; 200 960: the benched video tower, per-wave row chains in every kernel
+@pytest.mark.parametrize('rows', [3001, 12289, 200960])
 @pytest.mark.parametrize('cols', [768, 512, 1024])
-def test_exact_width_layernorm_kernels_equal_the_general_ones_bit_for_bit(cols, tmp_path):
+def test_exact_width_layernorm_kernels_equal_the_general_ones_bit_for_bit(cols, rows, tmp_path):
     """lvl_layernorm_fwd / bwd take branch-free exact-width instantiations (ln_fwd_exact_kernel / ln_bwd_exact_kernel) at
     cols = VPL * 256 for the operand combinations of the training step, the general kernels otherwise -- and activation
     checkpointing (timesformer.py:173-187) may recompute a forward through the other one. Both families write their fused
@@ -682,12 +695,15 @@ def test_exact_width_layernorm_kernels_equal_the_general_ones_bit_for_bit(cols, 
     res = []
     for e in ('0', '1'):
         out = str(tmp_path / f'ln_{e}.pt')
-        subprocess.run([sys.executable, '-c', _LN_EXACT_PROBE, out, str(cols)], check=True, cwd=root,
+        subprocess.run([sys.executable, '-c', _LN_EXACT_PROBE, out, str(cols), str(rows)], check=True, cwd=root,
                        env=dict(os.environ, LAVILA_LN_EXACT=e, PYTHONPATH=root), timeout=600)
         res.append(torch.load(out))
     assert len(res[0]) == len(res[1]) and len(res[0]) >= 20
     for i, (a, b) in enumerate(zip(*res)):
-        assert torch.equal(a, b), (i, (a.float() - b.float()).abs().max().item())
+        if isinstance(a, torch.Tensor):
+            assert torch.equal(a, b), (i, (a.float() - b.float()).abs().max().item())
+        else:
+            assert a == b, (i, a, b)
 
 
 def test_cast_transpose_multi_equals_the_single_launches_and_refresh_follows_the_weights():
