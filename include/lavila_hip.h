@@ -307,9 +307,6 @@ int lvl_linear_skinny_f32c(const void* x3, const void* w3, const float* bias, fl
 int lvl_linear_skinny_ln(const void* res, const void* y, const float* gate, const float* gamma, const float* beta,
                          float eps, void* res_out, const void* w, const float* bias, void* out, int M, int N, int K,
                          int act, void* stream);
-/* Measurement hook (tools/probe_skinny.py): selects another workgroup tiling / k-step assignment of lvl_linear_skinny for
- * shapes that allow it (0 = the shipped choice). Results are the same up to f32 summation order. */
-int lvl_debug_skinny_variant(int variant);
 int lvl_gpt2_embed(const int64_t* ids, const void* wte, const void* wpe, const int* pos_dev, void* out, int rows, int L,
                    int D, int vocab, int positions, int dtype, void* stream);
 int lvl_gated_add_layernorm(const void* res, const void* y, const float* gate, const float* gamma, const float* beta,
@@ -319,9 +316,6 @@ int lvl_decode_self_attn(const void* qkv, void* cache, const int* pos_dev, void*
                          void* stream);
 int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, int qrep, int Tk, int H, int dtype,
                             void* stream);
-/* Measurement hook: n = 4 / 8 / 16 forces lvl_cross_attn_rows_fwd's VALU shared-context kernel with n waves per
- * workgroup (-1: 16) where the MFMA kernel would run (bf16, qrep >= 2, Tk <= 256); 0 = the shipped choice. */
-int lvl_debug_cross_attn_waves(int waves);
 
 /* lvl_sample_next_token: everything VCLM_HF.generate does with one step's logits (narrator.py:122-137 and the warpers
  * of :368-389 = transformers' Temperature / TopK / TopP logits warpers with min_tokens_to_keep = 1), one workgroup per

@@ -243,16 +243,8 @@ extern "C" int lvl_cls_attn_fwd(const void* q, const void* kv, void* out, float*
   return LVL_OK;
 }
 
-namespace { std::atomic<int> g_shared_waves{0}; }
-
 int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
                                hipStream_t st);          // cross_attn_mfma.hip
-
-// measurement hook (tools/probe_decode_kernels.py): waves per workgroup of the shared-context kernel (0 = by qrep)
-extern "C" int lvl_debug_cross_attn_waves(int waves) {
-  g_shared_waves.store(waves, std::memory_order_relaxed);
-  return LVL_OK;
-}
 
 extern "C" int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, int qrep, int Tk, int H,
                                        int dtype, void* stream) {
@@ -263,25 +255,24 @@ extern "C" int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out,
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(kv) && lvl_aligned16(out),
               "cross_attn_rows_fwd: pointers must be 16-byte aligned");
   if (rows == 0) return LVL_OK;
-  // bf16, several rows per context, <= 256 keys: the MFMA kernel (lvl_debug_cross_attn_waves(n != 0) keeps the VALU form)
-  if (dtype == LVL_BF16 && qrep >= 2 && Tk <= 256 && g_shared_waves.load(std::memory_order_relaxed) == 0)
+  // bf16, several rows per context, <= 256 keys: the MFMA kernel
+  if (dtype == LVL_BF16 && qrep >= 2 && Tk <= 256)
     return lvl_launch_cross_attn_mfma(q, kv, out, rows / qrep, qrep, Tk, H, (hipStream_t)stream);
   const size_t lds = (size_t)Tk * 128 * (dtype == LVL_F32 ? 4 : 2);
   if (qrep >= 2 && lds <= 150 * 1024) {           // the context's keys / values fit LDS: read them once per (context, head)
     const unsigned grid = (unsigned)(rows / qrep * H);
-    int nw = g_shared_waves.load(std::memory_order_relaxed);
-    if (nw <= 0) nw = 16;      // measured (profiles/r03_decode_kernels.json): 16 waves win from qrep = 2 on (19 vs 25 us)
-#define LVL_CA(TT, NWV)                                                                                       \
+    // 16 waves per workgroup: they win from qrep = 2 on (19 vs 25 us, profiles/r03_decode_kernels.json)
+#define LVL_CA(TT)                                                                                            \
   do {                                                                                                        \
     if (lds > 64 * 1024)                                                                                      \
-      if (int rc = lvl_allow_lds<cross_attn_shared_kernel<TT, NWV>>()) return rc;                             \
-    hipLaunchKernelGGL((cross_attn_shared_kernel<TT, NWV>), dim3(grid), dim3(64 * NWV), lds, (hipStream_t)stream, \
+      if (int rc = lvl_allow_lds<cross_attn_shared_kernel<TT, 16>>()) return rc;                              \
+    hipLaunchKernelGGL((cross_attn_shared_kernel<TT, 16>), dim3(grid), dim3(64 * 16), lds, (hipStream_t)stream, \
                        (const TT*)q, (const TT*)kv, (TT*)out, Tk, H, qrep);                                   \
   } while (0)
     if (dtype == LVL_F32) {
-      if (nw >= 16) LVL_CA(float, 16); else if (nw >= 8) LVL_CA(float, 8); else LVL_CA(float, 4);
+      LVL_CA(float);
     } else if (dtype == LVL_BF16) {
-      if (nw >= 16) LVL_CA(bf16_t, 16); else if (nw >= 8) LVL_CA(bf16_t, 8); else LVL_CA(bf16_t, 4);
+      LVL_CA(bf16_t);
     } else {
       return lvl_fail(LVL_EINVAL, "unknown dtype %d", dtype);
     }

@@ -556,8 +556,6 @@ int launch_mid(const void* x, const void* w, const float* bias, void* y, int M, 
   return LVL_OK;
 }
 
-std::atomic<int> g_variant{0};      // lvl_debug_skinny_variant: 0 = the shipped choice
-
 }  // namespace
 
 extern "C" int lvl_linear_skinny(const void* x, const void* w, const float* bias, void* y, int M, int N, int K, int act,
@@ -570,36 +568,12 @@ extern "C" int lvl_linear_skinny(const void* x, const void* w, const float* bias
   LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(w) && lvl_aligned16(y) && lvl_aligned16(bias),
               "linear_skinny: pointers must be 16-byte aligned");
   if (M == 0) return LVL_OK;
-  // Output block per workgroup, from measurements on the decoder's shapes (tools/probe_skinny.py,
-  // profiles/r03_skinny_variants.json): up to 128 rows a 16 x 16 block with PAIRED k-steps (a wave reads whole 128-byte
-  // lines: 12.6 -> 7.6 us at K = 3072), or 32 rows x 64 columns once N >= 2048 gives >= 64 strips; beyond 128 rows
-  // (64 clips x 10 sampled captions = 640) 64 rows x 32 columns, which halves the re-reads of the weight strip
-  // (25.6 -> 19.3 us for [768 x 3072]), or 64 x 64 for N >= 2048.
+  // Output block per workgroup, from measurements on the decoder's shapes (profiles/r03_skinny_variants.json; the probe
+  // that timed the tilings, tools/probe_skinny.py, is in the project's history): up to 128 rows a 16 x 16 block with
+  // PAIRED k-steps (a wave reads whole 128-byte lines: 12.6 -> 7.6 us at K = 3072), or 32 rows x 64 columns once
+  // N >= 2048 gives >= 64 strips; beyond 128 rows (64 clips x 10 sampled captions = 640) 64 rows x 32 columns, which
+  // halves the re-reads of the weight strip (25.6 -> 19.3 us for [768 x 3072]), or 64 x 64 for N >= 2048.
   const hipStream_t st = (hipStream_t)stream;
-  switch (g_variant.load(std::memory_order_relaxed)) {       // measurement variants (tools/probe_skinny.py)
-    case 1: if (N % 32 == 0) return launch_skinny<2, 2, true>(x, w, bias, y, M, N, K, act, st); break;
-    case 2: if (N % 32 == 0) return launch_skinny<2, 4, false>(x, w, bias, y, M, N, K, act, st); break;
-    case 3: if (N % 64 == 0) return launch_skinny<4, 4, false>(x, w, bias, y, M, N, K, act, st); break;
-    case 4: if (N % 32 == 0) return launch_skinny<2, 4, true>(x, w, bias, y, M, N, K, act, st); break;
-    case 5: if (N % 32 == 0) return launch_skinny<2, 1, true>(x, w, bias, y, M, N, K, act, st); break;
-    case 6: return launch_skinny<1, 1, true>(x, w, bias, y, M, N, K, act, st);
-    case 7: if (N % 64 == 0) return launch_skinny<4, 2, false>(x, w, bias, y, M, N, K, act, st); break;
-    case 8: if (N % 32 == 0) return launch_skinny<2, 2, false>(x, w, bias, y, M, N, K, act, st); break;
-    case 9: return launch_skinny<1, 1, false>(x, w, bias, y, M, N, K, act, st);
-    case 10: if (N % 64 == 0) return launch_skinny<4, 4, false, 3>(x, w, bias, y, M, N, K, act, st); break;
-    case 11: if (N % 64 == 0) return launch_skinny<4, 4, false, 4>(x, w, bias, y, M, N, K, act, st); break;
-    case 12: if (N % 64 == 0) return launch_skinny<4, 4, true, 4>(x, w, bias, y, M, N, K, act, st); break;
-    case 13: if (N % 32 == 0) return launch_skinny<2, 4, false, 4>(x, w, bias, y, M, N, K, act, st); break;
-    case 14: if (K % 64 == 0) return launch_mid<2, 4, 2, 2, 5>(x, w, bias, y, M, N, K, act, st); break;   // 64 x 128, 5 blocks in flight
-    case 15: if (K % 64 == 0) return launch_mid<2, 4, 2, 2, 3>(x, w, bias, y, M, N, K, act, st); break;   // 64 x 128 (8 waves)
-    case 16: if (K % 64 == 0) return launch_mid<2, 2, 2, 2, 3>(x, w, bias, y, M, N, K, act, st); break;   // 64 x 64 (4 waves)
-    case 17: if (K % 64 == 0) return launch_mid<2, 2, 2, 2, 6>(x, w, bias, y, M, N, K, act, st); break;   // 64 x 64, 6 blocks in flight
-    case 18: if (K % 64 == 0) return launch_mid<2, 2, 2, 2, 3, 2>(x, w, bias, y, M, N, K, act, st); break;   // 64 x 64, two K groups
-    case 19: if (K % 64 == 0) return launch_mid<2, 2, 1, 2, 3, 1>(x, w, bias, y, M, N, K, act, st); break;   // 32 x 64
-    case 20: if (K % 128 == 0) return launch_mid<2, 2, 1, 2, 3, 2>(x, w, bias, y, M, N, K, act, st); break;  // 32 x 64, two K groups
-    case 21: if (K % 128 == 0) return launch_mid<2, 2, 2, 1, 3, 2>(x, w, bias, y, M, N, K, act, st); break;  // 64 x 32, two K groups
-    default: break;
-  }
   if (K % 64 == 0) {
     // the LDS-staged kernel where whole-line loads and operand reuse decide (in-graph times, profiles/r03_skinny_variants.json):
     // lm_head [50432 x 768] at <= 128 rows 17.3 us (strips 40.6, the 256-column-panel kernel 31.6, library 16.3); beyond
@@ -646,11 +620,6 @@ extern "C" int lvl_linear_skinny_f32c(const void* x3, const void* w3, const floa
   }
   if (N >= 2048 && N % 64 == 0) return launch_skinny<4, 2, false, 6, true>(x3, w3, bias, y, M, N, K3, act, st);
   return launch_skinny<1, 1, true, 6, true>(x3, w3, bias, y, M, N, K3, act, st);
-}
-
-extern "C" int lvl_debug_skinny_variant(int v) {
-  g_variant.store(v, std::memory_order_relaxed);
-  return LVL_OK;
 }
 
 extern "C" int lvl_linear_skinny_ln(const void* res, const void* y, const float* gate, const float* gamma,

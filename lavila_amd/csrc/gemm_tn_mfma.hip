@@ -133,32 +133,11 @@ __device__ __forceinline__ uint4 widen_pair(uint2 a, uint2 b) {
   return make_uint4(r0[0], r1[0], r0[1], r1[1]);
 }
 
-// Result stores of the epilogue (bf16 path). GM_STORE_POLICY picks the cache policy of the 16-byte stores (build-time A/B,
-// tools/probe_gemm_store_policy.py): 0 plain, 1 nt, 2 sc1, 3 sc0 sc1. What the flavours do on gfx950 (MI355X_MICROARCH.md,
-// "stores of each flavour"): plain / nt keep the written line in the XCD's L2, sc1 / sc0 sc1 drop it -- a 256 x 256 tile
-// leaves 128-256 KB per workgroup, 4-8 MB per round per XCD, against a 4 MiB L2 that also has to hold the X and W panels.
-#ifndef GM_STORE_POLICY
-#define GM_STORE_POLICY 0
-#endif
-__device__ __forceinline__ void gm_store16(void* p, uint4 v) {
-#if GM_STORE_POLICY == 0
-  *reinterpret_cast<uint4*>(p) = v;
-#elif GM_STORE_POLICY == 1
-  __builtin_nontemporal_store(__builtin_bit_cast(lvl_u32x4, v), reinterpret_cast<lvl_u32x4*>(p));
-#elif GM_STORE_POLICY == 2
-  // s_nop 1 inside the string: a store of more than 64 bits reads its data registers for two more wait states, and the
-  // hazard recogniser does not look into asm (without it the next VALU write to v corrupts the stored value: measured)
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(__builtin_bit_cast(lvl_u32x4, v)) : "memory");
-#else
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(__builtin_bit_cast(lvl_u32x4, v)) : "memory");
-#endif
-}
-
-// GM_EXP (timing experiments only, results are WRONG; tools/probe_gemm_variants.py): 1 = no s_barrier in the K loop, 2 = no vmcnt
-// wait in front of the barriers, 4 = epilogues 1 / 4 skip their second result store, 8 = epilogue 4 skips the QuickGELU arithmetic
-#ifndef GM_EXP
-#define GM_EXP 0
-#endif
+// Result stores of the epilogue (bf16 path): plain write-back. nt / sc1 / sc0 sc1 stores measured slower on every shape of a
+// block (round 6, profiles/r06_gemm_store_policy.txt). What the flavours do on gfx950 (MI355X_MICROARCH.md, "stores of each
+// flavour"): plain / nt keep the written line in the XCD's L2, sc1 / sc0 sc1 drop it -- a 256 x 256 tile leaves 128-256 KB
+// per workgroup, 4-8 MB per round per XCD, against a 4 MiB L2 that also has to hold the X and W panels.
+__device__ __forceinline__ void gm_store16(void* p, uint4 v) { *reinterpret_cast<uint4*>(p) = v; }
 
 // GM_AUDIT (debug build only, tests/test_gpu_gemm_tails.py): every wave counts the vector-memory stores its epilogue
 // ISSUES, at the issue sites, and records them with the vmcnt allowance the next tile's first K blocks use (see NS below).
@@ -175,17 +154,6 @@ __device__ __forceinline__ int gm_wave_max(int v) {
 #else
 #define GM_AUD_STORE(j) ((void)0)
 #define GM_AUD_COLPART() ((void)0)
-#endif
-
-// build-time shape of the aux_in epilogues (see `epilogue`): row groups requested up front, re-read of xA / wA
-#ifndef GM_UPFRONT_RES
-#define GM_UPFRONT_RES 4
-#endif
-#ifndef GM_UPFRONT_COLSUM
-#define GM_UPFRONT_COLSUM 3
-#endif
-#ifndef GM_REREAD_RES
-#define GM_REREAD_RES 1
 #endif
 
 template <int EPI, bool F32O>
@@ -476,12 +444,11 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     // epilogue on the same shape). So the aux rows of ALL FOUR row groups are requested, and every one of them has landed
     // (`landed`: a register use the compiler has to wait for), before the first store leaves; from there on nothing is
     // pending and packing and stores interleave freely. Registers: UPFRONT groups are requested at once, the rest when
-    // group 0 is packed and its accumulators are dead; HOLD groups are packed before the first store; with REREAD the next
-    // tile's first fragments (xA / wA, read during the last K block) are not carried across the epilogue but read again
-    // from the ring under the last stores (the column-sum epilogues hold 32 running sums on top of the aux rows).
-    constexpr int UPFRONT = COLSUM ? GM_UPFRONT_COLSUM : GM_UPFRONT_RES;
+    // group 0 is packed and its accumulators are dead; HOLD groups are packed before the first store; the next tile's
+    // first fragments (xA / wA, read during the last K block) are not carried across the epilogue but read again from the
+    // ring under the last stores (the column-sum epilogues hold 32 running sums on top of the aux rows).
+    constexpr int UPFRONT = COLSUM ? 3 : 4;
     constexpr int HOLD = UPFRONT == 4 ? 1 : 2;
-    constexpr bool REREAD = COLSUM ? true : (GM_REREAD_RES != 0);
     uint2 ub[AUXIN ? 4 : 1][8];
     auto load_u = [&](int j, uint2 (&dst)[8]) {
       const int64_t m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + r5;
@@ -513,7 +480,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
             const int64_t o = m * (int64_t)N + n0 + wn * 64 + i * 32 + 16 * jj + 8 * hi;
             gm_store16(Y + o, y4[i][jj]);
             GM_AUD_STORE(j);
-            if (TWO_OUT && !(GM_EXP & 4)) {      // (GM_EXP 4: timing experiment)
+            if (TWO_OUT) {
               gm_store16(aux_out + o, uv[i][jj]);
               GM_AUD_STORE(j);
             }
@@ -549,8 +516,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               float y, r;
-              if (GM_EXP & 8) { y = v[e]; r = v[e]; } else qgelu1(v[e], y, r);      // (GM_EXP 8: timing experiment)
-              g[e] = (GM_EXP & 8) ? r : qgelu_grad1(y, r);
+              qgelu1(v[e], y, r);
+              g[e] = qgelu_grad1(y, r);
               v[e] = y;
             }
             upk[rq] = make_uint2(f32x2_to_bf16x2(g[0], g[1]), f32x2_to_bf16x2(g[2], g[3]));
@@ -596,7 +563,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
           for (int jp = 0; jp < HOLD; ++jp) store_group(jp, yv[jp]);
         }
-        if (REREAD && j == 3) {
+        if (j == 3) {                      // re-read of xA / wA
           __builtin_amdgcn_sched_barrier(0);
           read_x(par + S_X0, xA);
           read_w(par + S_W0, wA);
@@ -696,8 +663,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   // fence would drain the run-ahead fills.
 #define GM_BAR(N)                                                     \
   do {                                                                \
-    if (!(GM_EXP & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");          \
-    if (!(GM_EXP & 1)) __builtin_amdgcn_s_barrier();                  \
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");          \
+    __builtin_amdgcn_s_barrier();                                     \
     asm volatile("" ::: "memory");                                    \
     __builtin_amdgcn_sched_barrier(0);                                \
   } while (0)

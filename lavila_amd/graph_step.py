@@ -36,7 +36,7 @@ Limits, loudly: `update_freq` (gradient accumulation) other than 1, stochastic d
 replay is not advanced here), a changing batch shape, activation checkpointing, and DistributedDataParallel WRAPPERS:
 DDP's bucket all-reduces would be launched from inside the captured backward, and with collectives pending torch's NCCL
 watchdog thread polls their events while the stream is capturing -- this ROCm build answers hipErrorStreamCaptureUnsupported
-and aborts (tried on a one-rank RCCL group: tools/gpu_runs/gpu_r4o.sh).
+and aborts (tried on a one-rank RCCL group: git show 06298df:tools/gpu_runs/gpu_r4o.sh).
 
 Multi-GPU jobs (round 5): hand over the BARE module with a process group initialised. The step then keeps every
 collective OUTSIDE the captures: the iteration is recorded as a chain  graph | collective | graph | ... | graph  -- the

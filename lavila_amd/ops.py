@@ -339,18 +339,15 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw, db
 
 
-# What the fused MLP keeps for its backward in bf16: quickgelu'(u) (default) or the pre-activation u (LAVILA_GELU_DERIV=0).
-GELU_DERIV = os.environ.get('LAVILA_GELU_DERIV', '1') != '0'
-
-
 class _MlpFn(torch.autograd.Function):
     """y = fc2(QuickGELU(fc1(x) + b1)) without fc2's bias (the caller leaves it pending for the next fused
     residual + LayerNorm): timesformer.py:52-58 / openai_model.py:189-192. Two lvl_linear_tn calls forward (the
     first one adds the bias, applies the activation and keeps what the backward needs), and in backward the QuickGELU
     derivative and the fc1 bias gradient are the epilogue of fc2's input-gradient GEMM: the [rows, 4D] tensors are
-    touched by GEMM epilogues only. What is kept (GELU_DERIV): bf16 keeps quickgelu'(u) itself -- the forward epilogue
-    has sigmoid(1.702 u) in a register, the backward epilogue then is one multiply (LVL_EPI_BIAS_QUICKGELU_DERIV /
-    LVL_EPI_MUL_AUX_COLSUM; LAVILA_GELU_DERIV=0 keeps the pre-activation u as the f32-class mode always does)."""
+    touched by GEMM epilogues only. What is kept: bf16 keeps quickgelu'(u) itself -- the forward epilogue has
+    sigmoid(1.702 u) in a register, the backward epilogue then is one multiply (LVL_EPI_BIAS_QUICKGELU_DERIV /
+    LVL_EPI_MUL_AUX_COLSUM); the f32-class mode keeps the pre-activation u (LVL_EPI_BIAS_QUICKGELU /
+    LVL_EPI_QUICKGELU_BWD)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2):
@@ -360,9 +357,8 @@ class _MlpFn(torch.autograd.Function):
         f32 = ctx.f32 = x.dtype == torch.float32        # f32-class mode: term images in, float32 u / a / y
         w1b, w1t = weight_copies(w1, f32)
         w2b, w2t = weight_copies(w2, f32)
-        ctx.deriv = GELU_DERIV and not f32
         a, u = linear_tn_raw(split3(x2, 0) if f32 else x2, w1b, _f32(b1),
-                             C.EPI_BIAS_QUICKGELU_DERIV if ctx.deriv else C.EPI_BIAS_QUICKGELU, f32=f32)
+                             C.EPI_BIAS_QUICKGELU if f32 else C.EPI_BIAS_QUICKGELU_DERIV, f32=f32)
         y = linear_tn_raw(split3(a, 0) if f32 else a, w2b, None, C.EPI_BIAS, f32=f32)
         ctx.save_for_backward(x2, u, a, w1t, w2t)
         ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, x.shape)
@@ -383,7 +379,7 @@ class _MlpFn(torch.autograd.Function):
                   if ctx.needs_input_grad[0] else None)
             dw1 = _wgrad_f32(du, x2, w1dt) if ctx.needs_input_grad[1] else None
             return dx, dw1, (db1.to(b1dt) if (b1dt is not None and ctx.needs_input_grad[2]) else None), dw2
-        du, db1 = linear_tn_raw(dy2, w2t, None, C.EPI_MUL_AUX_COLSUM if ctx.deriv else C.EPI_QUICKGELU_BWD, aux_in=u)
+        du, db1 = linear_tn_raw(dy2, w2t, None, C.EPI_MUL_AUX_COLSUM, aux_in=u)
         dw2 = _wgrad(dy2, a, w2dt) if ctx.needs_input_grad[3] else None
         dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
         dw1 = _wgrad(du, x2, w1dt) if ctx.needs_input_grad[1] else None
@@ -528,8 +524,9 @@ def linear_f32_rows(x2, w3, bias=None, act=None):
 # the activation's gradient, each Function computing it from what it already has (a [D] x [D, D] vector-matrix product,
 # lvl_vec_mat_f32, a few microseconds) instead of a 300 MB pass over dout per attention. Exact in real arithmetic; in
 # floating point it is the more accurate of the two (float32 sums of float32 column sums against sums of bf16-rounded
-# rows). LAVILA_COLSUM_TOKENS=0 switches the tokens off (the attention backward then reduces dout itself, as before).
-COLSUM_TOKENS = os.environ.get('LAVILA_COLSUM_TOKENS', '1') != '0'
+# rows). COLSUM_TOKENS = False switches the tokens off (the attention backward then reduces dout itself, as before): the
+# tests compare the two paths.
+COLSUM_TOKENS = True
 
 
 def vec_mat(v, weight):
@@ -811,8 +808,7 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
         w1b, w1t = weight_copies(w1)
         w2b, w2t = weight_copies(w2)
-        ctx.deriv = GELU_DERIV
-        a, u = linear_tn_raw(x2, w1b, _f32(b1), C.EPI_BIAS_QUICKGELU_DERIV if ctx.deriv else C.EPI_BIAS_QUICKGELU)
+        a, u = linear_tn_raw(x2, w1b, _f32(b1), C.EPI_BIAS_QUICKGELU_DERIV)
         s = linear_tn_raw(a, w2b, _f32(b2), C.EPI_BIAS_RESIDUAL, aux_in=res2)
         g = _f32(gamma)
         h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, _f32(beta), eps, False)
@@ -829,8 +825,7 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
         dsum, dg, dbeta, dcol = layernorm_bwd_raw(dh.reshape(s.shape).contiguous(), s, None, None, g, mean, rstd, dadd,
                                                   b2dt is not None)
         with torch.autocast('cuda', enabled=False):
-            du, db1 = linear_tn_raw(dsum, w2t, None, C.EPI_MUL_AUX_COLSUM if ctx.deriv else C.EPI_QUICKGELU_BWD,
-                                    aux_in=u)
+            du, db1 = linear_tn_raw(dsum, w2t, None, C.EPI_MUL_AUX_COLSUM, aux_in=u)
             dw2 = _wgrad(dsum, a, w2dt) if ctx.needs_input_grad[3] else None
             dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
             dw1 = _wgrad(du, x2, w1dt) if ctx.needs_input_grad[1] else None
@@ -961,9 +956,6 @@ def patchify(video: torch.Tensor, patch: int, dtype: torch.dtype, frame_major: b
     return out
 
 
-EMBED_BWD_KERNEL = os.environ.get('LAVILA_EMBED_BWD_KERNEL', '1') != '0'      # 0: framework reductions (A/B)
-
-
 class _EmbedTokensFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pe, cls_token, pos_embed, temporal_embed, frames, n_per_frame):
@@ -982,7 +974,7 @@ class _EmbedTokensFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx):
         B, Fr, N, D, num_frames = ctx.dims
-        if EMBED_BWD_KERNEL and dx.is_cuda and dx.dtype in (torch.bfloat16, torch.float32) and D % 8 == 0 and B > 0:
+        if dx.is_cuda and dx.dtype in (torch.bfloat16, torch.float32) and D % 8 == 0 and B > 0:
             # one pass over dx (lvl_embed_tokens_bwd) instead of a float32 copy of it and three framework reductions
             dx = dx.contiguous()
             dpos = torch.empty(1, N + 1, D, dtype=torch.float32, device=dx.device)
@@ -1005,9 +997,6 @@ class _EmbedTokensFn(torch.autograd.Function):
 
 def embed_tokens(pe, cls_token, pos_embed, temporal_embed, frames, n_per_frame):
     return _EmbedTokensFn.apply(lowp(pe), cls_token, pos_embed, temporal_embed, frames, n_per_frame)
-
-
-TEXT_EMBED_KERNEL = os.environ.get('LAVILA_TEXT_EMBED_KERNEL', '1') != '0'
 
 
 class _TextEmbedFn(torch.autograd.Function):
@@ -1046,7 +1035,7 @@ def text_embed(text, table, pos, out_dtype):
     """CLIP.encode_text's first two lines on the own kernels when they apply (a device int64 [B, L] view whose rows are
     contiguous, float32 table / positions of a width that is a multiple of 8 and at most 2048); None otherwise (the caller
     keeps nn.Embedding)."""
-    if not (TEXT_EMBED_KERNEL and text.is_cuda and text.dtype == torch.int64 and text.dim() == 2 and text.stride(1) == 1
+    if not (text.is_cuda and text.dtype == torch.int64 and text.dim() == 2 and text.stride(1) == 1
             and text.shape[0] > 0 and text.shape[1] > 0
             and table.dtype == torch.float32 and pos.dtype == torch.float32 and table.is_contiguous()
             and pos.is_contiguous() and table.shape[1] % 8 == 0 and table.shape[1] <= 2048

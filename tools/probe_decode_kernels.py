@@ -1,5 +1,5 @@
 """Times the decoder's row kernels at the narrator's sizes (64 clips, 12 heads, 256 image tokens, width 768):
-lvl_cross_attn_rows_fwd over qrep (captions per clip) x waves per workgroup, lvl_decode_self_attn, lvl_gated_add_layernorm.
+lvl_cross_attn_rows_fwd over qrep (captions per clip), lvl_decode_self_attn, lvl_gated_add_layernorm.
 Launches are timed back to back inside a captured hipGraph (50 per replay), i.e. without host launch gaps.
     python tools/probe_decode_kernels.py [--out file]"""
 import argparse
@@ -43,17 +43,14 @@ def main():
     for qrep in (1, 2, 4, 10, 20):
         q = torch.randn(ctx * qrep, D, device='cuda').bfloat16()
         out = torch.empty_like(q)
-        for nw in ((0,) if qrep == 1 else (0, 4, 16)):       # 0 = shipped (MFMA kernel for qrep >= 2), n = VALU form with n waves
-            C.lib().lvl_debug_cross_attn_waves(nw)
-            it = [0]
+        it = [0]
 
-            def run():
-                kv = kvs[it[0] % 12]
-                it[0] += 1
-                C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), ctx * qrep, qrep, Tk, H, C.LVL_BF16,
-                                                        C.stream_ptr()), 'cross')
-            res[f'cross_attn_qrep{qrep}_waves{nw}'] = round(graph_time(run, 48), 2)
-    C.lib().lvl_debug_cross_attn_waves(0)
+        def run():
+            kv = kvs[it[0] % 12]
+            it[0] += 1
+            C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), ctx * qrep, qrep, Tk, H, C.LVL_BF16,
+                                                    C.stream_ptr()), 'cross')
+        res[f'cross_attn_qrep{qrep}'] = round(graph_time(run, 48), 2)
     for rows in (64, 640):
         qkv = torch.randn(rows, 3 * D, device='cuda').bfloat16()
         cache = torch.randn(rows, 77, 2 * D, device='cuda').bfloat16()

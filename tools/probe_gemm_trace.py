@@ -8,12 +8,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SO = os.path.join(ROOT, 'tools', 'probes', 'libgemm_trace%s.so' % os.environ.get('GM_VARIANT', ''))   # probe builds stay out of the product lib dir
+SO = os.path.join(ROOT, 'tools', 'probes', 'libgemm_trace.so')   # probe builds stay out of the product lib dir
 if '--build' in sys.argv:
     src = os.path.join(ROOT, 'lavila_amd', 'csrc')
     subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared',
-                           '-DGM_TRACE', '-fno-slp-vectorize', *[a for a in sys.argv[1:] if a.startswith('-D')], os.path.join(src, 'gemm_tn_mfma.hip'), os.path.join(ROOT, 'tools', 'probes', 'trace_stub.hip'),
-                           '-o', SO])
+                           '-DGM_TRACE', '-fno-slp-vectorize', os.path.join(src, 'gemm_tn_mfma.hip'),
+                           os.path.join(ROOT, 'tools', 'probes', 'trace_stub.hip'), '-o', SO])
     print('built', SO)
     sys.exit(0)
 import torch  # noqa: E402
