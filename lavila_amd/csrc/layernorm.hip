@@ -11,7 +11,8 @@
 #include "common.h"
 
 // The general and the exact-width kernels must agree to the bit (activation checkpointing recomputes a forward that may take
-// the other instantiation): no implicit contraction in this file, every fused multiply-add is written as one.
+// the other instantiation): no implicit contraction in this file, every fused multiply-add is written as one, and each
+// expression of the row arithmetic is written once, in the ln_*_elem helpers that all four kernels call.
 #pragma clang fp contract(off)
 
 namespace {
@@ -19,27 +20,32 @@ namespace {
 constexpr int kRowsPerBlock = 4;          // 4 waves per 256-thread workgroup
 constexpr int kLnBwdParts = 768;          // partial dgamma/dbeta/dxsum slabs (one per workgroup)
 
-template <int W>
-__device__ __forceinline__ void load_f32(const float* p, float (&v)[W]) { VecIO<float, W>::load(p, v); }
-
-// s = x (+ x2) (+ bias)
-template <typename T, int W>
-__device__ __forceinline__ void load_sum(const T* __restrict__ x, const T* __restrict__ x2,
-                                         const float* __restrict__ bias, int64_t off, int c0, float (&v)[W]) {
-  VecIO<T, W>::load(x + off, v);
-  if (x2 != nullptr) {
-    float w[W];
-    VecIO<T, W>::load(x2 + off, w);
-#pragma unroll
-    for (int j = 0; j < W; ++j) v[j] += w[j];
-  }
-  if (bias != nullptr) {
-    float bb[W];
-    load_f32<W>(bias + c0, bb);
-#pragma unroll
-    for (int j = 0; j < W; ++j) v[j] += bb[j];
-  }
+// The row arithmetic, per element (helpers over whole vectors cost the backward registers and a wave per SIMD). What differs
+// between the kernels stays in them: column guards, operand flags, and with those the order x, += x2, += bias of the input sum.
+// a row mean from the lanes' partial sums: mu, the variance, and the two means of the backward
+__device__ __forceinline__ float ln_mean(float lane_sum, float inv_cols) { return wave_sum(lane_sum) * inv_cols; }
+__device__ __forceinline__ void ln_sq_elem(float v, float mu, float& sq) { const float d = v - mu; sq = fmaf(d, d, sq); }
+__device__ __forceinline__ float ln_rstd(float sq, float inv_cols, float eps) { return rsqrtf(ln_mean(sq, inv_cols) + eps); }
+// the normalised element: the forward's, and what the backward rebuilds from its packed operands
+__device__ __forceinline__ float ln_xhat_elem(float v, float mu, float rs) { return (v - mu) * rs; }
+__device__ __forceinline__ float ln_norm_elem(float v, float mu, float rs, float g, float b) {
+  return fmaf(ln_xhat_elem(v, mu, rs), g, b);
 }
+// s1 / s2: this lane's share of sum dy*g and sum dy*g*xhat; ag / ab: the dgamma / dbeta columns
+__device__ __forceinline__ void ln_bwd_accum_elem(float dv, float xh, float g, float& s1, float& s2, float& ag, float& ab) {
+  const float dgj = dv * g;
+  s1 += dgj;
+  s2 = fmaf(dgj, xh, s2);
+  ag = fmaf(dv, xh, ag);
+  ab += dv;
+}
+// dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat))
+__device__ __forceinline__ float ln_bwd_dx_elem(float dv, float xh, float g, float rs, float c1, float c2) {
+  return rs * fmaf(-xh, c2, dv * g - c1);
+}
+// the column sum of a stored gradient adds the value as stored (rounded to T)
+template <typename T>
+__device__ __forceinline__ void ln_bwd_colsum_elem(float o, float& ax) { ax += Elem<T>::round(o); }
 
 // X2: the row is x + x2 (compile time: the plain LayerNorm then carries no registers for the second operand's two rows in
 // flight -- 76 -> 64 VGPRs for 768 columns = 8 instead of 6 waves per SIMD, round 6)
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
         }
         if (bias != nullptr) {
           float bb[W];
-          load_f32<W>(bias + c * W, bb);
+          VecIO<float, W>::load(bias + c * W, bb);
 #pragma unroll
           for (int j = 0; j < W; ++j) v[i][j] += bb[j];
         }
@@ -104,25 +110,25 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
         for (int j = 0; j < W; ++j) sum += v[i][j];
       }
     }
-    const float mu = wave_sum(sum) * inv_cols;
+    const float mu = ln_mean(sum, inv_cols);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       if (lane + i * 64 < nvec) {
 #pragma unroll
-        for (int j = 0; j < W; ++j) { const float d = v[i][j] - mu; sq = fmaf(d, d, sq); }
+        for (int j = 0; j < W; ++j) ln_sq_elem(v[i][j], mu, sq);
       }
     }
-    const float rs = rsqrtf(wave_sum(sq) * inv_cols + eps);
+    const float rs = ln_rstd(sq, inv_cols, eps);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + i * 64;
       if (c < nvec) {
         float g[W], b[W], o[W];
-        load_f32<W>(gamma + c * W, g);
-        load_f32<W>(beta + c * W, b);
+        VecIO<float, W>::load(gamma + c * W, g);
+        VecIO<float, W>::load(beta + c * W, b);
 #pragma unroll
-        for (int j = 0; j < W; ++j) o[j] = fmaf((v[i][j] - mu) * rs, g[j], b[j]);
+        for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, g[j], b[j]);
         VecIO<T, W>::store(out + row * cols + c * W, o);
       }
     }
@@ -134,9 +140,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
   }
 }
 
-// EXACT-WIDTH forward (cols == VPL * 64 * W, no s_out; round 6): the same arithmetic as ln_fwd_kernel with NO conditional
-// vector-memory instruction in the row loop. Why it exists: the compiler's s_waitcnt insertion merges its counters
-// conservatively over branches, and ln_fwd_kernel's per-chunk `c < nvec` / `row + stride < rows` / nullable-pointer branches
+// EXACT-WIDTH forward (cols == VPL * 64 * W, no s_out; round 6): ln_fwd_kernel with NO conditional vector-memory instruction
+// in the row loop. Why it exists: the compiler's s_waitcnt insertion merges its counters conservatively over branches, and
+// ln_fwd_kernel's per-chunk `c < nvec` / `row + stride < rows` / nullable-pointer branches
 // left the row loop with `s_waitcnt vmcnt(0)` in front of the reductions (the prefetched NEXT row was waited for too) and
 // behind each per-row reload of gamma / beta (three dependent L2 round trips per row). Here gamma, beta (and the optional
 // bias) live in registers, the prefetch is unconditional (the last rows re-read row `rows - 1`), mean / rstd are stored by every
@@ -156,9 +162,9 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
   float g[VPL][W], b[VPL][W], bb[BIAS ? VPL : 1][W];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
-    load_f32<W>(gamma + (lane + i * 64) * W, g[i]);
-    load_f32<W>(beta + (lane + i * 64) * W, b[i]);
-    if constexpr (BIAS) load_f32<W>(bias + (lane + i * 64) * W, bb[i]);
+    VecIO<float, W>::load(gamma + (lane + i * 64) * W, g[i]);
+    VecIO<float, W>::load(beta + (lane + i * 64) * W, b[i]);
+    if constexpr (BIAS) VecIO<float, W>::load(bias + (lane + i * 64) * W, bb[i]);
   }
   RawVec<T, W> cur[VPL], cur2[X2 ? VPL : 1], nxt[VPL], nxt2[X2 ? VPL : 1];
   auto load_row = [&](int64_t r, RawVec<T, W> (&a)[VPL], RawVec<T, W> (&a2)[X2 ? VPL : 1]) {
@@ -182,8 +188,7 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
     }
   }
   for (; row < rows; row += stride) {
-    const int64_t rn = row + stride < rows ? row + stride : rows - 1;      // unconditional prefetch
-    load_row(rn, nxt, nxt2);
+    load_row(row + stride < rows ? row + stride : rows - 1, nxt, nxt2);      // unconditional prefetch
     float v[VPL][W];
     float sum = 0.f;
 #pragma unroll
@@ -202,18 +207,18 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
 #pragma unroll
       for (int j = 0; j < W; ++j) sum += v[i][j];
     }
-    const float mu = wave_sum(sum) * inv_cols;
+    const float mu = ln_mean(sum, inv_cols);
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i)
 #pragma unroll
-      for (int j = 0; j < W; ++j) { const float d = v[i][j] - mu; sq = fmaf(d, d, sq); }
-    const float rs = rsqrtf(wave_sum(sq) * inv_cols + eps);
+      for (int j = 0; j < W; ++j) ln_sq_elem(v[i][j], mu, sq);
+    const float rs = ln_rstd(sq, inv_cols, eps);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       float o[W];
 #pragma unroll
-      for (int j = 0; j < W; ++j) o[j] = fmaf((v[i][j] - mu) * rs, g[i][j], b[i][j]);
+      for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, g[i][j], b[i][j]);
       VecIO<T, W>::store(out + row * cols + (lane + i * 64) * W, o);
     }
     mean[row] = mu;          // every lane, one address: no exec-masked (conditional) store in the loop; both non-null here
@@ -226,8 +231,7 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
   }
 }
 
-// dx = rstd * (dy*g - mean(dy*g) - shat * mean(dy*g*shat)) (+ dadd);
-// per-workgroup partial slabs [3][cols] = {sum dy*shat, sum dy, sum dx}
+// Backward: dx (+ dadd) and per-workgroup partial slabs [3][cols] = {sum dy*shat, sum dy, sum dx}.
 // The row loop is software-pipelined: the packed operands of the NEXT row (and its mean/rstd) are requested before
 // the current row is reduced, so each wave keeps two rows of loads in flight (4 waves/SIMD would otherwise leave
 // HBM idle during the two cross-lane reductions).
@@ -298,10 +302,10 @@ __device__ __forceinline__ void ln_bwd_combine(float* smem, float* __restrict__ 
   }
 }
 
-// EXACT-WIDTH backward (cols == VPL * 64 * W; round 6): ln_bwd_kernel's arithmetic with no conditional vector-memory
-// instruction in the row loop (see ln_fwd_exact_kernel: the general kernel's loop waits vmcnt(0) -- for the prefetched next
-// row as well -- in front of every reduction). X2: the normalised row is x + x2 (+ bias, zeros when there is none);
-// DADD / PLAIN as in the general kernel. mean / rstd of the next row are prefetched with it.
+// EXACT-WIDTH backward (cols == VPL * 64 * W; round 6): ln_bwd_kernel with no conditional vector-memory instruction in the
+// row loop (see ln_fwd_exact_kernel: the general kernel's loop waits vmcnt(0) -- for the prefetched next row as well -- in
+// front of every reduction). X2: the normalised row is x + x2 (+ bias, zeros when there is none); DADD: dx = dx_ln + dadd;
+// PLAIN: dx_ln is stored to dx_plain as well. mean / rstd of the next row are prefetched with it.
 template <typename T, int VPL, int W, bool X2, bool DADD, bool PLAIN>
 __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)) void ln_bwd_exact_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ x2,
@@ -317,7 +321,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   for (int i = 0; i < VPL; ++i) {
 #pragma unroll
     for (int j = 0; j < W; ++j) { ag[i][j] = 0.f; ab[i][j] = 0.f; ax[i][j] = 0.f; }
-    load_f32<W>(gamma + (lane + i * 64) * W, g[i]);
+    VecIO<float, W>::load(gamma + (lane + i * 64) * W, g[i]);
     if constexpr (X2) {
 #pragma unroll
       for (int j = 0; j < W; ++j) bb[i][j] = 0.f;
@@ -326,7 +330,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   if constexpr (X2) {
     if (bias != nullptr) {            // before the loop: a branch here costs nothing
 #pragma unroll
-      for (int i = 0; i < VPL; ++i) load_f32<W>(bias + (lane + i * 64) * W, bb[i]);
+      for (int i = 0; i < VPL; ++i) VecIO<float, W>::load(bias + (lane + i * 64) * W, bb[i]);
     }
   }
   const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
@@ -365,8 +369,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
     }
   }
   for (; row < rows; row += stride) {
-    const int64_t rn = row + stride < rows ? row + stride : rows - 1;      // unconditional prefetch
-    load_row(rn, nxt);
+    load_row(row + stride < rows ? row + stride : rows - 1, nxt);      // unconditional prefetch
     const float mu = cur.mu, rs = cur.rs;
     auto xhat = [&](int i, float (&xh)[W]) {
       cur.x[i].unpack(xh);
@@ -374,10 +377,10 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
         float w[W];
         cur.x2[i].unpack(w);
 #pragma unroll
-        for (int j = 0; j < W; ++j) xh[j] = (xh[j] + w[j]) + bb[i][j];      // the general kernel's order of additions
+        for (int j = 0; j < W; ++j) xh[j] = (xh[j] + w[j]) + bb[i][j];      // x, += x2, += bias as in every kernel
       }
 #pragma unroll
-      for (int j = 0; j < W; ++j) xh[j] = (xh[j] - mu) * rs;
+      for (int j = 0; j < W; ++j) xh[j] = ln_xhat_elem(xh[j], mu, rs);
     };
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -386,26 +389,20 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
       xhat(i, xh);
       cur.dy[i].unpack(dv);
 #pragma unroll
-      for (int j = 0; j < W; ++j) {
-        const float dgj = dv[j] * g[i][j];
-        s1 += dgj;
-        s2 = fmaf(dgj, xh[j], s2);
-        ag[i][j] = fmaf(dv[j], xh[j], ag[i][j]);
-        ab[i][j] += dv[j];
-      }
+      for (int j = 0; j < W; ++j) ln_bwd_accum_elem(dv[j], xh[j], g[i][j], s1, s2, ag[i][j], ab[i][j]);
     }
-    const float c1 = wave_sum(s1) * inv_cols, c2 = wave_sum(s2) * inv_cols;
+    const float c1 = ln_mean(s1, inv_cols), c2 = ln_mean(s2, inv_cols);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       float xh[W], dv[W], o[W];
       xhat(i, xh);
       cur.dy[i].unpack(dv);
 #pragma unroll
-      for (int j = 0; j < W; ++j) o[j] = rs * fmaf(-xh[j], c2, dv[j] * g[i][j] - c1);
+      for (int j = 0; j < W; ++j) o[j] = ln_bwd_dx_elem(dv[j], xh[j], g[i][j], rs, c1, c2);
       const int64_t off = row * cols + (lane + i * 64) * W;
-      if constexpr (PLAIN) {           // the normalisation's own input gradient leaves separately
+      if constexpr (PLAIN) {           // the normalisation's own input gradient leaves separately, and is what is summed
 #pragma unroll
-        for (int j = 0; j < W; ++j) ax[i][j] += Elem<T>::round(o[j]);
+        for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
         VecIO<T, W>::store(dx_plain + off, o);
       }
       if constexpr (DADD) {
@@ -416,7 +413,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
       }
       if constexpr (!PLAIN) {
 #pragma unroll
-        for (int j = 0; j < W; ++j) ax[i][j] += Elem<T>::round(o[j]);
+        for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
       }
       VecIO<T, W>::store(dx + off, o);
     }
@@ -441,7 +438,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
     const int c = lane + i * 64;
 #pragma unroll
     for (int j = 0; j < W; ++j) { ag[i][j] = 0.f; ab[i][j] = 0.f; ax[i][j] = 0.f; g[i][j] = 0.f; }
-    if (c < nvec) load_f32<W>(gamma + c * W, g[i]);
+    if (c < nvec) VecIO<float, W>::load(gamma + c * W, g[i]);
   }
   float bb[VPL][W];     // residual-branch bias (recompute variant only)
   if (bias != nullptr) {
@@ -450,7 +447,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
       const int c = lane + i * 64;
 #pragma unroll
       for (int j = 0; j < W; ++j) bb[i][j] = 0.f;
-      if (c < nvec) load_f32<W>(bias + c * W, bb[i]);
+      if (c < nvec) VecIO<float, W>::load(bias + c * W, bb[i]);
     }
   }
   const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
@@ -461,7 +458,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
     if (row + stride < rows) nxt.load(dy, x, x2, dadd, mean, rstd, row + stride, cols, lane, nvec);
     const float mu = cur.mu, rs = cur.rs;
     // normalised input of vector i, rebuilt from the packed operands (cheaper than holding it across the reduction)
-    auto xhat = [&](int i, int c, float (&xh)[W]) {
+    auto xhat = [&](int i, float (&xh)[W]) {
       cur.x[i].unpack(xh);
       if (x2 != nullptr) {
         float w[W];
@@ -474,39 +471,32 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
         for (int j = 0; j < W; ++j) xh[j] += bb[i][j];
       }
 #pragma unroll
-      for (int j = 0; j < W; ++j) xh[j] = (xh[j] - mu) * rs;
+      for (int j = 0; j < W; ++j) xh[j] = ln_xhat_elem(xh[j], mu, rs);
     };
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
-      const int c = lane + i * 64;
-      if (c < nvec) {
+      if (lane + i * 64 < nvec) {
         float xh[W], dv[W];
-        xhat(i, c, xh);
+        xhat(i, xh);
         cur.dy[i].unpack(dv);
 #pragma unroll
-        for (int j = 0; j < W; ++j) {
-          const float dgj = dv[j] * g[i][j];
-          s1 += dgj;
-          s2 = fmaf(dgj, xh[j], s2);
-          ag[i][j] = fmaf(dv[j], xh[j], ag[i][j]);
-          ab[i][j] += dv[j];
-        }
+        for (int j = 0; j < W; ++j) ln_bwd_accum_elem(dv[j], xh[j], g[i][j], s1, s2, ag[i][j], ab[i][j]);
       }
     }
-    const float c1 = wave_sum(s1) * inv_cols, c2 = wave_sum(s2) * inv_cols;
+    const float c1 = ln_mean(s1, inv_cols), c2 = ln_mean(s2, inv_cols);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int c = lane + i * 64;
       if (c < nvec) {
         float xh[W], dv[W], o[W];
-        xhat(i, c, xh);
+        xhat(i, xh);
         cur.dy[i].unpack(dv);
 #pragma unroll
-        for (int j = 0; j < W; ++j) o[j] = rs * fmaf(-xh[j], c2, dv[j] * g[i][j] - c1);
-        if (dx_plain != nullptr) {       // the normalisation's own input gradient leaves separately (see header)
+        for (int j = 0; j < W; ++j) o[j] = ln_bwd_dx_elem(dv[j], xh[j], g[i][j], rs, c1, c2);
+        if (dx_plain != nullptr) {
 #pragma unroll
-          for (int j = 0; j < W; ++j) ax[i][j] += Elem<T>::round(o[j]);
+          for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
           VecIO<T, W>::store(dx_plain + row * cols + c * W, o);
         }
         if (dadd != nullptr) {
@@ -517,7 +507,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
         }
         if (dx_plain == nullptr) {
 #pragma unroll
-          for (int j = 0; j < W; ++j) ax[i][j] += Elem<T>::round(o[j]);
+          for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
         }
         VecIO<T, W>::store(dx + row * cols + c * W, o);
       }
@@ -617,19 +607,75 @@ __global__ __launch_bounds__(256) void colsum_stage2_kernel(const float* __restr
 }
 
 // (VPL, W) for a row length: W = 4 with exactly cols/256 vectors per lane when possible
-#define LN_DISPATCH(cols, CALL)                          \
-  do {                                                   \
-    if ((cols) % 256 == 0 && (cols) <= 1024) {           \
-      switch ((cols) / 256) {                            \
-        case 1: CALL(1, 4); break;                       \
-        case 2: CALL(2, 4); break;                       \
-        case 3: CALL(3, 4); break;                       \
-        default: CALL(4, 4); break;                      \
-      }                                                  \
-    } else if ((cols) / 8 <= 128) CALL(2, 8);            \
-    else if ((cols) / 8 <= 256) CALL(4, 8);              \
-    else CALL(8, 8);                                     \
-  } while (0)
+constexpr int ln_w(int cols) { return cols % 256 == 0 && cols <= 1024 ? 4 : 8; }
+constexpr int ln_vpl(int cols) { return ln_w(cols) == 4 ? cols / 256 : (cols / 8 <= 128 ? 2 : (cols / 8 <= 256 ? 4 : 8)); }
+#define LN_CASE(CALL, VPL, W) case (W) * 16 + (VPL): CALL(VPL, W); break
+#define LN_DISPATCH(cols, CALL)                                                           \
+  switch (ln_w(cols) * 16 + ln_vpl(cols)) {                                               \
+    LN_CASE(CALL, 1, 4); LN_CASE(CALL, 2, 4); LN_CASE(CALL, 3, 4); LN_CASE(CALL, 4, 4);   \
+    LN_CASE(CALL, 2, 8); LN_CASE(CALL, 4, 8); LN_CASE(CALL, 8, 8);                        \
+    default: return lvl_fail(LVL_EINVAL, "layernorm: no kernel for cols=%d", (int)(cols));  \
+  }
+
+// Is there an exact-width kernel for (T, VPL, W)? Where LN_DISPATCH picks (VPL, W) for the width VPL * 64 * W itself (1024
+// columns go to (4, 4), never to (2, 8)); in the backward for the 2-byte type of the training step only. The launch code asks
+// this with `if constexpr`: what is compiled is what can be chosen.
+template <typename T, int VPL, int W>
+constexpr bool ln_has_exact(bool backward) {
+  return ln_vpl(VPL * 64 * W) == VPL && ln_w(VPL * 64 * W) == W && (!backward || sizeof(T) == 2);
+}
+
+// LAVILA_LN_EXACT=0 sends every call to the general kernels (the bit-for-bit test compares the two families through it)
+bool ln_exact_enabled() {
+  static const bool on = !(getenv("LAVILA_LN_EXACT") && atoi(getenv("LAVILA_LN_EXACT")) == 0);
+  return on;
+}
+
+// one workgroup of 256 threads per kRowsPerBlock rows; more than 64 KiB of dynamic LDS needs the limit raised first
+template <auto Kernel, typename... Args>
+int ln_launch(int64_t blocks, size_t shmem, hipStream_t st, Args... args) {
+  if (shmem > 64 * 1024)
+    if (int rc = lvl_allow_lds<Kernel>()) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(256), shmem, st, args...);
+  return LVL_OK;
+}
+
+// The exact-width kernel where there is one for the operands of this call (in the backward: the operand combinations of the
+// training step), the general kernel otherwise.
+template <typename T, int VPL, int W>
+int ln_fwd_launch(const T* x, const T* x2, const float* bias, const float* gamma, const float* beta, T* s_out, T* y,
+                  float* mean, float* rstd, int64_t rows, int cols, float eps, int64_t blocks, hipStream_t st) {
+#define LN_E(X2, BIAS) \
+  ln_launch<ln_fwd_exact_kernel<T, VPL, W, X2, BIAS>>(blocks, 0, st, x, x2, bias, gamma, beta, y, mean, rstd, rows, eps)
+#define LN_G(X2) \
+  ln_launch<ln_fwd_kernel<T, VPL, W, X2>>(blocks, 0, st, x, x2, bias, gamma, beta, s_out, y, mean, rstd, rows, cols, eps)
+  if constexpr (ln_has_exact<T, VPL, W>(false)) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W && !s_out && mean && rstd && (x2 || !bias))
+      return !x2 ? LN_E(false, false) : (bias ? LN_E(true, true) : LN_E(true, false));
+  }
+  return x2 ? LN_G(true) : LN_G(false);
+#undef LN_G
+#undef LN_E
+}
+
+template <typename T, int VPL, int W>
+int ln_bwd_launch(const T* dy, const T* x, const T* x2, const float* bias, const float* gamma, const float* mean,
+                  const float* rstd, const T* dadd, T* dx, T* dx_plain, float* ws, int64_t rows, int cols, int64_t blocks,
+                  hipStream_t st) {
+  const size_t shmem = (size_t)3 * 3 * cols * sizeof(float);
+#define LN_ARGS blocks, shmem, st, dy, x, x2, bias, gamma, mean, rstd, dadd, dx, dx_plain, ws, rows
+#define LN_E(X2, DADD, PLAIN) ln_launch<ln_bwd_exact_kernel<T, VPL, W, X2, DADD, PLAIN>>(LN_ARGS)
+  if constexpr (ln_has_exact<T, VPL, W>(true)) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W && rows > 0) {
+      if (!x2 && !bias && !dx_plain) return dadd ? LN_E(false, true, false) : LN_E(false, false, false);
+      if (x2 && !dadd && !dx_plain) return LN_E(true, false, false);
+      if (x2 && dadd && dx_plain) return LN_E(true, true, true);
+    }
+  }
+  return ln_launch<ln_bwd_kernel<T, VPL, W>>(LN_ARGS, cols);
+#undef LN_E
+#undef LN_ARGS
+}
 
 }  // namespace
 
@@ -670,29 +716,13 @@ extern "C" int lvl_layernorm_fwd(const void* x, const void* x2, const float* xbi
   // (56 VGPRs, 8 waves/SIMD) measured best with 4 x its resident workgroups (0.136 ms at 8192 against 0.142 at 3072 and 0.176
   // at 2048 for 200 960 rows of 768: profiles/r06_rowops_ln_fwd.txt)
   const int64_t cap = x2 == nullptr ? 8192 : 3072;
-  static const bool exact_off = getenv("LAVILA_LN_EXACT") && atoi(getenv("LAVILA_LN_EXACT")) == 0;      // A/B switch
-  const bool exact = !exact_off && s_out == nullptr && mean != nullptr && rstd != nullptr;
   if (blocks > cap) blocks = cap;
-#define LN_FWD_X(TT, VPL, W, X2)                                                                                \
-  hipLaunchKernelGGL((ln_fwd_kernel<TT, VPL, W, X2>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, \
-                     (const TT*)x, (const TT*)x2, xbias, gamma, beta, (TT*)s_out, (TT*)y, mean, rstd, rows, cols, eps)
-#define LN_FWD_E(TT, VPL, W, X2, BIAS)                                                                             \
-  hipLaunchKernelGGL((ln_fwd_exact_kernel<TT, VPL, W, X2, BIAS>), dim3((unsigned)blocks), dim3(256), 0,              \
-                     (hipStream_t)stream, (const TT*)x, (const TT*)x2, xbias, gamma, beta, (TT*)y, mean, rstd, rows, eps)
-#define LN_FWD_T(TT, VPL, W)                                                              \
-  do {                                                                                    \
-    if (exact && (VPL) * 64 * (W) == cols && x2 == nullptr && xbias == nullptr) LN_FWD_E(TT, VPL, W, false, false); \
-    else if (exact && (VPL) * 64 * (W) == cols && x2 != nullptr && xbias != nullptr) LN_FWD_E(TT, VPL, W, true, true); \
-    else if (exact && (VPL) * 64 * (W) == cols && x2 != nullptr) LN_FWD_E(TT, VPL, W, true, false); \
-    else if (x2 != nullptr) LN_FWD_X(TT, VPL, W, true);                                   \
-    else LN_FWD_X(TT, VPL, W, false);                                                     \
-  } while (0)
-#define LN_FWD(VPL, W) LN_FWD_T(T, VPL, W)
+#define LN_FWD(VPL, W)                                                                                               \
+  if (int rc = ln_fwd_launch<T, VPL, W>((const T*)x, (const T*)x2, xbias, gamma, beta, (T*)s_out, (T*)y, mean, rstd, rows, \
+                                        cols, eps, blocks, (hipStream_t)stream))                                       \
+  return rc
   LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, LN_FWD));
 #undef LN_FWD
-#undef LN_FWD_T
-#undef LN_FWD_X
-#undef LN_FWD_E
   LVL_CHECK_LAUNCH("layernorm_fwd");
   return LVL_OK;
 }
@@ -711,43 +741,12 @@ extern "C" int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, 
   int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
   if (blocks > kLnBwdParts) blocks = kLnBwdParts;
   if (blocks < 1) blocks = 1;
-  const size_t shmem = (size_t)3 * 3 * cols * sizeof(float);
-  static const bool exact_off = getenv("LAVILA_LN_EXACT") && atoi(getenv("LAVILA_LN_EXACT")) == 0;      // A/B switch
-  const bool exact = !exact_off;
-#define LN_BWD_E(TT, VPL, W, X2, DADD, PLAIN)                                                                      \
-  do {                                                                                                            \
-    if (shmem > 64 * 1024)                                                                                        \
-      if (int rc = lvl_allow_lds<ln_bwd_exact_kernel<TT, VPL, W, X2, DADD, PLAIN>>()) return rc;                  \
-    hipLaunchKernelGGL((ln_bwd_exact_kernel<TT, VPL, W, X2, DADD, PLAIN>), dim3((unsigned)blocks), dim3(256), shmem, \
-                       st, (const TT*)dy, (const TT*)x, (const TT*)x2, xbias, gamma, mean, rstd, (const TT*)dadd,  \
-                       (TT*)dx, (TT*)dx_plain, ws, rows);                                                         \
-  } while (0)
-#define LN_BWD_G(TT, VPL, W)                                                                                    \
-  do {                                                                                                          \
-    if (shmem > 64 * 1024)                                                                                      \
-      if (int rc = lvl_allow_lds<ln_bwd_kernel<TT, VPL, W>>()) return rc;                                       \
-    hipLaunchKernelGGL((ln_bwd_kernel<TT, VPL, W>), dim3((unsigned)blocks), dim3(256), shmem, st, (const TT*)dy, \
-                       (const TT*)x, (const TT*)x2, xbias, gamma, mean, rstd, (const TT*)dadd, (TT*)dx,          \
-                       (TT*)dx_plain, ws, rows,                                                                   \
-                       cols);                                                                                   \
-  } while (0)
-// the exact-width kernel for the operand combinations of the training step (bf16), the general kernel otherwise
-#define LN_BWD_T(TT, VPL, W)                                                                                    \
-  do {                                                                                                          \
-    constexpr bool kHalf = sizeof(TT) == 2;                                                                     \
-    const bool ex = kHalf && exact && (VPL) * 64 * (W) == cols && rows > 0;                                     \
-    if (ex && !x2 && !xbias && !dadd && !dx_plain) LN_BWD_E(TT, VPL, W, false, false, false);                   \
-    else if (ex && !x2 && !xbias && dadd && !dx_plain) LN_BWD_E(TT, VPL, W, false, true, false);                \
-    else if (ex && x2 && !dadd && !dx_plain) LN_BWD_E(TT, VPL, W, true, false, false);                          \
-    else if (ex && x2 && dadd && dx_plain) LN_BWD_E(TT, VPL, W, true, true, true);                              \
-    else LN_BWD_G(TT, VPL, W);                                                                                  \
-  } while (0)
-#define LN_BWD(VPL, W) LN_BWD_T(T, VPL, W)
+#define LN_BWD(VPL, W)                                                                                               \
+  if (int rc = ln_bwd_launch<T, VPL, W>((const T*)dy, (const T*)x, (const T*)x2, xbias, gamma, mean, rstd, (const T*)dadd, \
+                                        (T*)dx, (T*)dx_plain, ws, rows, cols, blocks, st))                             \
+  return rc
   LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, LN_BWD));
 #undef LN_BWD
-#undef LN_BWD_T
-#undef LN_BWD_G
-#undef LN_BWD_E
   LVL_CHECK_LAUNCH("layernorm_bwd");
   return lvl_launch_column_reduce(ws, (int)blocks, 3 * cols, cols, ws + (size_t)kLnBwdParts * 3 * cols, dgamma, dbeta,
                                   dxsum, st);
