@@ -84,6 +84,25 @@ int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, const float
                       void* dx, void* dx_plain, float* dgamma, float* dbeta, float* dxsum, float* ws,
                       int64_t rows, int cols, int dtype, void* stream);
 
+/* ---- LayerNorm output, rebuilt (selective activation recompute) -----------------------------------
+ * y = (s - mean[row]) * rstd[row] * gamma + beta with s = x (+ x2) (+ xbias) formed as lvl_layernorm_fwd
+ * forms it, and mean / rstd the statistics that call returned: y equals that call's y to the bit (pass
+ * its s_out as x and x2 = xbias = NULL when the sum was kept). No reductions: one read of the operands,
+ * one write of y. Operand conventions, alignment and cols limits of lvl_layernorm_fwd; mean, rstd: [rows]
+ * f32, required. Used in backward in front of the weight-gradient GEMM that reads a LayerNorm output which
+ * the forward did not keep (norm3 / norm1 / norm2 of SpaceTimeBlock, timesformer.py:183-196). */
+int lvl_layernorm_apply(const void* x, const void* x2, const float* xbias, const float* gamma,
+                        const float* beta, const float* mean, const float* rstd, void* y,
+                        int64_t rows, int cols, int dtype, void* stream);
+
+/* ---- QuickGELU of a kept pre-activation (selective activation recompute) ----------------------------
+ * a = u * sigmoid(1.702 u) with the arithmetic of lvl_linear_tn's LVL_EPI_BIAS_QUICKGELU epilogue, whose
+ * aux_out is u: a equals that call's y to the bit (bf16: the activation of the bf16 value; f32: of the
+ * f32 value). Mlp.act of timesformer.py:52-54, rebuilt in front of fc2's weight-gradient GEMM instead of
+ * kept. u, a: [rows, cols] dtype, 16-byte aligned; cols % 8 == 0. Not lvl_bias_quickgelu_fwd, whose
+ * sigmoid is a different expression. */
+int lvl_quickgelu_apply(const void* u, void* a, int64_t rows, int cols, int dtype, void* stream);
+
 /* ---- bias + QuickGELU --------------------------------------------------------------------------
  * a = (u + bias) * sigmoid(1.702 (u + bias)); replaces the bias add of Mlp.fc1 / mlp.c_fc and
  * QuickGELU.forward (openai_model.py:177-179; timesformer.py:52-54). u,a,da,du: [rows, cols] dtype;

@@ -206,6 +206,22 @@ template <> struct RawVec<bf16_t, 8> {
 __device__ __forceinline__ void load8_f32(const float* p, float (&v)[8]) { Elem<float>::load8(p, v); }
 
 // ---------------------------------------------------------------------------------------------
+// QuickGELU, y = u * sigmoid(1.702 u). One definition for the TN GEMM's epilogues (gemm_tn_mfma.hip) and for the kernel that
+// rebuilds the activation from the kept pre-activation (quickgelu.hip): the two must agree to the bit.
+// ---------------------------------------------------------------------------------------------
+// sigmoid through v_exp_f32 + v_rcp_f32 (1 ulp each; the results are rounded to bf16): an IEEE division here costs
+// ~10 VALU instructions per element of a 256x256 tile's epilogue
+__device__ __forceinline__ float sigmoid1702(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * u)); }
+__device__ __forceinline__ float quick_gelu(float u) { return u * sigmoid1702(u); }       // the f32-class epilogues
+__device__ __forceinline__ float bf16_lo(uint32_t p) { return __uint_as_float(p << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
+// the bf16 epilogues: quickgelu(u) = u r, r = sigmoid(1.702 u) = 1 / (1 + 2^(-1.702 log2(e) u))
+__device__ __forceinline__ void qgelu1(float u, float& y, float& r) {
+  r = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(u * (-1.702f * 1.44269504088896341f)));
+  y = u * r;
+}
+
+// ---------------------------------------------------------------------------------------------
 // wave-level (64-lane) reductions; every lane receives the result.
 // DPP within the 16-lane rows (quad xor 1, xor 2, half-mirror, mirror: 4 VALU ops, no LDS crossbar), then the four
 // row results travel through SGPRs (v_readlane). ~10 issue slots instead of 6 dependent ds_bpermute round trips.

@@ -100,10 +100,7 @@ __device__ __forceinline__ gm_f32x16 mfma32(uint4 a, uint4 b, gm_f32x16 c) {
                                                  c, 0, 0, 0);
 }
 
-// sigmoid through v_exp_f32 + v_rcp_f32 (1 ulp each; the results are rounded to bf16): an IEEE division here costs
-// ~10 VALU instructions per element of a 256x256 tile's epilogue
-__device__ __forceinline__ float sigmoid1702(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * u)); }
-__device__ __forceinline__ float quick_gelu(float u) { return u * sigmoid1702(u); }
+// sigmoid1702 / quick_gelu / qgelu1 / bf16_lo / bf16_hi: common.h (shared with quickgelu.hip, which rebuilds the activation)
 __device__ __forceinline__ float quick_gelu_grad(float u) {
   const float s = sigmoid1702(u);
   return s * (1.f + 1.702f * u * (1.f - s));
@@ -116,12 +113,6 @@ __device__ __forceinline__ float quick_gelu_grad(float u) {
 // compiler does not form them either.
 // quickgelu(u) = u r, r = sigmoid(1.702 u) = 1 / (1 + 2^(-1.702 log2(e) u)); quickgelu'(u) = r (1 + 1.702 u (1 - r))
 // = r + 1.702 (u r)(1 - r).
-__device__ __forceinline__ float bf16_lo(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
-__device__ __forceinline__ void qgelu1(float u, float& y, float& r) {
-  r = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(u * (-1.702f * 1.44269504088896341f)));
-  y = u * r;
-}
 __device__ __forceinline__ float qgelu_grad1(float y, float r) { return fmaf((1.f - r) * y, 1.702f, r); }
 
 // lanes l < 32 and l + 32 hold adjacent 8-byte pieces (4 bf16) of the same output row for two neighbouring

@@ -231,6 +231,136 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
   }
 }
 
+// APPLY: y = ln_norm_elem(x (+ x2) (+ bias), mean[row], rstd[row], gamma, beta) -- the forward's output rebuilt from the
+// forward's operands and the statistics it stored (selective activation recompute: the normalised rows are not kept, the
+// weight-gradient GEMM that reads them gets them back from here). No reductions; the input sum is formed in the forward's
+// order and the element goes through the same ln_norm_elem, so the rows equal the forward's to the bit, whichever of
+// the two forward kernels produced them and whichever of the two kernels below rebuilds them.
+template <typename T, int VPL, int W, bool X2>
+__global__ __launch_bounds__(256) void ln_apply_kernel(
+    const T* __restrict__ x, const T* __restrict__ x2, const float* __restrict__ bias,
+    const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ rstd, T* __restrict__ out, int64_t rows, int cols) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nvec = cols / W;
+  const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
+  int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
+  LnFwdRow<T, VPL, W, X2> cur, nxt;
+  float mu = 0.f, rs = 0.f, mu_n = 0.f, rs_n = 0.f;
+  if (row < rows) {
+    cur.load(x, x2, row, cols, lane, nvec);
+    mu = mean[row];
+    rs = rstd[row];
+  }
+  for (; row < rows; row += stride) {
+    if (row + stride < rows) {
+      nxt.load(x, x2, row + stride, cols, lane, nvec);
+      mu_n = mean[row + stride];
+      rs_n = rstd[row + stride];
+    }
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = lane + i * 64;
+      if (c < nvec) {
+        float v[W], g[W], b[W], o[W];
+        cur.x[i].unpack(v);
+        if constexpr (X2) {
+          float w[W];
+          cur.x2[i].unpack(w);
+#pragma unroll
+          for (int j = 0; j < W; ++j) v[j] += w[j];
+        }
+        if (bias != nullptr) {
+          float bb[W];
+          VecIO<float, W>::load(bias + c * W, bb);
+#pragma unroll
+          for (int j = 0; j < W; ++j) v[j] += bb[j];
+        }
+        VecIO<float, W>::load(gamma + c * W, g);
+        VecIO<float, W>::load(beta + c * W, b);
+#pragma unroll
+        for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[j], mu, rs, g[j], b[j]);
+        VecIO<T, W>::store(out + row * cols + c * W, o);
+      }
+    }
+    cur = nxt;
+    mu = mu_n;
+    rs = rs_n;
+  }
+}
+
+// EXACT-WIDTH apply (cols == VPL * 64 * W): as ln_fwd_exact_kernel, no conditional vector-memory instruction in the row loop --
+// gamma, beta (and the optional bias) in registers, the next row and its mean / rstd prefetched unconditionally (the last
+// rows re-read row `rows - 1`), so that the wait in front of a row's arithmetic is a counted one and the next row's loads
+// and this row's stores stay in flight.
+template <typename T, int VPL, int W, bool X2, bool BIAS>
+__global__ __launch_bounds__(256) void ln_apply_exact_kernel(
+    const T* __restrict__ x, const T* __restrict__ x2, const float* __restrict__ bias,
+    const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ rstd, T* __restrict__ out, int64_t rows) {
+  constexpr int cols = VPL * 64 * W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
+  int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
+  if (row >= rows) return;
+  float g[VPL][W], b[VPL][W], bb[BIAS ? VPL : 1][W];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    VecIO<float, W>::load(gamma + (lane + i * 64) * W, g[i]);
+    VecIO<float, W>::load(beta + (lane + i * 64) * W, b[i]);
+    if constexpr (BIAS) VecIO<float, W>::load(bias + (lane + i * 64) * W, bb[i]);
+  }
+  struct Row {
+    RawVec<T, W> x[VPL], x2[X2 ? VPL : 1];
+    float mu, rs;
+  } cur, nxt;
+  auto load_row = [&](int64_t r, Row& q) {
+    q.mu = mean[r];
+    q.rs = rstd[r];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      q.x[i].load(x + r * cols + (lane + i * 64) * W);
+      if constexpr (X2) q.x2[i].load(x2 + r * cols + (lane + i * 64) * W);
+    }
+  };
+  load_row(row, cur);
+  // everything requested so far has landed before the loop is entered (see ln_fwd_exact_kernel)
+  asm volatile("" : "+v"(cur.mu), "+v"(cur.rs));
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    cur.x[i].pin();
+    if constexpr (X2) cur.x2[i].pin();
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      asm volatile("" : "+v"(g[i][j]), "+v"(b[i][j]));
+      if constexpr (BIAS) asm volatile("" : "+v"(bb[i][j]));
+    }
+  }
+  for (; row < rows; row += stride) {
+    load_row(row + stride < rows ? row + stride : rows - 1, nxt);      // unconditional prefetch
+    const float mu = cur.mu, rs = cur.rs;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      float v[W], o[W];
+      cur.x[i].unpack(v);
+      if constexpr (X2) {
+        float w[W];
+        cur.x2[i].unpack(w);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] += w[j];
+      }
+      if constexpr (BIAS) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] += bb[i][j];
+      }
+#pragma unroll
+      for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[j], mu, rs, g[i][j], b[i][j]);
+      VecIO<T, W>::store(out + row * cols + (lane + i * 64) * W, o);
+    }
+    cur = nxt;
+  }
+}
+
 // Backward: dx (+ dadd) and per-workgroup partial slabs [3][cols] = {sum dy*shat, sum dy, sum dx}.
 // The row loop is software-pipelined: the packed operands of the NEXT row (and its mean/rstd) are requested before
 // the current row is reduced, so each wave keeps two rows of loads in flight (4 waves/SIMD would otherwise leave
@@ -659,6 +789,21 @@ int ln_fwd_launch(const T* x, const T* x2, const float* bias, const float* gamma
 }
 
 template <typename T, int VPL, int W>
+int ln_apply_launch(const T* x, const T* x2, const float* bias, const float* gamma, const float* beta, const float* mean,
+                    const float* rstd, T* y, int64_t rows, int cols, int64_t blocks, hipStream_t st) {
+#define LN_E(X2, BIAS) \
+  ln_launch<ln_apply_exact_kernel<T, VPL, W, X2, BIAS>>(blocks, 0, st, x, x2, bias, gamma, beta, mean, rstd, y, rows)
+#define LN_G(X2) ln_launch<ln_apply_kernel<T, VPL, W, X2>>(blocks, 0, st, x, x2, bias, gamma, beta, mean, rstd, y, rows, cols)
+  if constexpr (ln_has_exact<T, VPL, W>(false)) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W && (x2 || !bias))
+      return !x2 ? LN_E(false, false) : (bias ? LN_E(true, true) : LN_E(true, false));
+  }
+  return x2 ? LN_G(true) : LN_G(false);
+#undef LN_G
+#undef LN_E
+}
+
+template <typename T, int VPL, int W>
 int ln_bwd_launch(const T* dy, const T* x, const T* x2, const float* bias, const float* gamma, const float* mean,
                   const float* rstd, const T* dadd, T* dx, T* dx_plain, float* ws, int64_t rows, int cols, int64_t blocks,
                   hipStream_t st) {
@@ -724,6 +869,30 @@ extern "C" int lvl_layernorm_fwd(const void* x, const void* x2, const float* xbi
   LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, LN_FWD));
 #undef LN_FWD
   LVL_CHECK_LAUNCH("layernorm_fwd");
+  return LVL_OK;
+}
+
+extern "C" int lvl_layernorm_apply(const void* x, const void* x2, const float* xbias, const float* gamma,
+                                   const float* beta, const float* mean, const float* rstd, void* y, int64_t rows,
+                                   int cols, int dtype, void* stream) {
+  LVL_REQUIRE(rows == 0 || (x && gamma && beta && mean && rstd && y), "layernorm_apply: null pointer");
+  LVL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 4096,
+              "layernorm_apply: cols=%d must be a multiple of 8, <= 4096", cols);
+  LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(x2) && lvl_aligned16(xbias) && lvl_aligned16(y) &&
+                  lvl_aligned16(gamma) && lvl_aligned16(beta),
+              "layernorm_apply: pointers must be 16-byte aligned");
+  if (rows == 0) return LVL_OK;
+  int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  // the forward's grids (same rows in flight per wave, fewer registers than the forward in either form)
+  const int64_t apply_cap = x2 != nullptr ? 3072 : 8192;
+  if (blocks > apply_cap) blocks = apply_cap;
+#define LN_APPLY(VPL, W)                                                                                              \
+  if (int rc = ln_apply_launch<T, VPL, W>((const T*)x, (const T*)x2, xbias, gamma, beta, mean, rstd, (T*)y, rows, cols, \
+                                          blocks, (hipStream_t)stream))                                                \
+  return rc
+  LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, LN_APPLY));
+#undef LN_APPLY
+  LVL_CHECK_LAUNCH("layernorm_apply");
   return LVL_OK;
 }
 

@@ -219,6 +219,11 @@ class CLIP(nn.Module):
             return _half_out(ops.project(x, self.text_projection), self.text_projection)
 
     def forward(self, image, text, use_checkpoint=False, norm_embed=False):
+        """use_checkpoint (here and in encode_image / encode_text): False / None, True (= what LAVILA_CHECKPOINT says, 'block'
+        by default), 'block' (torch.utils.checkpoint around every block of both towers) or 'selective' (the video tower
+        rebuilds its LayerNorm outputs and MLP hidden activations in backward instead of keeping them; the text tower runs
+        its plain path): ops.checkpoint_mode."""
+        ops.checkpoint_mode(use_checkpoint)           # anything else raises here, before a kernel is enqueued
         with ops.model_forward():
             return self._forward(image, text, use_checkpoint, norm_embed)
 

@@ -165,10 +165,10 @@ class VCLM_HF(nn.Module):
             return _like_caller(self.img_attn_pool_norm(pooled), image, self.img_queries)
 
     def forward(self, image, text, mask=None, use_checkpoint=False, norm_embed=False):
-        """narrator.py:92-110 around whatever decoder the constructor was given."""
+        """narrator.py:92-110 around whatever decoder the constructor was given. use_checkpoint: ops.checkpoint_mode."""
         if self.text_decoder is None:
             raise NotImplementedError('VCLM_HF.forward needs a text decoder (lavila_amd.gpt2_gated.GPT2LMHeadModel)')
-        if use_checkpoint:
+        if ops.checkpoint_mode(use_checkpoint) == 'block':        # 'selective' is the video tower's; the decoder runs plain
             self.text_decoder.gradient_checkpointing_enable()
         else:
             self.text_decoder.gradient_checkpointing_disable()

@@ -274,16 +274,77 @@ def _tn_ok_f32(rows: int, n_out: int, n_in: int) -> bool:
     return F32_MFMA and _tn_ok(rows, n_out, 3 * n_in)
 
 
+# --------------------------------------------------------------------------------------------------
+# Activation checkpointing modes (the `use_checkpoint` argument of the model wrappers)
+# --------------------------------------------------------------------------------------------------
+# What `use_checkpoint=True` means: 'block' (torch.utils.checkpoint around every block of the video tower / the text tower)
+# or 'selective' (see checkpoint_mode). The reference's drivers pass a bool (main_pretrain.py --use-checkpoint), so this is how
+# they reach the selective mode.
+CHECKPOINT = os.environ.get('LAVILA_CHECKPOINT', 'block')
+CHECKPOINT_MODES = ('block', 'selective')
+
+
+def checkpoint_mode(use_checkpoint):
+    """The one place that decides what a `use_checkpoint` argument means: None (keep every activation), 'block' (re-run the
+    whole block in backward) or 'selective'.
+
+    False / None -> None; 'block' / 'selective' -> themselves; True -> LAVILA_CHECKPOINT (ops.CHECKPOINT), 'block' by
+    default. Anything else, as the argument or in the variable, raises ValueError.
+
+    'selective' runs the video tower's blocks as the plain step does but keeps neither the three LayerNorm outputs of a
+    block nor its MLP hidden activation (7 of the 22 [tokens, D] units a block keeps); each is rebuilt elementwise
+    (lvl_layernorm_apply / lvl_quickgelu_apply) right before the weight-gradient GEMM that reads it. No GEMM and no
+    attention kernel runs twice. The text tower runs its plain path under 'selective'."""
+    if use_checkpoint is None or use_checkpoint is False:
+        return None
+    mode = CHECKPOINT if use_checkpoint is True else use_checkpoint
+    if isinstance(mode, str) and mode in CHECKPOINT_MODES:
+        return mode
+    if use_checkpoint is True:
+        raise ValueError(f'LAVILA_CHECKPOINT={mode!r}: expected one of {CHECKPOINT_MODES}')
+    raise ValueError(f'use_checkpoint={use_checkpoint!r}: expected False, None, True or one of {CHECKPOINT_MODES}')
+
+
+class LnRecipe:
+    """What a LayerNorm output h is rebuilt from (selective activation recompute): the operands the LayerNorm function keeps
+    for its own backward anyway -- the input as x, or x + x2 + xbias summed in the forward's order -- with mean, rstd,
+    gamma, and beta. The LayerNorm function fills it, the caller hands it to the Linear that consumes h (`ln=`), and that
+    Linear saves these tensors (through save_for_backward) instead of h."""
+
+    __slots__ = ('x', 'x2', 'xbias', 'gamma', 'beta', 'mean', 'rstd', 'dtype')
+
+    def fill(self, x, x2, xbias, gamma, beta, mean, rstd):
+        d = lambda t: None if t is None else t.detach()
+        self.x, self.x2, self.xbias, self.gamma, self.beta = d(x), d(x2), d(xbias), d(gamma), d(beta)
+        self.mean, self.rstd, self.dtype = mean, rstd, x.dtype
+
+    def saved(self):
+        return self.x, self.x2, self.xbias, self.gamma, self.beta, self.mean, self.rstd
+
+
+def _ln_for(ln, x):
+    """The recipe when `x` is the kernel's own output (same dtype: no cast between the LayerNorm and the Linear), else None:
+    the Linear then keeps x itself."""
+    return ln if (ln is not None and ln.dtype == x.dtype) else None
+
+
+def _ln_rebuild(saved, shape):
+    x, x2, xbias, gamma, beta, mean, rstd = saved
+    return layernorm_apply_raw(x, x2, xbias, gamma, beta, mean, rstd).reshape(shape)
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T (+ b) for token-major activations [rows, in].
 
     bf16: forward and input gradient are lvl_linear_tn calls (the input gradient multiplies by the cached transposed
     weight copy, so both GEMMs read contraction-contiguous operands), the weight gradient is lvl_linear_wgrad. f32
     (the parity configuration): the same three kernels in f32-class mode (bf16 term images in, float32 out: split3).
-    Widths the kernels do not tile use the library GEMM."""
+    Widths the kernels do not tile use the library GEMM.
+    ln (an LnRecipe): x is a LayerNorm output that is not to be kept; the recipe's tensors are saved in its place and x is
+    rebuilt right before the weight-gradient GEMM, its only reader in backward."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, ln=None):
         x2 = x.reshape(-1, x.shape[-1])
         rows, n_in, n_out = x2.shape[0], x2.shape[1], weight.shape[0]
         own = (x.dtype == torch.bfloat16 and x.is_cuda and _tn_ok(rows, n_out, n_in)
@@ -292,30 +353,34 @@ class _LinearFn(torch.autograd.Function):
         ctx.meta = (weight.dtype, None if bias is None else bias.dtype, x.shape)
         ctx.f32own = (not own and x.dtype == torch.float32 and x.is_cuda and _tn_ok_f32(rows, n_out, n_in)
                       and (not ctx.needs_input_grad[0] or _tn_ok_f32(rows, n_in, n_out)))
+        ctx.ln = ln is not None
         if ctx.f32own:          # f32-class mode of the same kernels (the parity configuration)
             w3, wt3 = weight_copies(weight, f32=True)
             x2 = x2 if x2.is_contiguous() else x2.contiguous()
-            ctx.save_for_backward(x2, wt3)
+            ctx.save_for_backward(*(ln.saved() if ctx.ln else (x2,)), wt3)
             y = linear_tn_raw(split3(x2, 0), w3, _f32(bias), C.EPI_BIAS, f32=True)
             return y.reshape(*x.shape[:-1], n_out)
         if own:
             w, wt = weight_copies(weight)
-            ctx.save_for_backward(x2 if x2.is_contiguous() else x2.contiguous(), wt)
-            y = linear_tn_raw(x2 if x2.is_contiguous() else x2.contiguous(), w, _f32(bias), C.EPI_BIAS)
+            x2 = x2 if x2.is_contiguous() else x2.contiguous()
+            ctx.save_for_backward(*(ln.saved() if ctx.ln else (x2,)), wt)
+            y = linear_tn_raw(x2, w, _f32(bias), C.EPI_BIAS)
             return y.reshape(*x.shape[:-1], n_out)
         if x.dtype == torch.bfloat16 and rows >= 4096:
             warn_once(('linear', n_out, n_in), f'Linear [{n_out},{n_in}] runs on the library GEMM (lvl_linear_tn needs '
                                                'out % 256 == 0 and in % 64 == 0)')
         w = weight if weight.dtype == x.dtype else weight.to(x.dtype)
         b = None if bias is None else (bias if bias.dtype == x.dtype else bias.to(x.dtype))
-        ctx.save_for_backward(x2, w)
+        ctx.save_for_backward(*(ln.saved() if ctx.ln else (x2,)), w)
         with torch.autocast('cuda', enabled=False):
             return torch.nn.functional.linear(x, w, b)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w = ctx.saved_tensors                 # own path: w is the TRANSPOSED copy [in, out]
+        *kept, w = ctx.saved_tensors              # own path: w is the TRANSPOSED copy [in, out]
         wdt, bdt, xshape = ctx.meta
+        # the weight gradient's operand: kept, or (ln) rebuilt right before its only reader
+        x_rows = (lambda: _ln_rebuild(kept, (-1, xshape[-1]))) if ctx.ln else (lambda: kept[0])
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
@@ -326,17 +391,19 @@ class _LinearFn(torch.autograd.Function):
                 if ctx.needs_input_grad[0]:
                     dx = linear_tn_raw(split3(dy2, 0), w, None, C.EPI_BIAS, f32=True).reshape(xshape)
                 if ctx.needs_input_grad[1]:
-                    dw = _wgrad_f32(dy2, x2, wdt)
+                    dw = _wgrad_f32(dy2, x_rows(), wdt)
                 if bdt is not None and ctx.needs_input_grad[2]:
                     db = dy2.sum(0).to(bdt)
-                return dx, dw, db
+                return dx, dw, db, None
             if ctx.needs_input_grad[0]:
                 dx = (linear_tn_raw(dy2, w, None, C.EPI_BIAS) if ctx.own else dy2 @ w).reshape(xshape)
             if ctx.needs_input_grad[1]:
+                x2 = x_rows()
                 dw = _wgrad(dy2, x2, wdt) if (ctx.own or x2.dtype != torch.float32) else _wgrad_f32(dy2, x2, wdt)
+                del x2
             if bdt is not None and ctx.needs_input_grad[2]:
                 db = dy2.sum(0, dtype=torch.float32).to(bdt)      # f32 accumulation AND f32 result
-        return dx, dw, db
+        return dx, dw, db, None
 
 
 class _MlpFn(torch.autograd.Function):
@@ -350,55 +417,90 @@ class _MlpFn(torch.autograd.Function):
     LVL_EPI_QUICKGELU_BWD)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2):
+    def forward(ctx, x, w1, b1, w2, ln=None):
         x2 = x.reshape(-1, x.shape[-1])
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         f32 = ctx.f32 = x.dtype == torch.float32        # f32-class mode: term images in, float32 u / a / y
+        sel = ctx.sel = ln is not None                  # selective recompute: keep u, neither x (a LayerNorm output) nor a
         w1b, w1t = weight_copies(w1, f32)
         w2b, w2t = weight_copies(w2, f32)
         a, u = linear_tn_raw(split3(x2, 0) if f32 else x2, w1b, _f32(b1),
-                             C.EPI_BIAS_QUICKGELU if f32 else C.EPI_BIAS_QUICKGELU_DERIV, f32=f32)
+                             C.EPI_BIAS_QUICKGELU if (f32 or sel) else C.EPI_BIAS_QUICKGELU_DERIV, f32=f32)
         y = linear_tn_raw(split3(a, 0) if f32 else a, w2b, None, C.EPI_BIAS, f32=f32)
-        ctx.save_for_backward(x2, u, a, w1t, w2t)
+        if sel:
+            ctx.save_for_backward(*ln.saved(), u, w1t, w2t)
+        else:
+            ctx.save_for_backward(x2, u, a, w1t, w2t)
         ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, x.shape)
         return y.reshape(*x.shape[:-1], w2.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        x2, u, a, w1t, w2t = ctx.saved_tensors
         w1dt, b1dt, w2dt, xshape = ctx.meta
+        if ctx.sel:
+            *kept, u, w1t, w2t = ctx.saved_tensors
+            x2 = a = None
+        else:
+            x2, u, a, w1t, w2t = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         if ctx.f32:
             dy2 = dy2.float()
-            du, db1 = linear_tn_raw(split3(dy2, 0), w2t, None, C.EPI_QUICKGELU_BWD, aux_in=u, f32=True)
-            dw2 = _wgrad_f32(dy2, a, w2dt) if ctx.needs_input_grad[3] else None
-            dx = (linear_tn_raw(split3(du, 0), w1t, None, C.EPI_BIAS, f32=True).reshape(xshape)
-                  if ctx.needs_input_grad[0] else None)
-            dw1 = _wgrad_f32(du, x2, w1dt) if ctx.needs_input_grad[1] else None
-            return dx, dw1, (db1.to(b1dt) if (b1dt is not None and ctx.needs_input_grad[2]) else None), dw2
-        du, db1 = linear_tn_raw(dy2, w2t, None, C.EPI_MUL_AUX_COLSUM, aux_in=u)
-        dw2 = _wgrad(dy2, a, w2dt) if ctx.needs_input_grad[3] else None
-        dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
-        dw1 = _wgrad(du, x2, w1dt) if ctx.needs_input_grad[1] else None
-        return dx, dw1, (db1.to(b1dt) if (b1dt is not None and ctx.needs_input_grad[2]) else None), dw2
+        dx, dw1, db1, dw2 = _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept if ctx.sel else None)
+        return dx, dw1, db1, dw2, None
 
 
-def mlp_quickgelu(x, w1, b1, w2):
-    """fc2(QuickGELU(fc1(x))) minus fc2's bias; fused GEMM epilogues in bf16, composed kernels otherwise."""
+def _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept, need=(0, 1, 2, 3)):
+    """The backward of fc2(QuickGELU(fc1(x) + b1)) shared by _MlpFn and _MlpResidualLayerNormFn: (dx, dw1, db1, dw2) for
+    the gradient dy2 [rows, D] of fc2's output. need: positions of x, w1, b1, w2 among the Function's inputs.
+    Plain: x2 and a were kept; u is quickgelu'(u) in bf16 (one multiply in the epilogue) and the pre-activation in f32.
+    Selective (ctx.sel): u is the pre-activation in both; a = QuickGELU(u) and then x = the LayerNorm output of the recipe
+    `kept` are rebuilt one after the other, each right before the weight-gradient GEMM that reads it and only if that
+    gradient is wanted, so that at most one [rows, 4D] and one [rows, D] rebuilt tensor are alive at a time."""
+    w1dt, b1dt, w2dt, xshape = ctx.meta[0], ctx.meta[1], ctx.meta[2], ctx.meta[-1]
+    f32, sel = ctx.f32, ctx.sel
+    gx, gw1, gb1, gw2 = (ctx.needs_input_grad[i] for i in need)
+    wgrad = _wgrad_f32 if f32 else _wgrad
+    if f32:
+        du, db1 = linear_tn_raw(split3(dy2, 0), w2t, None, C.EPI_QUICKGELU_BWD, aux_in=u, f32=True)
+    else:
+        du, db1 = linear_tn_raw(dy2, w2t, None, C.EPI_QUICKGELU_BWD if sel else C.EPI_MUL_AUX_COLSUM, aux_in=u)
+    dw2 = None
+    if gw2:
+        if sel:
+            a = quickgelu_apply_raw(u)
+        dw2 = wgrad(dy2, a, w2dt)
+    del a, u
+    if f32:
+        dx = linear_tn_raw(split3(du, 0), w1t, None, C.EPI_BIAS, f32=True).reshape(xshape) if gx else None
+    else:
+        dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if gx else None
+    dw1 = None
+    if gw1:
+        if sel:
+            x2 = _ln_rebuild(kept, (-1, xshape[-1]))
+        dw1 = wgrad(du, x2, w1dt)
+    return dx, dw1, (db1.to(b1dt) if (b1dt is not None and gb1) else None), dw2
+
+
+def mlp_quickgelu(x, w1, b1, w2, ln=None):
+    """fc2(QuickGELU(fc1(x))) minus fc2's bias; fused GEMM epilogues in bf16, composed kernels otherwise.
+    ln: the LnRecipe of x (selective activation recompute: neither x nor the hidden activation is kept by the fused
+    function; the composed form keeps the hidden activation and rebuilds x only)."""
     x = _act(x)
+    ln = _ln_for(ln, x)
     rows = x.numel() // x.shape[-1]
     if (x.dtype == torch.bfloat16 and x.is_cuda and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1])
             and _tn_ok(rows, w1.shape[1], w1.shape[0]) and _tn_ok(rows, w2.shape[0], w2.shape[1])
             and _tn_ok(rows, w2.shape[1], w2.shape[0])):
-        return _MlpFn.apply(x, w1, b1, w2)
+        return _MlpFn.apply(x, w1, b1, w2, ln)
     if (x.dtype == torch.float32 and x.is_cuda and b1 is not None and w1.dtype == torch.float32
             and _tn_ok_f32(rows, w1.shape[0], w1.shape[1]) and _tn_ok_f32(rows, w1.shape[1], w1.shape[0])
             and _tn_ok_f32(rows, w2.shape[0], w2.shape[1]) and _tn_ok_f32(rows, w2.shape[1], w2.shape[0])):
-        return _MlpFn.apply(x, w1, b1, w2)          # the same fused epilogues in f32-class mode
-    return linear(bias_quick_gelu(linear(x, w1), b1), w2)
+        return _MlpFn.apply(x, w1, b1, w2, ln)      # the same fused epilogues in f32-class mode
+    return linear(bias_quick_gelu(linear(x, w1, ln=ln), b1), w2)
 
 
 def linear_wgrad_raw(dy, x, want_dbias: bool, ws_floats: int = -1):
@@ -589,9 +691,10 @@ def project(x, proj):
     return linear(x, proj.t())
 
 
-def linear(x, weight, bias=None):
+def linear(x, weight, bias=None, ln=None):
     """nn.Linear forward with hand-written forward / input-gradient / weight-gradient GEMMs behind it.
-    Activation dtype = x.dtype (the autocast dtype when autocast is on; fp16 -> bf16); parameters stay masters."""
+    Activation dtype = x.dtype (the autocast dtype when autocast is on; fp16 -> bf16); parameters stay masters.
+    ln: the LnRecipe of x when x is a LayerNorm output that is to be rebuilt in backward instead of kept (_LinearFn)."""
     x = _act(x)
     if x.dtype == torch.bfloat16 and x.is_cuda and not (torch.is_grad_enabled() and (
             x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))):
@@ -613,7 +716,7 @@ def linear(x, weight, bias=None):
                 and rows * max(3 * n_in, n_out) * 4 < (1 << 31)):
             return linear_f32_rows(x.reshape(-1, n_in), weight_copies(weight, f32=True)[0],
                                    _f32(bias)).reshape(*x.shape[:-1], n_out)
-    return _LinearFn.apply(x, weight, bias)
+    return _LinearFn.apply(x, weight, bias, _ln_for(ln, x))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -630,6 +733,29 @@ def layernorm_fwd_raw(x, x2, xbias, gamma, beta, eps, keep_sum):
                                       C.ptr(y), C.ptr(mean), C.ptr(rstd), rows, cols, float(eps),
                                       C.dtype_code(x), C.stream_ptr()), 'lvl_layernorm_fwd')
     return y, s, mean, rstd
+
+
+def layernorm_apply_raw(x, x2, xbias, gamma, beta, mean, rstd):
+    """One lvl_layernorm_apply call: the y of the layernorm_fwd_raw call that had these operands and returned this
+    mean / rstd, to the bit (pass its kept sum as x with x2 = xbias = None)."""
+    C.require_device(x, x2, xbias, gamma, beta, mean, rstd)
+    rows, cols = _rows_cols(x)
+    y = torch.empty_like(x)
+    C.check(C.lib().lvl_layernorm_apply(C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(beta), C.ptr(mean),
+                                        C.ptr(rstd), C.ptr(y), rows, cols, C.dtype_code(x), C.stream_ptr()),
+            'lvl_layernorm_apply')
+    return y
+
+
+def quickgelu_apply_raw(u):
+    """One lvl_quickgelu_apply call: a = QuickGELU(u) with the arithmetic of linear_tn_raw's EPI_BIAS_QUICKGELU epilogue
+    (whose second result is u)."""
+    C.require_device(u)
+    rows, cols = _rows_cols(u)
+    a = torch.empty_like(u)
+    C.check(C.lib().lvl_quickgelu_apply(C.ptr(u), C.ptr(a), rows, cols, C.dtype_code(u), C.stream_ptr()),
+            'lvl_quickgelu_apply')
+    return a
 
 
 def layernorm_bwd_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_plain=False):
@@ -655,19 +781,21 @@ class _LayerNormFn(torch.autograd.Function):
     """y = LN(x) ; see lvl_layernorm_fwd/bwd."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps):
+    def forward(ctx, x, weight, bias, eps, rec=None):
         x = x.contiguous()
         g, b = _f32(weight), _f32(bias)
         y, _, mean, rstd = layernorm_fwd_raw(x, None, None, g, b, eps, False)
         ctx.save_for_backward(x, g, mean, rstd)
         ctx.pdt = (weight.dtype, bias.dtype)
+        if rec is not None:
+            rec.fill(x, None, None, g, b, mean, rstd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, g, mean, rstd = ctx.saved_tensors
         dx, dg, db, _ = layernorm_bwd_raw(dy.contiguous(), x, None, None, g, mean, rstd, None, False)
-        return dx, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None
+        return dx, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None
 
 
 # Residual stream dtype under autocast. Default: the autocast dtype (bf16) from the patch embedding to the final norm
@@ -689,20 +817,26 @@ def _narrow(h):
     return h.to(lp) if (lp is not None and h.dtype == torch.float32) else h
 
 
-def layer_norm(x, weight, bias, eps, stream=False):
-    """stream=True: the output IS the residual stream (ln_pre): it keeps the dtype of x."""
-    y = _LayerNormFn.apply(lowp(x), weight, bias, eps)
-    return y if stream else _narrow(y)
+def layer_norm(x, weight, bias, eps, stream=False, recipe=False):
+    """stream=True: the output IS the residual stream (ln_pre): it keeps the dtype of x.
+    recipe=True (here and in the fused forms below): the result is followed by the LnRecipe from which the Linear that
+    consumes the normalised rows rebuilds them instead of keeping them (`ln=` of linear / mlp_quickgelu / ...)."""
+    rec = LnRecipe() if recipe else None
+    y = _LayerNormFn.apply(lowp(x), weight, bias, eps, rec)
+    y = y if stream else _narrow(y)
+    return (y, rec) if recipe else y
 
 
 class _AddLayerNormFn(torch.autograd.Function):
     """(s, h) = (res + y + ybias, LN(res + y + ybias)); s is only materialised when keep_sum."""
 
     @staticmethod
-    def forward(ctx, res, y, ybias, weight, bias, eps, keep_sum):
+    def forward(ctx, res, y, ybias, weight, bias, eps, keep_sum, rec=None):
         res, y = res.contiguous(), y.contiguous()
         yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
         h, s, mean, rstd = layernorm_fwd_raw(res, y, yb, g, b, eps, keep_sum)
+        if rec is not None:
+            rec.fill(*((s, None, None) if keep_sum else (res, y, yb)), g, b, mean, rstd)
         if keep_sum:
             ctx.save_for_backward(s, g, mean, rstd)
         else:
@@ -726,7 +860,7 @@ class _AddLayerNormFn(torch.autograd.Function):
             res, y, yb, g, mean, rstd = ctx.saved_tensors
             dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), res, y, yb, g, mean, rstd, None, ctx.has_ybias)
         dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
-        return dx, dx, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None
+        return dx, dx, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None
 
 
 # Residual adds in GEMM epilogues (LVL_EPI_BIAS_RESIDUAL; LAVILA_RESIDUAL_EPILOGUE=0 restores the composed form): the space
@@ -744,15 +878,17 @@ class _LinearResidualLayerNormFn(torch.autograd.Function):
     weight gradient: lvl_linear_wgrad)."""
 
     @staticmethod
-    def forward(ctx, x, weight, lbias, res, gamma, beta, eps, xtoken=None):
+    def forward(ctx, x, weight, lbias, res, gamma, beta, eps, xtoken=None, rec=None):
         x2 = x.reshape(-1, x.shape[-1])
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         res2 = res.reshape(-1, res.shape[-1])
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
         w, wt = weight_copies(weight)
         s = linear_tn_raw(x2, w, _f32(lbias), C.EPI_BIAS_RESIDUAL, aux_in=res2)
-        g = _f32(gamma)
-        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, _f32(beta), eps, False)
+        g, b = _f32(gamma), _f32(beta)
+        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
+        if rec is not None:
+            rec.fill(s, None, None, g, b, mean, rstd)
         ctx.has_token = xtoken is not None
         ctx.save_for_backward(x2, wt, s, g, mean, rstd, *((weight,) if ctx.has_token else ()))
         ctx.meta = (weight.dtype, None if lbias is None else lbias.dtype, gamma.dtype, beta.dtype, x.shape)
@@ -775,10 +911,10 @@ class _LinearResidualLayerNormFn(torch.autograd.Function):
             dtok = vec_mat(dcol, saved[6]) if want_tok else None
         db = dcol.to(bdt) if (bdt is not None and ctx.needs_input_grad[2]) else None
         return (dx, dw, db, dsum.reshape(ds.shape if ds is not None else dh.shape), dg.to(gdt), dbeta.to(betadt), None,
-                dtok)
+                dtok, None)
 
 
-def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=None):
+def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=None, recipe=False):
     """(s, h) = (res + Linear(x), LayerNorm(s)) through the GEMM's residual epilogue, or None when the shapes / dtypes are
     not the benched bf16 configuration (the caller then composes linear + add_layer_norm as before). xtoken: the
     column-sum token of x (see COLSUM_TOKENS)."""
@@ -790,8 +926,9 @@ def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=N
         return None
     if xtoken is not None and weight.dtype != torch.float32:
         xtoken = None
-    s, h = _LinearResidualLayerNormFn.apply(x, weight, lbias, res, gamma, beta, eps, xtoken)
-    return s, _narrow(h)
+    rec = LnRecipe() if recipe else None
+    s, h = _LinearResidualLayerNormFn.apply(x, weight, lbias, res, gamma, beta, eps, xtoken, rec)
+    return (s, _narrow(h), rec) if recipe else (s, _narrow(h))
 
 
 class _MlpResidualLayerNormFn(torch.autograd.Function):
@@ -801,50 +938,60 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
     gradient, leaves ds and its column sums = d b2), then _MlpFn's backward on ds."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps):
+    def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, rec=None):
         x2 = x.reshape(-1, x.shape[-1])
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         res2 = res.reshape(-1, res.shape[-1])
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
+        ctx.f32 = False
+        sel = ctx.sel = ln is not None       # selective recompute, as in _MlpFn: keep u, neither x nor a
         w1b, w1t = weight_copies(w1)
         w2b, w2t = weight_copies(w2)
-        a, u = linear_tn_raw(x2, w1b, _f32(b1), C.EPI_BIAS_QUICKGELU_DERIV)
+        a, u = linear_tn_raw(x2, w1b, _f32(b1), C.EPI_BIAS_QUICKGELU if sel else C.EPI_BIAS_QUICKGELU_DERIV)
         s = linear_tn_raw(a, w2b, _f32(b2), C.EPI_BIAS_RESIDUAL, aux_in=res2)
-        g = _f32(gamma)
-        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, _f32(beta), eps, False)
-        ctx.save_for_backward(x2, u, a, w1t, w2t, s, g, mean, rstd)
+        g, b = _f32(gamma), _f32(beta)
+        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
+        if rec is not None:
+            rec.fill(s, None, None, g, b, mean, rstd)
+        if sel:
+            ctx.save_for_backward(*ln.saved(), u, w1t, w2t, s, g, mean, rstd)
+        else:
+            ctx.save_for_backward(x2, u, a, w1t, w2t, s, g, mean, rstd)
         ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype, gamma.dtype,
                     beta.dtype, x.shape)
         return s.reshape(res.shape), h.reshape(res.shape)
 
     @staticmethod
     def backward(ctx, ds, dh):
-        x2, u, a, w1t, w2t, s, g, mean, rstd = ctx.saved_tensors
+        kept = x2 = a = None
+        if ctx.sel:
+            *kept, u, w1t, w2t, s, g, mean, rstd = ctx.saved_tensors
+        else:
+            x2, u, a, w1t, w2t, s, g, mean, rstd = ctx.saved_tensors
         w1dt, b1dt, w2dt, b2dt, gdt, betadt, xshape = ctx.meta
         dadd = None if ds is None else ds.reshape(s.shape).contiguous()
         dsum, dg, dbeta, dcol = layernorm_bwd_raw(dh.reshape(s.shape).contiguous(), s, None, None, g, mean, rstd, dadd,
                                                   b2dt is not None)
+        del dadd, s
         with torch.autocast('cuda', enabled=False):
-            du, db1 = linear_tn_raw(dsum, w2t, None, C.EPI_MUL_AUX_COLSUM, aux_in=u)
-            dw2 = _wgrad(dsum, a, w2dt) if ctx.needs_input_grad[3] else None
-            dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
-            dw1 = _wgrad(du, x2, w1dt) if ctx.needs_input_grad[1] else None
-        return (dx, dw1, db1.to(b1dt) if (b1dt is not None and ctx.needs_input_grad[2]) else None, dw2,
-                dcol.to(b2dt) if (b2dt is not None and ctx.needs_input_grad[4]) else None,
-                dsum.reshape(dh.shape), dg.to(gdt), dbeta.to(betadt), None)
+            dx, dw1, db1, dw2 = _mlp_backward(ctx, dsum, x2, u, a, w1t, w2t, kept)
+        return (dx, dw1, db1, dw2, dcol.to(b2dt) if (b2dt is not None and ctx.needs_input_grad[4]) else None,
+                dsum.reshape(dh.shape), dg.to(gdt), dbeta.to(betadt), None, None, None)
 
 
-def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps):
+def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, recipe=False):
     """(s, h) = (res + Mlp(x), LayerNorm(s)) with the residual add in fc2's GEMM epilogue, or None when the configuration
-    is not the benched bf16 one (the caller then composes mlp_quickgelu + add_layer_norm)."""
+    is not the benched bf16 one (the caller then composes mlp_quickgelu + add_layer_norm). ln: the LnRecipe of x (see
+    mlp_quickgelu); recipe: see layer_norm."""
     x, res = _act(x), lowp(res)
     rows = x.numel() // x.shape[-1]
     if not (RESIDUAL_EPILOGUE and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and x.is_cuda
             and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1]) and _tn_ok(rows, w1.shape[1], w1.shape[0])
             and _tn_ok(rows, w2.shape[0], w2.shape[1]) and _tn_ok(rows, w2.shape[1], w2.shape[0])):
         return None
-    s, h = _MlpResidualLayerNormFn.apply(x, w1, b1, w2, b2, res, gamma, beta, eps)
-    return s, _narrow(h)
+    rec = LnRecipe() if recipe else None
+    s, h = _MlpResidualLayerNormFn.apply(x, w1, b1, w2, b2, res, gamma, beta, eps, _ln_for(ln, x), rec)
+    return (s, _narrow(h), rec) if recipe else (s, _narrow(h))
 
 
 class _AddLayerNormPassFn(torch.autograd.Function):
@@ -854,10 +1001,12 @@ class _AddLayerNormPassFn(torch.autograd.Function):
     (dx = dx_plain + d_res_out) instead of by a separate full-size add of the autograd engine."""
 
     @staticmethod
-    def forward(ctx, res, y, ybias, weight, bias, eps, ytoken=None):
+    def forward(ctx, res, y, ybias, weight, bias, eps, ytoken=None, rec=None):
         res, y = res.contiguous(), y.contiguous()
         yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
         h, _, mean, rstd = layernorm_fwd_raw(res, y, yb, g, b, eps, False)
+        if rec is not None:
+            rec.fill(res, y, yb, g, b, mean, rstd)
         ctx.save_for_backward(res, y, yb, g, mean, rstd)
         ctx.has_ybias = ybias is not None
         ctx.has_token = ytoken is not None
@@ -876,26 +1025,28 @@ class _AddLayerNormPassFn(torch.autograd.Function):
                                                      want_sum, want_plain=True)
         dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
         dtok = dsum if (ctx.has_token and ctx.needs_input_grad[6]) else None      # token rule: sum_rows(dy) itself
-        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, dtok
+        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, dtok, None
 
 
-def add_layer_norm_pass(res, y, ybias, weight, bias, eps, ytoken=None):
+def add_layer_norm_pass(res, y, ybias, weight, bias, eps, ytoken=None, recipe=False):
     """Returns (res_again, h) with h = LayerNorm(res + y (+ ybias)); use res_again for the next consumer of res.
     ytoken: the column-sum token of y (see COLSUM_TOKENS)."""
     res = lowp(res)
     if y.dtype != res.dtype:
         y, ytoken = y.to(res.dtype), None
-    r, h = _AddLayerNormPassFn.apply(res, y, ybias, weight, bias, eps, ytoken)
-    return r, _narrow(h)
+    rec = LnRecipe() if recipe else None
+    r, h = _AddLayerNormPassFn.apply(res, y, ybias, weight, bias, eps, ytoken, rec)
+    return (r, _narrow(h), rec) if recipe else (r, _narrow(h))
 
 
-def add_layer_norm(res, y, ybias, weight, bias, eps, keep_sum=True):
+def add_layer_norm(res, y, ybias, weight, bias, eps, keep_sum=True, recipe=False):
     """Returns (s, h) with s = res + y (+ ybias) and h = LayerNorm(s). With keep_sum=False s is None."""
     res = lowp(res)
     if y.dtype != res.dtype:
         y = y.to(res.dtype)
-    s, h = _AddLayerNormFn.apply(res, y, ybias, weight, bias, eps, keep_sum)
-    return (s if keep_sum else None), _narrow(h)
+    rec = LnRecipe() if recipe else None
+    s, h = _AddLayerNormFn.apply(res, y, ybias, weight, bias, eps, keep_sum, rec)
+    return ((s if keep_sum else None), _narrow(h)) + ((rec,) if recipe else ())
 
 
 # --------------------------------------------------------------------------------------------------

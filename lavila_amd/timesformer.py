@@ -209,13 +209,14 @@ class VarAttention(nn.Module):
             return 'time', int(einops_dims['n'])
         raise NotImplementedError(f'einops pattern {einops_to!r}')
 
-    def core(self, x, mode, frames, n_per_frame, want_token=False):
+    def core(self, x, mode, frames, n_per_frame, want_token=False, ln=None):
         """qkv Linear + attention core; returns the pre-projection tensor [B,T,D] (want_token: and its column-sum token,
-        ops.COLSUM_TOKENS -- for callers that hand BOTH to a token-aware consumer and use the tensor nowhere else)."""
+        ops.COLSUM_TOKENS -- for callers that hand BOTH to a token-aware consumer and use the tensor nowhere else).
+        ln: the ops.LnRecipe of x (selective recompute: the qkv Linear rebuilds x in backward instead of keeping it)."""
         bias = self.qkv.bias
         # the GEMM adds the bias; its gradient comes out of the attention backward call (ops._DividedAttnFn),
         # hence the detached copy for the Linear
-        qkv = ops.linear(x, self.qkv.weight, None if bias is None else bias.detach())
+        qkv = ops.linear(x, self.qkv.weight, None if bias is None else bias.detach(), ln=ln)
         return ops.divided_attention(qkv, frames, n_per_frame, self.num_heads, mode, bias=bias, want_token=want_token)
 
     def forward(self, x, einops_from, einops_to, einops_dims):
@@ -230,27 +231,37 @@ class PendingMlp:
     the residual in its epilogue and the NEXT consumer's LayerNorm reads the sum, so the MLP is enqueued by that consumer
     (ops.mlp_residual_layer_norm). Travels in the `pend` slot of the fused residual chain; the fc2 bias in `pend_bias`."""
 
-    __slots__ = ('h', 'mlp')
+    __slots__ = ('h', 'mlp', 'ln')
 
-    def __init__(self, h, mlp):
-        self.h, self.mlp = h, mlp
+    def __init__(self, h, mlp, ln=None):
+        self.h, self.mlp, self.ln = h, mlp, ln      # ln: the ops.LnRecipe of h (selective recompute), or None
 
     def materialize(self):
         """The MLP branch as a tensor (fc2's bias still pending), for consumers that want the composed form."""
         m = self.mlp
-        return ops.mlp_quickgelu(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight)
+        return ops.mlp_quickgelu(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, ln=self.ln)
 
 
-def _close_pending(res, pend, pend_bias, norm):
-    """(s, h) = (res + pend + pend_bias, norm(s)) for a tensor or a PendingMlp in the `pend` slot."""
+def _close_pending(res, pend, pend_bias, norm, selective=False):
+    """(s, h) = (res + pend + pend_bias, norm(s)) for a tensor or a PendingMlp in the `pend` slot. selective: (s, h, recipe)
+    with the ops.LnRecipe of h, for the Linear that consumes h; a PendingMlp's own recipe travels with it."""
     if isinstance(pend, PendingMlp):
         m = pend.mlp
         fused = ops.mlp_residual_layer_norm(pend.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, pend_bias, res, norm.weight,
-                                            norm.bias, norm.eps)
+                                            norm.bias, norm.eps, ln=pend.ln, recipe=selective)
         if fused is not None:
             return fused
         pend = pend.materialize()
-    return ops.add_layer_norm(res, pend, pend_bias, norm.weight, norm.bias, norm.eps, keep_sum=True)
+    return ops.add_layer_norm(res, pend, pend_bias, norm.weight, norm.bias, norm.eps, keep_sum=True, recipe=selective)
+
+
+def _video_checkpoint_mode(use_checkpoint):
+    """ops.checkpoint_mode for the video tower: None, 'block' or 'selective'."""
+    mode = ops.checkpoint_mode(use_checkpoint)
+    if mode == 'selective' and ops.RESIDUAL_F32:
+        raise NotImplementedError("use_checkpoint='selective' with the float32 residual stream (LAVILA_RESIDUAL_F32): the "
+                                  'LayerNorm outputs there are casts of the kernel output and are not rebuilt')
+    return mode
 
 
 class SpaceTimeBlock(nn.Module):
@@ -282,71 +293,87 @@ class SpaceTimeBlock(nn.Module):
         return self.training and ((isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0.) or
                                   self.mlp.drop.p > 0.)
 
-    def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False):
+    def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False, selective=False):
         """One block on the fused residual chain.
 
         The block input is x = res + pend + pend_bias (pend/pend_bias may be None); that add is fused into
         norm3. Returns (x1, y, y_bias) with the block output = x1 + y + y_bias left *pending* so that the
-        next consumer (next block's norm3 or the final norm) fuses it too."""
+        next consumer (next block's norm3 or the final norm) fuses it too.
+        selective (use_checkpoint='selective'): the same kernels in the same order, but norm3 / norm1 / norm2's outputs and
+        the MLP hidden activation are not kept for backward: every LayerNorm hands out the recipe of its output
+        (ops.LnRecipe) and the Linear that consumes the output keeps that instead. A block that is dropping (stochastic
+        depth, MLP dropout) runs its plain path."""
         if self.attention_style != 'frozen-in-time':
             raise NotImplementedError
+        sel = bool(selective) and not self._dropping()
         n3, n1, n2 = self.norm3, self.norm1, self.norm2
+        r3 = r1 = r2 = None
         if pend is None:
             x = res
-            h3 = ops.layer_norm(x, n3.weight, n3.bias, n3.eps)
+            h3, *r3 = ops.layer_norm(x, n3.weight, n3.bias, n3.eps, recipe=True) if sel else \
+                (ops.layer_norm(x, n3.weight, n3.bias, n3.eps),)
         else:
-            x, h3 = _close_pending(res, pend, pend_bias, n3)
+            # (a pending MLP of the block before is closed here, in that block's mode: its recipe travels with it)
+            x, h3, *r3 = _close_pending(res, pend, pend_bias, n3, selective=sel)
+        r3 = r3[0] if r3 else None
         ta, sa = self.timeattn, self.attn
         tok_y = None
         if hasattr(self, 'alpha_timeattn'):
-            o_t = ta.core(h3, 'time', frames, n_per_frame)
+            o_t = ta.core(h3, 'time', frames, n_per_frame, ln=r3)
             y_t, b_t = torch.tanh(self.alpha_timeattn).to(o_t.dtype) * ops.linear(o_t, ta.proj.weight, ta.proj.bias), None
         else:
             # column-sum tokens (ops.COLSUM_TOKENS): o_t -> projection -> fused add + norm1; the backward hands
             # sum_rows(d o_t) to the attention backward, which needs it for the v third of d(qkv bias)
-            o_t, tok_o = ta.core(h3, 'time', frames, n_per_frame, want_token=True)
+            o_t, tok_o = ta.core(h3, 'time', frames, n_per_frame, want_token=True, ln=r3)
             (y_t, tok_y), b_t = ops.linear_with_token(o_t, ta.proj.weight, tok_o), ta.proj.bias
+        del h3
         # t = x + time_out is never stored; x is handed through so that its second use below sends its gradient into
         # norm1's backward kernel instead of a separate add
-        x, h1 = ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y)
+        x, h1, *r1 = ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y, recipe=sel)
+        r1 = r1[0] if r1 else None
         fused = None
         if not self._dropping():
             # ops.RESIDUAL_EPILOGUE: x1 leaves the projection GEMM (residual epilogue), norm2 reads it
-            o_s, tok_s = sa.core(h1, 'space', frames, n_per_frame, want_token=True)
+            o_s, tok_s = sa.core(h1, 'space', frames, n_per_frame, want_token=True, ln=r1)
             fused = ops.linear_residual_layer_norm(o_s, sa.proj.weight, sa.proj.bias, x, n2.weight, n2.bias, n2.eps,
-                                                   xtoken=tok_s)
+                                                   xtoken=tok_s, recipe=sel)
         else:
             o_s = sa.core(h1, 'space', frames, n_per_frame)
+        del h1
         if fused is not None:
-            x1, h2 = fused
+            x1, h2, *r2 = fused
         else:
             if self._dropping():
                 y_s, b_s = self.drop_path(ops.linear(o_s, sa.proj.weight, sa.proj.bias)), None
             else:
                 y_s, b_s = ops.linear(o_s, sa.proj.weight), sa.proj.bias
-            x1, h2 = ops.add_layer_norm(x, y_s, b_s, n2.weight, n2.bias, n2.eps, keep_sum=True)
+            x1, h2, *r2 = ops.add_layer_norm(x, y_s, b_s, n2.weight, n2.bias, n2.eps, keep_sum=True, recipe=sel)
+        r2 = r2[0] if r2 else None
         if self._dropping():
             return x1, self.drop_path(self.mlp(h2)), None
         if self.mlp._fused_act:
             if defer_mlp and ops.RESIDUAL_EPILOGUE and h2.dtype == torch.bfloat16 and x1.dtype == torch.bfloat16:
-                return x1, PendingMlp(h2, self.mlp), self.mlp.fc2.bias      # enqueued by the next consumer (_close_pending)
-            return x1, ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight), self.mlp.fc2.bias
+                return x1, PendingMlp(h2, self.mlp, r2), self.mlp.fc2.bias      # enqueued by the next consumer (_close_pending)
+            return (x1, ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, ln=r2),
+                    self.mlp.fc2.bias)
         return x1, ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight), self.mlp.fc2.bias
 
-    def chain_cls(self, res, pend, pend_bias, frames, n_per_frame):
+    def chain_cls(self, res, pend, pend_bias, frames, n_per_frame, selective=False):
         """The LAST block when only the cls row of its output is read (`norm(x)[:, 0]`, timesformer.py:377): same
         arithmetic as `chain`, restricted to what reaches that row. Time attention, norm1 and the k | v thirds of the space
         qkv run on every token (the cls query of the space attention reads the keys / values of all of them); the q
         third, the attention itself (lvl_cls_attn_*: one query per head), its output projection, norm2 and the whole MLP
         -- 2/3 of a block's flops -- run on the B cls rows only. Exact, like
         the caption trim of the text tower: the skipped rows feed nothing (their gradient is exactly zero in the
-        reference, too). Returns (x1, y, y_bias) of the cls rows, [B, D] each."""
+        reference, too). Returns (x1, y, y_bias) of the cls rows, [B, D] each.
+        selective: reaches _close_pending only (the pending MLP of the block before keeps neither its input nor its hidden
+        activation); this block's own LayerNorm outputs are kept (its MLP runs on B rows)."""
         n3, n1, n2 = self.norm3, self.norm1, self.norm2
         if pend is None:
             x = res
             h3 = ops.layer_norm(x, n3.weight, n3.bias, n3.eps)
         else:
-            x, h3 = _close_pending(res, pend, pend_bias, n3)
+            x, h3 = _close_pending(res, pend, pend_bias, n3, selective=selective)[:2]
         ta, sa = self.timeattn, self.attn
         tok_y = None
         if hasattr(self, 'alpha_timeattn'):
@@ -373,8 +400,11 @@ class SpaceTimeBlock(nn.Module):
                 time_n, space_f, use_checkpoint=False):
         """Reference signature (timesformer.py:173-174); materialises the block output."""
         frames, n = int(space_f), int(time_n)
-        if use_checkpoint:
+        mode = _video_checkpoint_mode(use_checkpoint)
+        if mode == 'block':
             x1, y, b = checkpoint.checkpoint(self.chain, x, None, None, frames, n, use_reentrant=False)
+        elif mode == 'selective':
+            x1, y, b = self.chain(x, None, None, frames, n, selective=True)
         else:
             x1, y, b = self.chain(x, None, None, frames, n)
         return _like_caller(x1 + (y if b is None else y + b.to(y.dtype)), x)
@@ -486,6 +516,7 @@ class SpaceTimeTransformer(nn.Module):
         if self.ln_pre is not None:
             x = ops.layer_norm(x, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps, stream=True)
         x = self.pos_drop(x)
+        mode = _video_checkpoint_mode(use_checkpoint)
         res, pend, pend_b = x, None, None
         hook = after_block
         last = len(self.blocks) - 1
@@ -493,10 +524,16 @@ class SpaceTimeTransformer(nn.Module):
             # the last block of a cls-pooled forward only has to produce its cls rows (SpaceTimeBlock.chain_cls)
             fn = blk.chain_cls if (cls_at_last and i == last and CLS_ONLY_LAST_BLOCK and not blk._dropping()
                                    and blk.attention_style == 'frozen-in-time') else blk.chain
-            if use_checkpoint:
+            if mode == 'block':
                 if isinstance(pend, PendingMlp):
                     pend = pend.materialize()
                 res, pend, pend_b = checkpoint.checkpoint(fn, res, pend, pend_b, frames, n, use_reentrant=False)
+            elif mode == 'selective':
+                # the plain step's kernels in the plain step's order; what is kept for backward differs (SpaceTimeBlock.chain)
+                if fn == blk.chain and i != last:
+                    res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True, selective=True)
+                else:
+                    res, pend, pend_b = fn(res, pend, pend_b, frames, n, selective=True)
             elif fn == blk.chain and i != last:
                 # the block's MLP may wait for the next block's norm3 (ops.RESIDUAL_EPILOGUE: residual add in fc2's epilogue)
                 res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True)
@@ -520,7 +557,8 @@ class SpaceTimeTransformer(nn.Module):
 
     def forward_features(self, x, use_checkpoint=False, cls_at_last=True):
         """Reference signature: x is [B, F, C, H, W] (timesformer.py:345-382; the narrator's entry with
-        cls_at_last=False, narrator.py:74). The gather reads this layout in place."""
+        cls_at_last=False, narrator.py:74). The gather reads this layout in place.
+        use_checkpoint: False / None, True, 'block' or 'selective' (ops.checkpoint_mode)."""
         with ops.model_forward():
             b, curr_frames, channels, _, _ = x.shape
             tok = self.patch_embed.tokens_from_btchw(x)
