@@ -255,6 +255,33 @@ int lvl_ssl_clip_loss_bwd(const void* img_all, const void* txt_all, const int32_
                           int B, int G, int E, int row0, float* dimg, float* dtxt, int dtype,
                           void* stream);
 
+/* ---- max-margin ranking losses of the retrieval fine-tune (loss.py:256-367) ---------------------------------
+ * MaxMarginRankingLoss (loss.py:267-312) and AdaptiveMaxMarginRankingLoss (loss.py:315-367) in slab form. With
+ * x[i,j] = cos(txt_i, img_j) (sim_matrix, loss.py:256-264: rows divided by max(norm, 1e-8)), d_i = x[i,i],
+ * m_i = margin * weight_i (weight NULL: 1) and c_i = m_i - d_i the loss is
+ *   (1/N) sum_i sum_j relu(c_i + x[i,j]) + relu(c_i + x[j,i]),
+ * over j != i with N = 2G(G-1) (fix_norm, loss.py:297-307) or over all j with N = 2G^2.
+ * img_all/txt_all: [G,E] dtype, the rank-ordered gathered RAW (un-normalised) rows; this rank owns rows
+ * [row0, row0+B). E in {64,128,256,512}; another width is an error.
+ * prepare (replaces loss.py:260-262,285 and the weight expansion :340-343) over all G rows:
+ *   prep [7,G] f32 = {1/max(|img_j|,1e-8), 1/max(|txt_j|,1e-8), d_j, c_j, m_j, max(|img_j|,1e-8), max(|txt_j|,1e-8)}.
+ * fwd (replaces loss.py:281-307 / :330-362: the G x G matrix, its four index-selected copies and the nonzero):
+ *   direction 0 sweeps the own text rows against all image rows (terms relu(c_i + x[i,j])), direction 1 the own image
+ *   rows against all text rows (terms relu(c_i + x[j,i])), the diagonal left out. hinge [2,B] f32: the row's hinge sum
+ *   (+ relu(m_i) when with_diag != 0: the diagonal term of fix_norm=False); count [2,B] int32: its active terms.
+ *   The loss is sum(hinge over all ranks) / N.
+ * bwd (replaces autograd through loss.py:256-312 and GatherLayer.backward's all-reduce): recomputes the scores and
+ *   writes coef * upstream * d(sum of all hinge terms)/d(RAW img_local | txt_local): [B,E] f32, normalisation
+ *   backward included; upstream (nullable): DEVICE pointer to d(objective)/d(loss); coef: host factor mult/N.
+ * Results are bit-reproducible and do not depend on how the G rows are split into slabs. */
+int lvl_margin_loss_prepare(const void* img_all, const void* txt_all, const float* weight, float margin, int G,
+                            int E, float* prep, int dtype, void* stream);
+int lvl_margin_loss_fwd(const void* img_all, const void* txt_all, const float* prep, int B, int G, int E,
+                        int row0, int with_diag, float* hinge, int32_t* count, int dtype, void* stream);
+int lvl_margin_loss_bwd(const void* img_all, const void* txt_all, const float* prep, const float* upstream,
+                        float coef, int B, int G, int E, int row0, float* dimg, float* dtxt, int dtype,
+                        void* stream);
+
 /* ---- cls-only attention (last block of a cls-pooled forward) ---------------------------------------------------
  * When only `norm(x)[:, 0]` leaves the tower (SpaceTimeTransformer.forward, timesformer.py:377,384-390) the last
  * block's space attention is needed for its cls query alone, which attends to all T tokens (timesformer.py:116-119):

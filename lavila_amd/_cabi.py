@@ -50,6 +50,9 @@ SIGNATURES = {
     'lvl_clip_loss_bwd': (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     'lvl_ssl_clip_loss_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     'lvl_ssl_clip_loss_bwd': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _I, _P]),
+    'lvl_margin_loss_prepare': (_I, [_P, _P, _P, _F, _I, _I, _P, _I, _P]),
+    'lvl_margin_loss_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    'lvl_margin_loss_bwd': (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _I, _P]),
     'lvl_linear_tn': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     'lvl_linear_wgrad': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     'lvl_cast_transpose': (_I, [_P, _P, _P, _I, _I, _P]),

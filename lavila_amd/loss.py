@@ -1,5 +1,7 @@
 """Contrastive (InfoNCE) loss of the dual encoder behind the reference interface
-(`lavila/models/loss.py`: gather_features :18-43, CLIPLoss :46-118).
+(`lavila/models/loss.py`: gather_features :18-43, CLIPLoss :46-118, SSLCLIPLoss :121-217) and the max-margin ranking
+losses of the retrieval fine-tune (sim_matrix :256-264, MaxMarginRankingLoss :267-312, AdaptiveMaxMarginRankingLoss
+:315-367; see _MarginRankingFn).
 
 Same constructor, same `criterion(outputs) -> {'loss','clip_loss','clip_acc'}` contract, same numbers.
 The plan is MI355X-first instead of a translation of the reference's NCCL call pattern:
@@ -284,3 +286,110 @@ class SSLCLIPLoss(nn.Module):
         return {'loss': loss, 'clip_loss': loss, 'num_gt': num_gt.reshape(1).long().cpu(),
                 'num_pseudo': num_pseudo.reshape(1).long().cpu(), 'clip_acc': acc, 'clip_acc_gt': acc_gt,
                 'clip_acc_pseudo': acc_pseudo}
+
+
+def sim_matrix(a, b, eps=1e-8):
+    """loss.py:256-264 for API completeness (the losses below never build the matrix)."""
+    unit = [t / t.norm(dim=1, keepdim=True).clamp_min(eps) for t in (a, b)]
+    return unit[0] @ unit[1].t()
+
+
+class _MarginRankingFn(torch.autograd.Function):
+    """Slab-parallel max-margin ranking loss (loss.py:267-367).
+
+      reference                                         here
+      ----------------------------------------------    -------------------------------------------------------
+      2-3 x gather_from_all (img, txt, weight)          1 x all_gather_rows of [img | txt | w]
+      every rank: the G x G cosine matrix, four G^2     each rank: its rows of both directions, two [B,G] sweeps
+      index-selected copies, a nonzero (host sync)      that never reach HBM; no host sync
+      backward: all_reduce of [W,B,E] per gather        backward: none -- the thresholds c_j of all rows come from
+                                                        the gathered rows, so the local gradient needs no other
+                                                        rank's result; one tiny gather of the partial sums in forward
+
+    Gradient convention: as on the vissl path of CLIPLoss, GatherLayer.backward sums W identical copies, so each rank
+    receives W x d(global loss)/d(its local rows). `weight` receives no gradient (the drivers pass data, not parameters).
+    """
+
+    @staticmethod
+    def forward(ctx, image_embed, text_embed, weight, crit):
+        from .distributed_utils import is_distributed_training_run
+        W = dist.get_world_size() if is_distributed_training_run() else 1
+        rank = dist.get_rank() if W > 1 else 0
+        B, E = image_embed.shape
+        dt = image_embed.dtype if (image_embed.dtype == text_embed.dtype and
+                                   image_embed.dtype in (torch.float32, torch.bfloat16)) else torch.float32
+        img, txt = image_embed.detach().to(dt), text_embed.detach().to(dt)
+        w = None if weight is None else weight.detach().to(img.device).float().reshape(-1)
+        if w is not None and w.shape[0] != B:
+            raise ValueError(f'weight has {w.shape[0]} entries for {B} pairs')
+        if W > 1 and w is not None:
+            both = all_gather_rows(torch.cat([img.float(), txt.float(), w[:, None]], dim=1))      # [G, 2E+1]
+            img_all, txt_all = both[:, :E].to(dt).contiguous(), both[:, E:2 * E].to(dt).contiguous()
+            w_all = both[:, 2 * E].contiguous()
+        elif W > 1:
+            both = all_gather_rows(torch.cat([img, txt], dim=1))                                  # [G, 2E]
+            img_all, txt_all, w_all = both[:, :E].contiguous(), both[:, E:].contiguous(), None
+        else:
+            img_all, txt_all, w_all = img.contiguous(), txt.contiguous(), None if w is None else w.contiguous()
+        G = img_all.shape[0]
+        row0 = rank * B
+        N = 2 * G * (G - 1) if crit.fix_norm else 2 * G * G
+
+        prep = crit._slab_prepare(img_all, txt_all, w_all, crit.margin)                          # [7,G] f32
+        hinge, _ = crit._slab_forward(img_all, txt_all, prep, B, row0, not crit.fix_norm)    # [2,B] f32, [2,B] i32
+        part = hinge.sum().reshape(1, 1)
+        total = all_gather_rows(part).sum() if W > 1 else part.sum()
+        loss = total / N                                 # G = 1 with fix_norm: 0 / 0 = NaN, the reference's empty mean
+        ctx.save_for_backward(img_all, txt_all, prep)
+        ctx.cfg = (B, row0, W, N, crit, image_embed.dtype, text_embed.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        img_all, txt_all, prep = ctx.saved_tensors
+        B, row0, W, N, crit, idt, tdt = ctx.cfg
+        up = dloss.detach().float().reshape(1).contiguous()
+        coef = float(W) / N if N else float('nan')
+        dimg, dtxt = crit._slab_backward(img_all, txt_all, prep, up, coef, B, row0)
+        return dimg.to(idt), dtxt.to(tdt), None, None
+
+
+class MaxMarginRankingLoss(nn.Module):
+    """Bidirectional max-margin ranking loss over the global batch -- loss.py:267-312. Same constructor, same
+    `forward(outputs, weight=None)` (the weight is ignored, as there), same output dict. Whether the batch is
+    gathered is decided as in the reference (`is_distributed_training_run()`), not by constructor arguments."""
+
+    adaptive = False
+
+    def __init__(self, margin=0.2, fix_norm=True):
+        super().__init__()
+        self.fix_norm = fix_norm
+        self.loss = nn.MarginRankingLoss(margin)         # attribute parity (loss.py:272); carries no state
+        self.margin = margin
+
+    # -- kernel hooks (tests override these three with the CPU restatement to exercise the collectives on gloo) ---
+    def _slab_prepare(self, img_all, txt_all, weight_all, margin):
+        return ops.margin_loss_prepare_raw(img_all, txt_all, weight_all, margin)
+
+    def _slab_forward(self, img_all, txt_all, prep, B, row0, with_diag):
+        return ops.margin_loss_fwd_raw(img_all, txt_all, prep, B, row0, with_diag)
+
+    def _slab_backward(self, img_all, txt_all, prep, upstream, coef, B, row0):
+        return ops.margin_loss_bwd_raw(img_all, txt_all, prep, upstream, coef, B, row0)
+
+    def forward(self, outputs, weight=None):
+        if self.adaptive and weight is None:
+            raise ValueError('AdaptiveMaxMarginRankingLoss needs the per-pair `weight` (forward(outputs, weight)): its '
+                             'margin is margin * weight')
+        loss = _MarginRankingFn.apply(outputs['image_embed'], outputs['text_embed'],
+                                      weight if self.adaptive else None, self)
+        return {'loss': loss, 'max_margin_loss': loss}
+
+
+class AdaptiveMaxMarginRankingLoss(MaxMarginRankingLoss):
+    """The same loss with the per-pair margin `margin * weight_i` -- loss.py:315-367."""
+
+    adaptive = True
+
+    def __init__(self, margin=0.4, fix_norm=True):
+        super().__init__(margin=margin, fix_norm=fix_norm)

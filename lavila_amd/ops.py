@@ -1433,3 +1433,42 @@ def ssl_clip_loss_bwd_raw(img_all, txt_all, ind_all, lse_all, scales3, upstream,
                                           C.ptr(scales3), C.ptr(upstream), float(coef), B, G, E, row0, C.ptr(dimg),
                                           C.ptr(dtxt), C.dtype_code(img_all), C.stream_ptr()), 'lvl_ssl_clip_loss_bwd')
     return dimg, dtxt
+
+
+# --------------------------------------------------------------------------------------------------
+# max-margin ranking losses of the retrieval fine-tune (raw kernels; autograd + collectives in lavila_amd/loss.py)
+# --------------------------------------------------------------------------------------------------
+def margin_loss_prepare_raw(img_all, txt_all, weight_all, margin: float):
+    """weight_all: [G] float32 device tensor or None (every weight 1). Returns prep [7,G] f32 =
+    {1/max(|img|,1e-8), 1/max(|txt|,1e-8), d, c, m, max(|img|,1e-8), max(|txt|,1e-8)}."""
+    C.require_device(img_all, txt_all, weight_all)
+    G, E = img_all.shape
+    prep = torch.empty(7, G, dtype=torch.float32, device=img_all.device)
+    C.check(C.lib().lvl_margin_loss_prepare(C.ptr(img_all), C.ptr(txt_all), C.ptr(weight_all), float(margin), G, E,
+                                            C.ptr(prep), C.dtype_code(img_all), C.stream_ptr()),
+            'lvl_margin_loss_prepare')
+    return prep
+
+
+def margin_loss_fwd_raw(img_all, txt_all, prep, B: int, row0: int, with_diag: bool):
+    """hinge [2,B] f32 (per direction and local row: sum of its hinge terms), count [2,B] int32 (its active terms)."""
+    C.require_device(img_all, txt_all, prep)
+    G, E = img_all.shape
+    hinge = torch.empty(2, B, dtype=torch.float32, device=img_all.device)
+    count = torch.empty(2, B, dtype=torch.int32, device=img_all.device)
+    C.check(C.lib().lvl_margin_loss_fwd(C.ptr(img_all), C.ptr(txt_all), C.ptr(prep), B, G, E, row0, int(with_diag),
+                                        C.ptr(hinge), C.ptr(count), C.dtype_code(img_all), C.stream_ptr()),
+            'lvl_margin_loss_fwd')
+    return hinge, count
+
+
+def margin_loss_bwd_raw(img_all, txt_all, prep, upstream, coef: float, B: int, row0: int):
+    """coef * upstream * d(sum of all hinge terms)/d(raw local rows): dimg, dtxt [B,E] f32."""
+    C.require_device(img_all, txt_all, prep, upstream)
+    G, E = img_all.shape
+    dimg = torch.empty(B, E, dtype=torch.float32, device=img_all.device)
+    dtxt = torch.empty(B, E, dtype=torch.float32, device=img_all.device)
+    C.check(C.lib().lvl_margin_loss_bwd(C.ptr(img_all), C.ptr(txt_all), C.ptr(prep), C.ptr(upstream), float(coef), B, G,
+                                        E, row0, C.ptr(dimg), C.ptr(dtxt), C.dtype_code(img_all), C.stream_ptr()),
+            'lvl_margin_loss_bwd')
+    return dimg, dtxt
