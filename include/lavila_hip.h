@@ -282,6 +282,37 @@ int lvl_margin_loss_bwd(const void* img_all, const void* txt_all, const float* p
                         float coef, int B, int G, int E, int row0, float* dimg, float* dtxt, int dtype,
                         void* stream);
 
+/* ---- vocabulary cross-entropy of the narrator's criterion (CaptionLoss, loss.py:220-253) -----------------------
+ * Row form of F.cross_entropy(logits [B,V,T], labels [B,T], ignore_index=pad_id, reduction='none') and the metric
+ * loop of loss.py:234-252. The logits are rows = B*T rows of `vocab` elements of dtype: row r starts at
+ * logits + r*row_stride ELEMENTS (row_stride >= vocab), class stride 1. Nothing is assumed about the alignment of a
+ * row beyond the element size; columns [vocab, row_stride) are never read. labels: int64, row r at
+ * labels[r*label_stride]. All arithmetic is float32.
+ * fwd, one pass over each row, per row:
+ *   lse     [rows] f32    log sum_j exp(x[r,j]); -inf entries are allowed anywhere in a row;
+ *   nll     [rows] f32    lse - x[r,label], exactly 0 when label == pad_id; the pad id is compared first and may lie
+ *                         outside [0,vocab); any other label outside [0,vocab) forms no address and gives NaN;
+ *   pred    [rows] int32  the FIRST index of the row's maximum (torch.argmax's tie rule, loss.py:239);
+ *   correct [rows] int32  (pred == label) & (label != pad_id);   counted [rows] int32  (label != pad_id).
+ * reduce, one workgroup, fixed summation order (no atomics; bit-reproducible), out3 [3] f32:
+ *   out3[0] = sum(nll) / (B*T)                                (reduction='none' then .mean(): pads count below)
+ *   out3[1] = 100 * sum(correct) / (sum(counted) + 1e-8)      (caption_acc, loss.py:252)
+ *   out3[2] = mean_b exp(sum_t nll[b,t] / sum_t counted[b,t]) (ppl, loss.py:243,253; a caption without a counted
+ *                                                              label gives 0/0 = NaN, as there)
+ * bwd, one pass: dlogits [rows, Vp] dtype, Vp = vocab rounded up to 8, 16-byte aligned:
+ *   dlogits[r,j] = coef * (*upstream) * (exp(x[r,j] - lse[r]) - [j == label_r])   for j < vocab, one rounding to dtype;
+ *   rows whose label is pad_id are exact zeros, rows whose label is out of range are NaN, and the columns
+ *   [vocab, Vp) of every row are written as zeros: every element of dlogits is written on every call.
+ *   upstream (nullable): DEVICE pointer to d(objective)/d(loss); coef: host factor 1/(B*T). */
+int lvl_token_xent_fwd(const void* logits, int64_t row_stride, const int64_t* labels, int64_t label_stride,
+                       int64_t rows, int vocab, int64_t pad_id, float* lse, float* nll, int32_t* pred,
+                       int32_t* correct, int32_t* counted, int dtype, void* stream);
+int lvl_token_xent_reduce(const float* nll, const int32_t* correct, const int32_t* counted, int B, int T,
+                          float* out3, void* stream);
+int lvl_token_xent_bwd(const void* logits, int64_t row_stride, const int64_t* labels, int64_t label_stride,
+                       const float* lse, const float* upstream, float coef, int64_t rows, int vocab, int64_t pad_id,
+                       void* dlogits, int dtype, void* stream);
+
 /* ---- cls-only attention (last block of a cls-pooled forward) ---------------------------------------------------
  * When only `norm(x)[:, 0]` leaves the tower (SpaceTimeTransformer.forward, timesformer.py:377,384-390) the last
  * block's space attention is needed for its cls query alone, which attends to all T tokens (timesformer.py:116-119):

@@ -1,7 +1,7 @@
 """Contrastive (InfoNCE) loss of the dual encoder behind the reference interface
 (`lavila/models/loss.py`: gather_features :18-43, CLIPLoss :46-118, SSLCLIPLoss :121-217) and the max-margin ranking
 losses of the retrieval fine-tune (sim_matrix :256-264, MaxMarginRankingLoss :267-312, AdaptiveMaxMarginRankingLoss
-:315-367; see _MarginRankingFn).
+:315-367; see _MarginRankingFn), and the narrator's criterion (CaptionLoss :220-253; see _CaptionFn).
 
 Same constructor, same `criterion(outputs) -> {'loss','clip_loss','clip_acc'}` contract, same numbers.
 The plan is MI355X-first instead of a translation of the reference's NCCL call pattern:
@@ -393,3 +393,85 @@ class AdaptiveMaxMarginRankingLoss(MaxMarginRankingLoss):
 
     def __init__(self, margin=0.4, fix_norm=True):
         super().__init__(margin=margin, fix_norm=fix_norm)
+
+
+class _CaptionFn(torch.autograd.Function):
+    """Token cross-entropy of the narrator in row form (loss.py:220-253).
+
+      reference                                            here
+      -----------------------------------------------      ------------------------------------------------------
+      F.cross_entropy(reduction='none') on [B,V,T]:         one pass over each of the B*T rows: lse, the label's
+      log-softmax image of the logits, then a gather         logit, the first argmax (csrc/caption_loss.hip)
+      a Python loop over B with an argmax of [V,T] each      one small reduce kernel: loss, caption_acc, ppl, on
+      and B host read-backs for ppl                          the device, no read-back
+      backward: softmax image kept from forward              backward: softmax recomputed from the logits and the
+                                                             saved per-row lse, written once in the logits' dtype
+
+    Saved for backward: the logits themselves (no copy when they arrive as the permuted view VCLM_HF.forward returns),
+    the labels and lse."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, crit):
+        B, V, T = logits.shape
+        if tuple(labels.shape) != (B, T):
+            raise ValueError(f'labels {tuple(labels.shape)} for logits {tuple(logits.shape)}: want [B, T] and [B, V, T]')
+        x = logits.detach()
+        in_place = (x.dtype in (torch.float32, torch.bfloat16) and x.stride(1) == 1 and x.stride(2) >= V and
+                    x.stride(0) == T * x.stride(2))
+        if in_place:                                     # [B,V,T] view of [B*T, >= V] rows: read where it lies
+            rows = x.as_strided((B * T, V), (x.stride(2), 1), x.storage_offset())
+        else:                                            # any other layout or dtype: one copy into padded rows
+            dt = x.dtype if x.dtype in (torch.float32, torch.bfloat16) else torch.float32
+            buf = torch.empty(B * T, (V + 7) // 8 * 8, dtype=dt, device=x.device)
+            buf.view(B, T, -1)[:, :, :V].copy_(x.permute(0, 2, 1))
+            rows = buf[:, :V]
+        lab = labels.detach().to(device=x.device, dtype=torch.int64).reshape(-1)   # a [B,T] copy of text[:, 1:] at most
+        lse, nll, _, correct, counted = crit._token_forward(rows, lab, crit.pad_id)
+        res = crit._token_reduce(nll, correct, counted, B, T)                        # [3] f32
+        loss, acc, ppl = res[0], res[1], res[2]
+        ctx.save_for_backward(logits if in_place else rows, lab, lse)
+        ctx.cfg = (B, V, T, in_place, crit, logits.dtype)
+        ctx.mark_non_differentiable(acc, ppl)
+        return loss, acc, ppl
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        kept, lab, lse = ctx.saved_tensors
+        B, V, T, in_place, crit, dtype = ctx.cfg
+        rows = kept.as_strided((B * T, V), (kept.stride(2), 1), kept.storage_offset()) if in_place else kept
+        up = dloss.detach().float().reshape(1).contiguous()
+        grad = crit._token_backward(rows, lab, lse, up, 1.0 / (B * T), crit.pad_id)   # [B*T, Vp], the rows' dtype
+        grad = grad.view(B, T, -1)[:, :, :V].permute(0, 2, 1)                          # [B, V, T] view of it
+        return grad.to(dtype), None, None
+
+
+class CaptionLoss(nn.Module):
+    """Teacher-forced token cross-entropy, token accuracy and perplexity of the narrator -- loss.py:220-253. Same
+    constructor (the pad id is read from `tokenizer.pad_token_id`, so a tokenizer is required, as there), same
+    `forward(outputs)` on {'text_tokens_logits': [B, V, T], 'labels': [B, T]} (what VCLM_HF.forward returns), same
+    output keys.
+
+    Departures: `loss` / `caption_loss` are 0-dim float32 whatever the logits' dtype; `caption_acc` and `ppl` are
+    non-differentiable 0-dim float32 tensors ON THE LOGITS' DEVICE (the reference assembles `ppl` from B `.item()`
+    read-backs into a CPU tensor; the drivers only call `.item()` on it). A label that is neither the pad id nor inside
+    [0, V) makes the loss NaN where torch raises a device assertion. float16 logits are computed in float32."""
+
+    def __init__(self, pad_id=0, tokenizer=None):
+        super().__init__()
+        self.pad_id = pad_id
+        self.tokenizer = tokenizer
+        self.pad_id = tokenizer.pad_token_id
+
+    # -- kernel hooks (tests override these three with the CPU restatement to exercise the host logic) ---
+    def _token_forward(self, rows, labels, pad_id):
+        return ops.token_xent_fwd_raw(rows, labels, pad_id)
+
+    def _token_reduce(self, nll, correct, counted, B, T):
+        return ops.token_xent_reduce_raw(nll, correct, counted, B, T)
+
+    def _token_backward(self, rows, labels, lse, upstream, coef, pad_id):
+        return ops.token_xent_bwd_raw(rows, labels, lse, upstream, coef, pad_id)
+
+    def forward(self, outputs):
+        loss, acc, ppl = _CaptionFn.apply(outputs['text_tokens_logits'], outputs['labels'], self)
+        return {'loss': loss, 'caption_loss': loss, 'caption_acc': acc, 'ppl': ppl}

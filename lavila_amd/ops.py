@@ -1472,3 +1472,72 @@ def margin_loss_bwd_raw(img_all, txt_all, prep, upstream, coef: float, B: int, r
                                         E, row0, C.ptr(dimg), C.ptr(dtxt), C.dtype_code(img_all), C.stream_ptr()),
             'lvl_margin_loss_bwd')
     return dimg, dtxt
+
+
+# --------------------------------------------------------------------------------------------------
+# vocabulary cross-entropy of the narrator's criterion (raw kernels; autograd + layouts in lavila_amd/loss.py)
+# --------------------------------------------------------------------------------------------------
+def _token_rows(logits, labels, *more):
+    """logits: a [rows, vocab] float32 / bfloat16 VIEW with class stride 1 and any row stride >= vocab (rows need not be
+    contiguous or 16-byte aligned); labels: [rows] int64 with any stride. Returns (rows, vocab)."""
+    for t in (logits, labels) + more:
+        if t is not None and not t.is_cuda:
+            raise C.HipExtensionError('lavila_amd: tensor on %s -- the HIP kernels need a ROCm device tensor; there is '
+                                      'no CPU fallback' % t.device)
+    C.require_device(*more)
+    if logits.device.index != torch.cuda.current_device() or labels.device != logits.device:
+        raise C.HipExtensionError(f'lavila_amd: logits on {logits.device}, labels on {labels.device}, current device '
+                                  f'cuda:{torch.cuda.current_device()}')
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or labels.dtype != torch.int64:
+        raise C.HipExtensionError(f'token_xent: logits {tuple(logits.shape)} / labels {tuple(labels.shape)} '
+                                  f'{labels.dtype}: want [rows, vocab] and [rows] int64')
+    rows, vocab = logits.shape
+    if vocab < 1 or (rows > 0 and logits.stride(1) != 1) or (rows > 1 and logits.stride(0) < vocab):
+        raise C.HipExtensionError(f'token_xent: logits strides {logits.stride()} for shape {tuple(logits.shape)}: the '
+                                  'class stride must be 1 and the row stride at least vocab')
+    return rows, vocab
+
+
+def _out_buffer(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise C.HipExtensionError(f'out= buffer {tuple(out.shape)} {out.dtype}: want contiguous {tuple(shape)} {dtype}')
+    return out
+
+
+def token_xent_fwd_raw(logits, labels, pad_id: int, out=None):
+    """One pass over each row. Returns (lse f32, nll f32, pred i32, correct i32, counted i32), each [rows]; `out`: an
+    optional tuple of five such buffers to write into."""
+    rows, vocab = _token_rows(logits, labels)
+    dev = logits.device
+    kinds = (torch.float32, torch.float32, torch.int32, torch.int32, torch.int32)
+    bufs = tuple(_out_buffer(None if out is None else out[k], (rows,), kinds[k], dev) for k in range(5))
+    C.check(C.lib().lvl_token_xent_fwd(C.ptr(logits), logits.stride(0) if rows > 1 else vocab, C.ptr(labels),
+                                       labels.stride(0) if rows > 1 else 1, rows, vocab, int(pad_id),
+                                       *(C.ptr(b) for b in bufs), C.dtype_code(logits), C.stream_ptr()),
+            'lvl_token_xent_fwd')
+    return bufs
+
+
+def token_xent_reduce_raw(nll, correct, counted, B: int, T: int, out=None):
+    """[3] f32 = {loss = sum(nll)/(B*T), caption_acc, ppl} from the per-row results, in a fixed summation order."""
+    C.require_device(nll, correct, counted)
+    if nll.numel() != B * T or correct.numel() != B * T or counted.numel() != B * T:
+        raise C.HipExtensionError(f'token_xent_reduce: {nll.numel()} rows for B={B} T={T}')
+    res = _out_buffer(out, (3,), torch.float32, nll.device)
+    C.check(C.lib().lvl_token_xent_reduce(C.ptr(nll), C.ptr(correct), C.ptr(counted), B, T, C.ptr(res), C.stream_ptr()),
+            'lvl_token_xent_reduce')
+    return res
+
+
+def token_xent_bwd_raw(logits, labels, lse, upstream, coef: float, pad_id: int, out=None):
+    """coef * upstream * d(sum of nll)/d(logits) in the logits' dtype: [rows, Vp], Vp = vocab rounded up to 8; pad rows
+    and the columns [vocab, Vp) are zeros, rows with an out-of-range label NaN. Every element is written."""
+    rows, vocab = _token_rows(logits, labels, lse, upstream)
+    grad = _out_buffer(out, (rows, (vocab + 7) // 8 * 8), logits.dtype, logits.device)
+    C.check(C.lib().lvl_token_xent_bwd(C.ptr(logits), logits.stride(0) if rows > 1 else vocab, C.ptr(labels),
+                                       labels.stride(0) if rows > 1 else 1, C.ptr(lse), C.ptr(upstream), float(coef),
+                                       rows, vocab, int(pad_id), C.ptr(grad), C.dtype_code(logits), C.stream_ptr()),
+            'lvl_token_xent_bwd')
+    return grad
