@@ -324,17 +324,24 @@ int lvl_cls_attn_fwd(const void* q, const void* kv, void* out, float* lse, int B
 int lvl_cls_attn_bwd(const void* q, const void* kv, const void* out, const void* dout, const float* lse, float* dq,
                      void* dkv, int B, int T, int H, int dtype, void* stream);
 
-/* ---- narrator seam: multi-query cross-attention pooling (inference) ------------------------------------------
+/* ---- narrator seam: multi-query cross-attention pooling ----------------------------------------------------------
  * The core of coca.py's CrossAttention (lavila/models/coca.py:93-123) between to_q / to_kv and to_out, as
  * VCLM_HF.encode_image runs it on the tower's token features (narrator.py:44-49,88-90): NQ x H query rows of 64
  * channels attend to the Tk context tokens through ONE shared key/value head:
  *   out[b,n,h,:] = softmax_j(0.125 * q[b,n,h,:] . k[b,j,:]) v[b,j,:]   (q * dim_head^-0.5, max-subtracted softmax)
  * q: [B or 1, NQ, H*64] with batch stride q_batch_stride elements (0 = the same queries for every clip: the narrator
- * repeats its learned img_queries); kv: [B, Tk, 128] = k | v as to_kv writes them; out: [B, NQ, H*64]. Forward only. */
+ * repeats its learned img_queries); kv: [B, Tk, 128] = k | v as to_kv writes them; out: [B, NQ, H*64].
+ * Backward, from q, kv and dout [B, NQ, H*64] alone (the softmax is recomputed): dq [B, NQ, H*64], or [NQ, H*64] when
+ * q_batch_stride is 0 -- the per-clip gradients of shared queries are then added in clip order -- and dkv [B, Tk, 128].
+ * f32 accumulation, no atomics, bit-reproducible. ws: lvl_mq_cross_attn_bwd_ws(B, NQ, H, q_batch_stride == 0) floats
+ * (host-side query; -1 for a shape with a non-positive extent). */
 int lvl_mq_cross_attn_fwd(const void* q, int64_t q_batch_stride, const void* kv, void* out, int B, int NQ, int H,
                           int Tk, int dtype, void* stream);
+int64_t lvl_mq_cross_attn_bwd_ws(int B, int NQ, int H, int shared_q);
+int lvl_mq_cross_attn_bwd(const void* q, int64_t q_batch_stride, const void* kv, const void* dout, void* dq, void* dkv,
+                          float* ws, int B, int NQ, int H, int Tk, int dtype, void* stream);
 
-/* ---- narrator decoder: gated-cross-attention GPT-2 (inference) --------------------------------------------------
+/* ---- narrator decoder: gated-cross-attention GPT-2 ---------------------------------------------------------------
  * The row passes of lavila/models/gpt2_gated.py's GPT2LMHeadModel around its Conv1D GEMMs (which run on lvl_linear_tn
  * against [out,in] bf16 copies of the [in,out] Conv1D weights). The reference's VCLM_HF.generate re-runs the whole prefix
  * for every token (narrator.py:118-143, use_cache=False); this ABI decodes ONE row per sequence and step against a
@@ -393,6 +400,31 @@ int lvl_decode_self_attn(const void* qkv, void* cache, const int* pos_dev, void*
                          void* stream);
 int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, int qrep, int Tk, int H, int dtype,
                             void* stream);
+/* Training forms of the row passes above (bf16 training of the decoder; the inference entry points keep their signatures).
+ * lvl_gated_add_layernorm_train: lvl_gated_add_layernorm (the same kernel: s and h equal its results to the bit) that also
+ *   returns the row statistics mean, rstd [rows] f32 of the stored sum.
+ * lvl_gated_add_layernorm_bwd: from dh [rows, D], the kept sum s, the statistics and an optional dadd [rows, D] (the
+ *   gradient that reaches the sum from the residual stream): ds [rows, D] = d res (lvl_layernorm_bwd on s, dadd added),
+ *   dgamma, dbeta [D] f32 and -- when y and gate are given -- dy [rows, D] = (*gate) * ds and ONE f32
+ *   *dgate = sum ds * y (per-workgroup partials added in slot order: no atomics, bit-reproducible); the caller turns it into
+ *   d alpha = dgate * (1 - tanh^2 alpha). Without a gate the gradient of y is ds itself and dy / dgate are not written.
+ *   ws: lvl_workspace_floats("gated_add_layernorm_bwd", rows, D). rows > 0.
+ * lvl_act_fwd: a = act(u), out of place (u is kept for the backward); lvl_act_bwd: du = da * act'(u) with the forward's
+ *   tanh expression for gelu_new and 2 relu(u) for relu^2 (exact zeros where u <= 0). n % 8 == 0.
+ * lvl_cross_attn_rows_bwd: from q, kv and dout [rows, H*64] (softmax recomputed): dq [rows, H*64] and
+ *   dkv [rows/qrep, Tk, 2*H*64], the latter accumulated in f32 over the qrep rows of a context inside one workgroup and
+ *   rounded once. Every element of dq and dkv is written. bf16 and 1 <= Tk <= 256 only, else LVL_ENOSYS; any qrep >= 1.
+ *   No workspace, no atomics, bit-reproducible. */
+int lvl_gated_add_layernorm_train(const void* res, const void* y, const float* gate, const float* gamma,
+                                  const float* beta, float eps, void* sum_out, void* h_out, float* mean, float* rstd,
+                                  int rows, int D, int dtype, void* stream);
+int lvl_gated_add_layernorm_bwd(const void* dh, const void* s, const void* y, const float* gate, const float* gamma,
+                                const float* mean, const float* rstd, const void* dadd, void* ds, void* dy, float* dgamma,
+                                float* dbeta, float* dgate, float* ws, int rows, int D, int dtype, void* stream);
+int lvl_act_fwd(const void* u, void* a, int64_t n, int act, int dtype, void* stream);
+int lvl_act_bwd(const void* u, const void* da, void* du, int64_t n, int act, int dtype, void* stream);
+int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows, int qrep,
+                            int Tk, int H, int dtype, void* stream);
 
 /* lvl_sample_next_token: everything VCLM_HF.generate does with one step's logits (narrator.py:122-137 and the warpers
  * of :368-389 = transformers' Temperature / TopK / TopP logits warpers with min_tokens_to_keep = 1), one workgroup per

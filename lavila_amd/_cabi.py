@@ -64,6 +64,8 @@ SIGNATURES = {
     'lvl_cls_attn_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'lvl_cls_attn_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'lvl_mq_cross_attn_fwd': (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'lvl_mq_cross_attn_bwd_ws': (_L, [_I, _I, _I, _I]),
+    'lvl_mq_cross_attn_bwd': (_I, [_P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'lvl_qkv_bias_grad': (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
     'lvl_divided_attn_bwd_bias_ws': (_L, [_I, _I, _I, _I, _I, _I]),
     'lvl_divided_attn_bwd_bias': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -82,6 +84,11 @@ SIGNATURES = {
     'lvl_gpt2_embed': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_gated_add_layernorm': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P]),
     'lvl_act_inplace': (_I, [_P, _L, _I, _I, _P]),
+    'lvl_gated_add_layernorm_train': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'lvl_gated_add_layernorm_bwd': (_I, [_P] * 14 + [_I, _I, _I, _P]),
+    'lvl_act_fwd': (_I, [_P, _P, _L, _I, _I, _P]),
+    'lvl_act_bwd': (_I, [_P, _P, _P, _L, _I, _I, _P]),
+    'lvl_cross_attn_rows_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'lvl_decode_self_attn': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'lvl_cross_attn_rows_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }

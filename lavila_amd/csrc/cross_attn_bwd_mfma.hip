@@ -1,0 +1,215 @@
+// Backward of the decoder cross-attention (lvl_cross_attn_rows_bwd), bf16, gfx950: the structure of the forward
+// (cross_attn_mfma.hip). One workgroup per (context, head) stages the head's keys and values (<= 256 x 64 each) ONCE into
+// the swizzled LDS images of attn_mfma_common.h and walks the context's `qrep` query rows in rounds of 64 (16 per wave).
+//
+// Phase A of a round, per wave on its 16 query rows (the forward's operand layout: scores transposed, a lane owns one query):
+//   S^T  = K . Q^T, exact single-pass softmax over the 16 key tiles held in registers -> P
+//   dP^T = V . dO^T;  delta = rowsum(P o dP);  dS = P o (dP - delta)
+//   dQ   = 0.125 dS . K       (dS packed to bf16 in registers, K through the LDS transpose read)
+//   P^T and dS^T (bf16) go to two [256 keys][64 queries] LDS images, Q and dO of the 16 rows to two [64][64] images.
+// Phase B, per wave on the 64 keys it OWNS (key tiles 4 wave .. 4 wave + 3), over the round's 64 query rows:
+//   dV += P^T . dO,  dK += dS^T . Q      (two full 32-deep contractions each; operands from the images above)
+// Every key row is accumulated by one wave, in f32 registers, rounds in order: there is nothing to combine across waves or
+// workgroups, no atomics, and two runs are bit-identical. dK (x 0.125) and dV are rounded once to bf16 at the end.
+// Tails: key rows >= Tk are zero in the images and masked in the softmax; query rows >= qrep are never read (zero operands,
+// so they add exact zeros in phase B) and never written.
+#include "attn_mfma_common.h"
+
+using namespace attn_mfma;
+
+namespace {
+
+constexpr int XW = 4;          // waves per workgroup
+constexpr int NKT = 16;        // key tiles of 16: up to 256 keys
+constexpr int QR = 16 * XW;    // query rows per round
+
+__global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint16_t* __restrict__ q,
+                                                                      const uint16_t* __restrict__ kv,
+                                                                      const uint16_t* __restrict__ dout,
+                                                                      uint16_t* __restrict__ dq,
+                                                                      uint16_t* __restrict__ dkv, int Tk, int H,
+                                                                      int qrep) {
+  extern __shared__ __align__(16) uint16_t xb_smem[];
+  uint16_t* Ks = xb_smem;
+  uint16_t* Vs = Ks + NKT * 16 * RS;
+  uint16_t* Pi = Vs + NKT * 16 * RS;        // P^T  [key][query of the round]
+  uint16_t* Di = Pi + NKT * 16 * RS;        // dS^T [key][query of the round]
+  uint16_t* Qi = Di + NKT * 16 * RS;        // Q  [query of the round][channel]
+  uint16_t* Oi = Qi + QR * RS;              // dO [query of the round][channel]
+  uint16_t* Ot = Oi + QR * RS;              // per-wave output transposition tiles
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int h = blockIdx.x % H, ctx = blockIdx.x / H;
+  const int D = H * 64;
+  const uint16_t* kb = kv + (size_t)ctx * Tk * 2 * D + h * 64;
+  stage_rows2<PrecBf16, 64 * XW, NKT / 2>(Ks, kb, (size_t)2 * D, nullptr, Vs, kb + D, (size_t)2 * D, nullptr, NKT * 16, Tk, tid, 0);
+  __syncthreads();
+  constexpr float kExp2 = 0.125f * 1.4426950408889634f;
+  const FragOff fo = frag_offsets(lane);
+  uint16_t* ot = Ot + wave * 16 * OS;
+  f32x4 dV[4][4], dK[4][4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      dV[kk][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      dK[kk][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  const int nrounds = (qrep + QR - 1) / QR;
+  const int qcol = wave * 16 + c;             // this lane's query as a column of the P^T / dS^T images
+#pragma unroll 1
+  for (int rd = 0; rd < nrounds; ++rd) {
+    // ---- phase A -------------------------------------------------------------------------------------------------
+    const int q0 = rd * QR + wave * 16;
+    const int qrow = q0 + c;
+    uint4 qf0 = make_uint4(0, 0, 0, 0), qf1 = qf0, df0 = qf0, df1 = qf0;
+    if (qrow < qrep) {
+      const size_t off = ((size_t)ctx * qrep + qrow) * D + h * 64 + g * 8;
+      qf0 = *reinterpret_cast<const uint4*>(q + off);
+      qf1 = *reinterpret_cast<const uint4*>(q + off + 32);
+      df0 = *reinterpret_cast<const uint4*>(dout + off);
+      df1 = *reinterpret_cast<const uint4*>(dout + off + 32);
+    }
+    *reinterpret_cast<uint4*>(Qi + img_off(qcol, g)) = qf0;
+    *reinterpret_cast<uint4*>(Qi + img_off(qcol, 4 + g)) = qf1;
+    *reinterpret_cast<uint4*>(Oi + img_off(qcol, g)) = df0;
+    *reinterpret_cast<uint4*>(Oi + img_off(qcol, 4 + g)) = df1;
+    f32x4 acc[NKT], dp[NKT];
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) acc[k] = mfma(tile_frag(Ks, k, fo.a[0]), qf0, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) acc[k] = mfma(tile_frag(Ks, k, fo.a[1]), qf1, acc[k]);
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) dp[k] = mfma(tile_frag(Vs, k, fo.a[0]), df0, f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) dp[k] = mfma(tile_frag(Vs, k, fo.a[1]), df1, dp[k]);
+    // acc[k][r] = raw S[query c][key k*16 + g*4 + r], dp[k][r] = dP of the same element
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = k * 16 + g * 4 + r;
+        acc[k][r] = key < Tk ? acc[k][r] : -INFINITY;
+        m = fmaxf(m, acc[k][r]);
+      }
+    }
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    const float mk = m * kExp2;                    // key 0 always exists: m is finite
+    float l = 0.f;
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __builtin_amdgcn_exp2f(fmaf(acc[k][r], kExp2, -mk));
+        acc[k][r] = p;
+        l += p;
+      }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float linv = 1.f / l;
+    float delta = 0.f;
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[k][r] *= linv;
+        delta = fmaf(acc[k][r], dp[k][r], delta);
+      }
+    }
+    delta += __shfl_xor(delta, 16, 64);
+    delta += __shfl_xor(delta, 32, 64);
+#pragma unroll
+    for (int k = 0; k < NKT; ++k) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        dp[k][r] = acc[k][r] * (dp[k][r] - delta);            // dS; masked keys: P = 0
+        const int key = k * 16 + g * 4 + r;
+        const int off = key * RS + ((((qcol >> 3) ^ (key & 7)) << 3) | (qcol & 7));
+        Pi[off] = f32_to_bf16(acc[k][r]);
+        Di[off] = f32_to_bf16(dp[k][r]);
+      }
+    }
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NKT / 2; ++j) {
+      uint4 pa;
+      pa.x = pack_bf16x2(dp[2 * j][0], dp[2 * j][1]);
+      pa.y = pack_bf16x2(dp[2 * j][2], dp[2 * j][3]);
+      pa.z = pack_bf16x2(dp[2 * j + 1][0], dp[2 * j + 1][1]);
+      pa.w = pack_bf16x2(dp[2 * j + 1][2], dp[2 * j + 1][3]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const uint2 lo = tile_frag_tr(Ks, 2 * j, fo.tr[dt]);
+        const uint2 hi = tile_frag_tr(Ks, 2 * j + 1, fo.tr[dt]);
+        o[dt] = mfma(pa, make_uint4(lo.x, lo.y, hi.x, hi.y), o[dt]);
+      }
+    }
+    // o[dt][r] = dQ[query g*4+r][channel dt*16 + c] / 0.125
+    store_tile_rows<PrecBf16>(
+        ot, o, 0.125f, lane, [&](int row) { return dq + ((size_t)ctx * qrep + q0 + row) * D + h * 64; },
+        [&](int row) { return q0 + row < qrep; });
+    __syncthreads();
+    // ---- phase B: the wave's own 64 keys against the round's 64 query rows -------------------------------------------
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int kt = wave * 4 + kk;
+      if (kt * 16 < Tk) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const uint4 aP = tile_frag(Pi, kt, fo.a[ks]);       // key row c of the tile, queries ks*32 + g*8 .. +7
+          const uint4 aD = tile_frag(Di, kt, fo.a[ks]);
+          const int r0 = ks * 32 + g * 8;
+#pragma unroll
+          for (int dt = 0; dt < 4; ++dt) {
+            const uint2 olo = img_frag_tr(Oi, r0, dt * 16, lane), ohi = img_frag_tr(Oi, r0 + 4, dt * 16, lane);
+            dV[kk][dt] = mfma(aP, make_uint4(olo.x, olo.y, ohi.x, ohi.y), dV[kk][dt]);
+            const uint2 qlo = img_frag_tr(Qi, r0, dt * 16, lane), qhi = img_frag_tr(Qi, r0 + 4, dt * 16, lane);
+            dK[kk][dt] = mfma(aD, make_uint4(qlo.x, qlo.y, qhi.x, qhi.y), dK[kk][dt]);
+          }
+        }
+      }
+    }
+    __syncthreads();                               // the next round overwrites the images
+  }
+  // dK[kk][dt][r] = dK[key (wave*4+kk)*16 + g*4 + r][channel dt*16 + c] / 0.125, dV alike
+  uint16_t* ob = dkv + (size_t)ctx * Tk * 2 * D + h * 64;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int k0 = (wave * 4 + kk) * 16;
+    if (k0 < Tk) {
+      store_tile_rows<PrecBf16>(
+          ot, dK[kk], 0.125f, lane, [&](int row) { return ob + (size_t)(k0 + row) * 2 * D; },
+          [&](int row) { return k0 + row < Tk; });
+      store_tile_rows<PrecBf16>(
+          ot, dV[kk], 1.f, lane, [&](int row) { return ob + (size_t)(k0 + row) * 2 * D + D; },
+          [&](int row) { return k0 + row < Tk; });
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows,
+                                       int qrep, int Tk, int H, int dtype, void* stream) {
+  LVL_REQUIRE(rows == 0 || (q && kv && dout && dq && dkv), "cross_attn_rows_bwd: null pointer");
+  LVL_REQUIRE(rows >= 0 && qrep > 0 && rows % qrep == 0 && Tk > 0 && H > 0,
+              "cross_attn_rows_bwd: bad shape rows=%d qrep=%d Tk=%d H=%d", rows, qrep, Tk, H);
+  LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(kv) && lvl_aligned16(dout) && lvl_aligned16(dq) && lvl_aligned16(dkv),
+              "cross_attn_rows_bwd: pointers must be 16-byte aligned");
+  if (dtype != LVL_BF16 || Tk > NKT * 16)
+    return lvl_fail(LVL_ENOSYS, "cross_attn_rows_bwd: built for bf16 and 1 <= Tk <= %d keys per context (got dtype %d, Tk=%d)",
+                    NKT * 16, dtype, Tk);
+  if (rows == 0) return LVL_OK;
+  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel>()) return rc;
+  hipLaunchKernelGGL(cross_attn_bwd_mfma_kernel, dim3((unsigned)((rows / qrep) * H)), dim3(64 * XW), lds,
+                     (hipStream_t)stream, (const uint16_t*)q, (const uint16_t*)kv, (const uint16_t*)dout, (uint16_t*)dq,
+                     (uint16_t*)dkv, Tk, H, qrep);
+  LVL_CHECK_LAUNCH("cross_attn_rows_bwd");
+  return LVL_OK;
+}

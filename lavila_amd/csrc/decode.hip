@@ -50,7 +50,9 @@ __global__ __launch_bounds__(LN_THREADS) void gated_add_ln_kernel(const T* res, 
                                                                   const float* __restrict__ gate,
                                                                   const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, float eps,
-                                                                  T* sum_out, T* __restrict__ h_out, int D) {
+                                                                  T* sum_out, T* __restrict__ h_out,
+                                                                  float* __restrict__ mean_out,
+                                                                  float* __restrict__ rstd_out, int D) {
   __shared__ float red[2][LN_THREADS / LVL_WAVE];
   const int r = blockIdx.x, tid = threadIdx.x;
   const float g = gate ? *gate : 1.f;
@@ -93,6 +95,10 @@ __global__ __launch_bounds__(LN_THREADS) void gated_add_ln_kernel(const T* res, 
   if ((tid & 63) == 0) red[1][tid >> 6] = q;
   __syncthreads();
   const float rstd = rsqrtf((red[1][0] + red[1][1]) / (float)D + eps);
+  if (mean_out != nullptr && tid == 0) {           // the training forward keeps the row statistics for its backward
+    mean_out[r] = mean;
+    rstd_out[r] = rstd;
+  }
 #pragma unroll
   for (int i = 0; i < LN_CHUNKS; ++i) {
     const int c = (i * LN_THREADS + tid) * 8;
@@ -111,24 +117,92 @@ __global__ __launch_bounds__(LN_THREADS) void gated_add_ln_kernel(const T* res, 
 // ------------------------------------------------------------------------------------------------------------
 // activations of the two MLPs
 // ------------------------------------------------------------------------------------------------------------
+// gelu_new(x) = 0.5 x (1 + tanh(z)), z = sqrt(2/pi) (x + 0.044715 x^3); one tanh expression for the forward and its derivative
+__device__ __forceinline__ float gelu_new_tanh(float x) {
+  const float z = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+  return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * z) + 1.f);      // tanh(z), see gemm_skinny.hip
+}
+
+// a = act(u); a may be u (lvl_act_inplace)
 template <typename T, int ACT>
-__global__ __launch_bounds__(256) void act_inplace_kernel(T* __restrict__ u, int64_t n8) {
+__global__ __launch_bounds__(256) void act_kernel(const T* u, T* a, int64_t n8) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     float x[8];
     Elem<T>::load8(u + i * 8, x);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (ACT == LVL_ACT_GELU_NEW) {
-        const float z = 0.7978845608028654f * (x[k] + 0.044715f * x[k] * x[k] * x[k]);
-        const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * z) + 1.f);      // tanh(z), see gemm_skinny.hip
+        const float t = gelu_new_tanh(x[k]);
         x[k] = 0.5f * x[k] * (1.f + t);
       } else {
         const float t = fmaxf(x[k], 0.f);
         x[k] = t * t;
       }
     }
-    Elem<T>::store8(u + i * 8, x);
+    Elem<T>::store8(a + i * 8, x);
   }
+}
+
+// du = da * act'(u): gelu_new' = 0.5 (1 + t) + 0.5 u (1 - t^2) sqrt(2/pi) (1 + 3 * 0.044715 u^2), (relu^2)' = 2 relu(u)
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void act_bwd_kernel(const T* __restrict__ u, const T* __restrict__ da,
+                                                      T* __restrict__ du, int64_t n8) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    float x[8], d[8];
+    Elem<T>::load8(u + i * 8, x);
+    Elem<T>::load8(da + i * 8, d);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (ACT == LVL_ACT_GELU_NEW) {
+        const float t = gelu_new_tanh(x[k]);
+        const float dz = 0.7978845608028654f * (1.f + 3.f * 0.044715f * x[k] * x[k]);
+        d[k] *= 0.5f * (1.f + t) + 0.5f * x[k] * (1.f - t * t) * dz;
+      } else {
+        d[k] = x[k] > 0.f ? d[k] * (2.f * x[k]) : 0.f;
+      }
+    }
+    Elem<T>::store8(du + i * 8, d);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// backward of the gated add, behind lvl_layernorm_bwd (which leaves ds, the gradient of the sum): dy = gate * ds and one
+// partial of dgate = sum ds * y per workgroup, then gate_grad_final_kernel adds the partials in slot order (no atomics)
+// ------------------------------------------------------------------------------------------------------------
+constexpr int GATE_PARTS = 256;
+
+template <typename T>
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const T* __restrict__ ds, const T* __restrict__ y,
+                                                       const float* __restrict__ gate, T* __restrict__ dy,
+                                                       float* __restrict__ part, int64_t n8) {
+  __shared__ float red[4];
+  const float g = *gate;
+  float acc = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    float a[8], b[8];
+    Elem<T>::load8(ds + i * 8, a);
+    Elem<T>::load8(y + i * 8, b);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      acc = fmaf(a[k], b[k], acc);
+      a[k] *= g;
+    }
+    Elem<T>::store8(dy + i * 8, a);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(GATE_PARTS) void gate_grad_final_kernel(const float* __restrict__ part, int nparts,
+                                                                     float* __restrict__ dgate) {
+  __shared__ float red[GATE_PARTS / 64];
+  float v = (int)threadIdx.x < nparts ? part[threadIdx.x] : 0.f;
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) *dgate = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -216,9 +290,9 @@ extern "C" int lvl_gpt2_embed(const int64_t* ids, const void* wte, const void* w
   return LVL_OK;
 }
 
-extern "C" int lvl_gated_add_layernorm(const void* res, const void* y, const float* gate, const float* gamma,
-                                       const float* beta, float eps, void* sum_out, void* h_out, int rows, int D,
-                                       int dtype, void* stream) {
+static int gated_add_layernorm_launch(const void* res, const void* y, const float* gate, const float* gamma,
+                                      const float* beta, float eps, void* sum_out, void* h_out, float* mean, float* rstd,
+                                      int rows, int D, int dtype, void* stream) {
   LVL_REQUIRE(rows == 0 || (res && gamma && beta && h_out), "gated_add_layernorm: null pointer");
   LVL_REQUIRE(rows >= 0 && D > 0 && D % 8 == 0 && D <= LN_THREADS * 8 * LN_CHUNKS,
               "gated_add_layernorm: width %d must be a multiple of 8, at most %d", D, LN_THREADS * 8 * LN_CHUNKS);
@@ -227,26 +301,91 @@ extern "C" int lvl_gated_add_layernorm(const void* res, const void* y, const flo
   if (rows == 0) return LVL_OK;
   LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gated_add_ln_kernel<T>), dim3((unsigned)rows), dim3(LN_THREADS), 0,
                                                (hipStream_t)stream, (const T*)res, (const T*)y, gate, gamma, beta, eps,
-                                               (T*)sum_out, (T*)h_out, D));
+                                               (T*)sum_out, (T*)h_out, mean, rstd, D));
   LVL_CHECK_LAUNCH("gated_add_layernorm");
   return LVL_OK;
 }
 
-extern "C" int lvl_act_inplace(void* u, int64_t n, int act, int dtype, void* stream) {
-  LVL_REQUIRE(n == 0 || u, "act_inplace: null pointer");
-  LVL_REQUIRE(n >= 0 && n % 8 == 0 && lvl_aligned16(u), "act_inplace: n %% 8 == 0 and a 16-byte aligned pointer are required");
-  LVL_REQUIRE(act == LVL_ACT_GELU_NEW || act == LVL_ACT_SQRELU, "act_inplace: unknown activation %d", act);
+extern "C" int lvl_gated_add_layernorm(const void* res, const void* y, const float* gate, const float* gamma,
+                                       const float* beta, float eps, void* sum_out, void* h_out, int rows, int D,
+                                       int dtype, void* stream) {
+  return gated_add_layernorm_launch(res, y, gate, gamma, beta, eps, sum_out, h_out, nullptr, nullptr, rows, D, dtype, stream);
+}
+
+extern "C" int lvl_gated_add_layernorm_train(const void* res, const void* y, const float* gate, const float* gamma,
+                                             const float* beta, float eps, void* sum_out, void* h_out, float* mean,
+                                             float* rstd, int rows, int D, int dtype, void* stream) {
+  LVL_REQUIRE(rows == 0 || (mean && rstd), "gated_add_layernorm_train: null statistics pointer");
+  return gated_add_layernorm_launch(res, y, gate, gamma, beta, eps, sum_out, h_out, mean, rstd, rows, D, dtype, stream);
+}
+
+int lvl_gate_bwd_parts() { return GATE_PARTS; }
+
+extern "C" int lvl_gated_add_layernorm_bwd(const void* dh, const void* s, const void* y, const float* gate,
+                                           const float* gamma, const float* mean, const float* rstd, const void* dadd,
+                                           void* ds, void* dy, float* dgamma, float* dbeta, float* dgate, float* ws,
+                                           int rows, int D, int dtype, void* stream) {
+  LVL_REQUIRE(rows > 0 && dgamma && dbeta && ws, "gated_add_layernorm_bwd: rows > 0 and non-null dgamma / dbeta / ws");
+  const bool gated = y != nullptr && gate != nullptr;
+  LVL_REQUIRE(!gated || (dy && dgate), "gated_add_layernorm_bwd: a gated add needs dy and dgate");
+  LVL_REQUIRE(lvl_aligned16(y) && lvl_aligned16(dy), "gated_add_layernorm_bwd: pointers must be 16-byte aligned");
+  if (int rc = lvl_layernorm_bwd(dh, s, nullptr, nullptr, gamma, mean, rstd, dadd, ds, nullptr, dgamma, dbeta, nullptr, ws,
+                                 rows, D, dtype, stream))
+    return rc;
+  if (!gated) return LVL_OK;
+  float* part = ws + lvl_workspace_floats("layernorm_bwd", rows, D);
+  const int64_t n8 = (int64_t)rows * D / 8;
+  const int blocks = (int)((n8 + 255) / 256 < GATE_PARTS ? (n8 + 255) / 256 : GATE_PARTS);
+  LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((gate_bwd_kernel<T>), dim3((unsigned)blocks), dim3(256), 0,
+                                               (hipStream_t)stream, (const T*)ds, (const T*)y, gate, (T*)dy, part, n8));
+  hipLaunchKernelGGL(gate_grad_final_kernel, dim3(1), dim3(GATE_PARTS), 0, (hipStream_t)stream, part, blocks, dgate);
+  LVL_CHECK_LAUNCH("gated_add_layernorm_bwd");
+  return LVL_OK;
+}
+
+static int act_launch(const void* u, void* a, int64_t n, int act, int dtype, void* stream) {
+  LVL_REQUIRE(n == 0 || (u && a), "act: null pointer");
+  LVL_REQUIRE(n >= 0 && n % 8 == 0 && lvl_aligned16(u) && lvl_aligned16(a),
+              "act: n %% 8 == 0 and 16-byte aligned pointers are required");
+  LVL_REQUIRE(act == LVL_ACT_GELU_NEW || act == LVL_ACT_SQRELU, "act: unknown activation %d", act);
   if (n == 0) return LVL_OK;
   const int64_t n8 = n / 8;
   const unsigned grid = (unsigned)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 : 4096);
   if (act == LVL_ACT_GELU_NEW) {
-    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_inplace_kernel<T, LVL_ACT_GELU_NEW>), dim3(grid), dim3(256), 0,
-                                                 (hipStream_t)stream, (T*)u, n8));
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_kernel<T, LVL_ACT_GELU_NEW>), dim3(grid), dim3(256), 0,
+                                                 (hipStream_t)stream, (const T*)u, (T*)a, n8));
   } else {
-    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_inplace_kernel<T, LVL_ACT_SQRELU>), dim3(grid), dim3(256), 0,
-                                                 (hipStream_t)stream, (T*)u, n8));
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_kernel<T, LVL_ACT_SQRELU>), dim3(grid), dim3(256), 0,
+                                                 (hipStream_t)stream, (const T*)u, (T*)a, n8));
   }
-  LVL_CHECK_LAUNCH("act_inplace");
+  LVL_CHECK_LAUNCH("act");
+  return LVL_OK;
+}
+
+extern "C" int lvl_act_inplace(void* u, int64_t n, int act, int dtype, void* stream) {
+  return act_launch(u, u, n, act, dtype, stream);
+}
+
+extern "C" int lvl_act_fwd(const void* u, void* a, int64_t n, int act, int dtype, void* stream) {
+  return act_launch(u, a, n, act, dtype, stream);
+}
+
+extern "C" int lvl_act_bwd(const void* u, const void* da, void* du, int64_t n, int act, int dtype, void* stream) {
+  LVL_REQUIRE(n == 0 || (u && da && du), "act_bwd: null pointer");
+  LVL_REQUIRE(n >= 0 && n % 8 == 0 && lvl_aligned16(u) && lvl_aligned16(da) && lvl_aligned16(du),
+              "act_bwd: n %% 8 == 0 and 16-byte aligned pointers are required");
+  LVL_REQUIRE(act == LVL_ACT_GELU_NEW || act == LVL_ACT_SQRELU, "act_bwd: unknown activation %d", act);
+  if (n == 0) return LVL_OK;
+  const int64_t n8 = n / 8;
+  const unsigned grid = (unsigned)((n8 + 255) / 256 < 4096 ? (n8 + 255) / 256 : 4096);
+  if (act == LVL_ACT_GELU_NEW) {
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_bwd_kernel<T, LVL_ACT_GELU_NEW>), dim3(grid), dim3(256), 0,
+                                                 (hipStream_t)stream, (const T*)u, (const T*)da, (T*)du, n8));
+  } else {
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((act_bwd_kernel<T, LVL_ACT_SQRELU>), dim3(grid), dim3(256), 0,
+                                                 (hipStream_t)stream, (const T*)u, (const T*)da, (T*)du, n8));
+  }
+  LVL_CHECK_LAUNCH("act_bwd");
   return LVL_OK;
 }
 

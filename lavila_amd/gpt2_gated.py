@@ -1,5 +1,5 @@
-"""The narrator's text decoder -- GPT-2 with gated cross-attention (lavila/models/gpt2_gated.py), MI355X-native,
-INFERENCE ONLY (BASELINE configs[4]: captioning).
+"""The narrator's text decoder -- GPT-2 with gated cross-attention (lavila/models/gpt2_gated.py), MI355X-native: an
+inference plan and a bf16 training plan (BASELINE configs[4]: captioning).
 
 Module and parameter names are the reference's (`transformer.{wte,wpe,ln_f}`, `transformer.h.{i}.{ln_1, attn.{c_attn,
 c_proj}, ln_2, mlp.{c_fc,c_proj}, crossattention.{c_attn,q_attn,c_proj}, ln_cross_attn, mlp_crossattention.{c_fc,c_proj},
@@ -22,8 +22,18 @@ strict=True. The modules only HOLD parameters; the computation is laid out for t
     numbers, quadratically more work.
 
 What the reference's vendored HF class offers beyond this path (attention / head masks, token types, past_key_values as
-arguments, pruning, model parallelism, the other heads) raises NotImplementedError. Training the decoder is not built:
-calling it with gradients enabled on parameters that require them raises.
+arguments, pruning, model parallelism, the other heads) raises NotImplementedError.
+
+Training (`GPT2LMHeadModel.forward` with gradients enabled and a trainable decoder parameter, or image tokens that require a
+gradient: the frozen-LM recipe with a trainable pooler): the same order of operations as `_Pack.run`, as small
+torch.autograd.Functions chained by autograd (`_train_forward`) -- Conv1D on lvl_linear_tn / lvl_linear_wgrad (no weight
+gradient for a frozen weight), gated add + LayerNorm (lvl_gated_add_layernorm_train / _bwd), the activations
+(lvl_act_fwd / lvl_act_bwd), cross-attention (lvl_cross_attn_rows_fwd / _bwd, at most 256 image tokens), ops.causal_attention,
+the embedding (lvl_text_embed_fwd / _bwd) and the tied lm_head, whose weight gradient adds into wte's. bf16 only (bf16
+parameters, or float32 masters under bf16 autocast): float32 with gradients raises NotImplementedError, and so does a
+non-zero resid / embd / attn_pdrop in training mode (there is no dropout kernel; transformers' GPT2Config defaults the three
+to 0.1, so the reference trains with dropout and this decoder does not). `gradient_checkpointing_enable()` is a no-op: the
+plan keeps its activations. The inference plan, DecodeSession and everything under torch.no_grad() are untouched by it.
 """
 import copy
 import os
@@ -57,7 +67,10 @@ def gpt2_config(name='gpt2', **overrides):
         vocab_size=50257, n_positions=1024, n_embd=width, n_layer=layers, n_head=heads, n_inner=None,
         activation_function='gelu_new', layer_norm_epsilon=1e-5, initializer_range=0.02, scale_attn_weights=True,
         scale_attn_by_inverse_layer_idx=False, reorder_and_upcast_attn=False, tie_word_embeddings=True,
-        add_cross_attention=False, bos_token_id=50256, eos_token_id=50256, use_cache=False)
+        add_cross_attention=False, bos_token_id=50256, eos_token_id=50256, use_cache=False,
+        # transformers' GPT2Config defaults these three to 0.1, so the reference's decoder trains WITH dropout; this decoder
+        # has no dropout kernel and refuses to train with a non-zero value (GPT2LMHeadModel._check_dropout)
+        resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0)
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg
@@ -374,6 +387,233 @@ class _Pack:
         return self.add_ln(x, *pend)                     # ln_f feeds lm_head (the 256-column-panel kernel): materialised
 
 
+# --------------------------------------------------------------------------------------------------
+# training plan (bf16): the order of operations of _Pack.run as autograd Functions over the own kernels
+# --------------------------------------------------------------------------------------------------
+class _Conv1DFn(torch.autograd.Function):
+    """y = x W + b for a Conv1D weight W [in, out]: forward and input gradient on lvl_linear_tn, weight gradient on
+    lvl_linear_wgrad (ops._wgrad), like ops._LinearFn. ops.weight_copies(W) yields both bf16 operands at once: the plain
+    cast [in, out] is what the input-gradient GEMM reads, its transpose [out, in] what the forward reads; the pair follows
+    the weight-copy discipline of ops.py (re-cast after every optimizer step and at the top of every training forward).
+    A frozen weight gets no weight-gradient GEMM. Widths the kernels do not tile go to the library GEMM, logged."""
+
+    @staticmethod
+    def forward(ctx, x2, weight, bias):
+        n_in, n_out = weight.shape
+        rows = x2.shape[0]
+        w_in_out, w_out_in = ops.weight_copies(weight)
+        ctx.own = ops._tn_ok(rows, n_out, n_in) and (not ctx.needs_input_grad[0] or ops._tn_ok(rows, n_in, n_out))
+        ctx.meta = (weight.dtype, bias.dtype)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        ctx.save_for_backward(x2, w_in_out)
+        if ctx.own:
+            return ops.linear_tn_raw(x2, w_out_in, ops._f32(bias), C.EPI_BIAS)
+        ops.warn_once(('conv1d', n_out, n_in), f'decoder Conv1D [{n_in}->{n_out}] on {rows} rows runs on the '
+                      'library GEMM (lvl_linear_tn needs out % 256 == 0 and in % 64 == 0)')
+        with torch.autocast('cuda', enabled=False):
+            return F.linear(x2, w_out_in, bias.detach().to(torch.bfloat16))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w_in_out = ctx.saved_tensors
+        wdt, bdt = ctx.meta
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dx = dw = db = None
+        with torch.autocast('cuda', enabled=False):
+            if ctx.needs_input_grad[0]:
+                dx = ops.linear_tn_raw(dy, w_in_out, None, C.EPI_BIAS) if ctx.own else dy @ w_in_out.t()
+            if ctx.needs_input_grad[1]:
+                dw = ops._wgrad(x2, dy, wdt)                  # x^T dy: [in, out], the Conv1D layout
+            if ctx.needs_input_grad[2]:
+                db = dy.sum(0, dtype=torch.float32).to(bdt)
+        return dx, dw, db
+
+
+class _GatedAddLnFn(torch.autograd.Function):
+    """s = res + tanh(alpha) * y, h = LayerNorm(s): (s, h) -- or h alone when there is no y (the first norm of the stack).
+    Forward lvl_gated_add_layernorm_train (the inference kernel, which also returns mean / rstd), backward
+    lvl_gated_add_layernorm_bwd: lvl_layernorm_bwd on the kept sum with the residual stream's gradient as `dadd`, then one
+    pass for dy = gate * ds and the deterministic gate gradient."""
+
+    @staticmethod
+    def forward(ctx, res, y, alpha, gamma, beta, eps):
+        res = res if res.is_contiguous() else res.contiguous()
+        rows, D = res.shape
+        g, b = ops._f32(gamma), ops._f32(beta)
+        gate = None if alpha is None else torch.tanh(alpha.detach().to(torch.float32)).reshape(1)
+        if y is not None:
+            y = y if y.is_contiguous() else y.contiguous()
+        s = torch.empty_like(res) if y is not None else None
+        h = torch.empty_like(res)
+        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+        C.require_device(res, y, g, b)
+        C.check(C.lib().lvl_gated_add_layernorm_train(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(b), float(eps),
+                                                      C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows, D,
+                                                      C.dtype_code(res), C.stream_ptr()), 'lvl_gated_add_layernorm_train')
+        ctx.save_for_backward(res if s is None else s, y if gate is not None else None, gate, g, mean, rstd)
+        ctx.meta = (y is not None, None if alpha is None else alpha.dtype, gamma.dtype, beta.dtype)
+        return h if s is None else (s, h)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        s, y, gate, g, mean, rstd = ctx.saved_tensors
+        has_y, adt, gdt, bdt = ctx.meta
+        dadd, dh = (grads if has_y else (None, grads[0]))
+        rows, D = s.shape
+        if dh is None:
+            dh = torch.zeros_like(s)
+        dh = dh if dh.is_contiguous() else dh.contiguous()
+        if dadd is not None and not dadd.is_contiguous():
+            dadd = dadd.contiguous()
+        ds = torch.empty_like(s)
+        dy = torch.empty_like(s) if gate is not None else None
+        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
+        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+        dgate = torch.empty(1, dtype=torch.float32, device=s.device) if gate is not None else None
+        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
+        C.check(C.lib().lvl_gated_add_layernorm_bwd(C.ptr(dh), C.ptr(s), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(mean),
+                                                    C.ptr(rstd), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma),
+                                                    C.ptr(dbeta), C.ptr(dgate), C.ptr(ws), rows, D, C.dtype_code(s),
+                                                    C.stream_ptr()), 'lvl_gated_add_layernorm_bwd')
+        dalpha = None
+        if gate is not None:
+            dalpha = (dgate * (1.0 - gate * gate)).reshape(()).to(adt)
+        return ds, ((dy if gate is not None else ds) if has_y else None), dalpha, dgamma.to(gdt), dbeta.to(bdt), None
+
+
+class _ActFn(torch.autograd.Function):
+    """a = gelu_new(u) / relu(u)^2 out of place (lvl_act_fwd; u is kept), du = da * act'(u) (lvl_act_bwd)."""
+
+    @staticmethod
+    def forward(ctx, u, which):
+        u = u if u.is_contiguous() else u.contiguous()
+        a = torch.empty_like(u)
+        C.check(C.lib().lvl_act_fwd(C.ptr(u), C.ptr(a), u.numel(), which, C.dtype_code(u), C.stream_ptr()), 'lvl_act_fwd')
+        ctx.save_for_backward(u)
+        ctx.which = which
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        u, = ctx.saved_tensors
+        da = da if da.is_contiguous() else da.contiguous()
+        du = torch.empty_like(u)
+        C.check(C.lib().lvl_act_bwd(C.ptr(u), C.ptr(da), C.ptr(du), u.numel(), ctx.which, C.dtype_code(u), C.stream_ptr()),
+                'lvl_act_bwd')
+        return du, None
+
+
+CROSS_ATTN_BWD_MAX_KEYS = 256
+
+
+class _CrossAttnRowsFn(torch.autograd.Function):
+    """lvl_cross_attn_rows_fwd / lvl_cross_attn_rows_bwd: q [rows, D] over kv [rows / qrep, Tk, 2 D]."""
+
+    @staticmethod
+    def forward(ctx, q, kv, qrep, heads):
+        if q.dtype != torch.bfloat16 or kv.shape[1] > CROSS_ATTN_BWD_MAX_KEYS:
+            raise C.HipExtensionError(f'decoder cross-attention backward is built for bf16 and at most '
+                                      f'{CROSS_ATTN_BWD_MAX_KEYS} image tokens per clip (got {q.dtype}, {kv.shape[1]})')
+        q = q if q.is_contiguous() else q.contiguous()
+        kv = kv if kv.is_contiguous() else kv.contiguous()
+        C.require_device(q, kv)
+        out = torch.empty_like(q)
+        C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), q.shape[0], qrep, kv.shape[1], heads,
+                                                C.dtype_code(q), C.stream_ptr()), 'lvl_cross_attn_rows_fwd')
+        ctx.save_for_backward(q, kv)
+        ctx.cfg = (qrep, heads)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv = ctx.saved_tensors
+        qrep, heads = ctx.cfg
+        dout = dout if dout.is_contiguous() else dout.contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        C.check(C.lib().lvl_cross_attn_rows_bwd(C.ptr(q), C.ptr(kv), C.ptr(dout), C.ptr(dq), C.ptr(dkv), q.shape[0], qrep,
+                                                kv.shape[1], heads, C.dtype_code(q), C.stream_ptr()),
+                'lvl_cross_attn_rows_bwd')
+        return dq, dkv, None, None
+
+
+class _LmHeadFn(torch.autograd.Function):
+    """logits = h W^T for the (tied) lm_head weight W [vocab, D]: the vocabulary is padded with zero rows to the GEMM's
+    256-column tiles (as the inference image is), the padded bf16 image and its transpose are cast per forward from the
+    current parameter (nothing cached, nothing stale) and the padded columns are dropped again. dW [vocab, D] comes back as
+    a gradient of the weight: tied, autograd adds it to the embedding's."""
+
+    @staticmethod
+    def forward(ctx, h2, weight):
+        V, D = weight.shape
+        rows = h2.shape[0]
+        w = _pad_rows(weight.detach().to(torch.bfloat16), 256)
+        Vp = w.shape[0]
+        ctx.own = ops._tn_ok(rows, Vp, D) and ops._tn_ok(rows, D, Vp)
+        h2 = h2 if h2.is_contiguous() else h2.contiguous()
+        ctx.save_for_backward(h2, w)
+        ctx.meta = (V, weight.dtype)
+        if ctx.own:
+            return ops.linear_tn_raw(h2, w, None, C.EPI_BIAS)[:, :V]
+        ops.warn_once(('lm_head', V, D), f'decoder lm_head [{D}->{V}] on {rows} rows runs on the library GEMM')
+        with torch.autocast('cuda', enabled=False):
+            return F.linear(h2, w)[:, :V]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        h2, w = ctx.saved_tensors
+        V, wdt = ctx.meta
+        dl = torch.zeros(h2.shape[0], w.shape[0], dtype=torch.bfloat16, device=h2.device)
+        dl[:, :V] = dlogits
+        dh = dw = None
+        with torch.autocast('cuda', enabled=False):
+            if ctx.needs_input_grad[0]:
+                dh = ops.linear_tn_raw(dl, w.t().contiguous(), None, C.EPI_BIAS) if ctx.own else dl @ w
+            if ctx.needs_input_grad[1]:
+                dw = ops._wgrad(dl, h2, wdt)[:V]
+        return dh, dw
+
+
+def _train_forward(model, ids, enc):
+    """Teacher-forced logits [B, L, vocab] with a backward: _Pack.run's order of operations on bf16 rows."""
+    tr = model.transformer
+    B, L = ids.shape
+    D, heads, eps = tr.embed_dim, tr.h[0].attn.num_heads, float(tr.ln_f.eps)
+    conv = lambda x2, m: _Conv1DFn.apply(x2, m.weight, m.bias)
+    x = ops.text_embed(ids, tr.wte.weight, tr.wpe.weight, torch.bfloat16)
+    if x is None:                                     # tables the gather kernel does not take (bf16 parameters, width > 2048)
+        x = (F.embedding(ids, tr.wte.weight) + tr.wpe.weight[:L]).to(torch.bfloat16)
+    x = x.reshape(B * L, D)
+    with_image = enc is not None and any(blk.has_cross for blk in tr.h)
+    if with_image:
+        enc2 = enc.reshape(-1, enc.shape[-1]).to(torch.bfloat16)
+
+    def first_ln(i):
+        if i == len(tr.h):
+            return tr.ln_f
+        blk = tr.h[i]
+        return blk.ln_cross_attn if (blk.has_cross and with_image) else blk.ln_1
+
+    ln = first_ln(0)
+    h = _GatedAddLnFn.apply(x, None, None, ln.weight, ln.bias, eps)
+    add_ln = lambda x, y, alpha, ln: _GatedAddLnFn.apply(x, y, alpha, ln.weight, ln.bias, eps)
+    for i, blk in enumerate(tr.h):
+        if blk.has_cross and with_image:
+            xa = blk.crossattention
+            q = conv(h, xa.q_attn)
+            kv = conv(enc2, xa.c_attn).reshape(enc.shape[0], enc.shape[1], 2 * D)
+            a = _CrossAttnRowsFn.apply(q, kv, L, heads)
+            x, h = add_ln(x, conv(a, xa.c_proj), getattr(blk, 'alpha_cattn', None), blk.ln_2_crossattention)
+            u = _ActFn.apply(conv(h, blk.mlp_crossattention.c_fc), C.ACT_SQRELU)
+            x, h = add_ln(x, conv(u, blk.mlp_crossattention.c_proj), getattr(blk, 'alpha_dense', None), blk.ln_1)
+        qkv = conv(h, blk.attn.c_attn)
+        a = ops.causal_attention(qkv.reshape(B, L, 3 * D), heads).reshape(B * L, D)
+        x, h = add_ln(x, conv(a, blk.attn.c_proj), None, blk.ln_2)
+        u = _ActFn.apply(conv(h, blk.mlp.c_fc), C.ACT_GELU_NEW)
+        x, h = add_ln(x, conv(u, blk.mlp.c_proj), None, first_ln(i + 1))
+    return _LmHeadFn.apply(h, model.lm_head.weight).reshape(B, L, -1)
+
+
 class DecodeSession:
     """Key/value-cached decoding of `rows = contexts * seqs_per_context` captions, one token per step.
     step(ids [rows]) -> logits [rows, vocab] of the NEXT token (a view of a buffer that the next step overwrites).
@@ -478,7 +718,7 @@ class DecodeSession:
 
 
 class GPT2LMHeadModel(nn.Module):
-    """gpt2_gated.py:1004-1162 (the language-model head on GPT2Model), inference only. `forward` takes the reference's
+    """gpt2_gated.py:1004-1162 (the language-model head on GPT2Model). `forward` takes the reference's
     keyword names; everything but input_ids / encoder_hidden_states / labels must be left at None."""
 
     def __init__(self, config):
@@ -513,7 +753,7 @@ class GPT2LMHeadModel(nn.Module):
             p.requires_grad = ('crossattention' in n or 'cross_attn' in n or 'alpha_cattn' in n or 'alpha_dense' in n)
 
     def gradient_checkpointing_enable(self):
-        pass                                    # inference only: nothing is kept for a backward
+        pass                                    # a no-op: the training plan keeps its activations
 
     def gradient_checkpointing_disable(self):
         pass
@@ -550,8 +790,8 @@ class GPT2LMHeadModel(nn.Module):
         pack = self._packs.get(dtype)
         if pack is None or pack.key != self._param_key():
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-                raise NotImplementedError('lavila_amd.gpt2_gated is inference-only (no backward kernels for the decoder): '
-                                          'call it under torch.no_grad()')
+                raise NotImplementedError('the packed inference image of lavila_amd.gpt2_gated (decoding, float32) has no '
+                                          'backward: call it under torch.no_grad()')
             C.require_device(self.transformer.wte.weight)
             with torch.no_grad(), torch.autocast('cuda', enabled=False):
                 pack = self._packs[dtype] = _Pack(self, dtype)
@@ -569,9 +809,8 @@ class GPT2LMHeadModel(nn.Module):
                                       'not on the narrator path (cached decoding: decode_session())')
         if input_ids is None:
             raise ValueError('You have to specify input_ids')
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError('lavila_amd.gpt2_gated is inference-only (no backward kernels for the decoder): '
-                                      'call it under torch.no_grad()')
+        if self._trains(encoder_hidden_states):
+            return self._forward_train(input_ids, encoder_hidden_states, labels)
         pack = self._pack()
         shape = tuple(input_ids.shape)
         L = shape[-1]
@@ -601,6 +840,46 @@ class GPT2LMHeadModel(nn.Module):
                 loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, pack.vocab).float(), labels[..., 1:].reshape(-1))
         if self.transformer.wte.weight.dtype == torch.float16 and not torch.is_autocast_enabled():
             logits = logits.to(torch.float16)
+        return CausalLMOutput(logits, loss)
+
+    # ---- training ----------------------------------------------------------------------------------------
+    def _trains(self, encoder_hidden_states):
+        """The training plan runs when gradients are enabled and a decoder parameter or the image tokens require one (the
+        latter: freeze_lm_weights() on everything with a trainable pooler in front)."""
+        return torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
+                                            (encoder_hidden_states is not None and encoder_hidden_states.requires_grad))
+
+    def _forward_train(self, input_ids, encoder_hidden_states, labels):
+        if self._compute_dtype() != torch.bfloat16:
+            raise NotImplementedError('lavila_amd.gpt2_gated trains in bf16 (bf16 parameters, or float32 masters under '
+                                      'torch.autocast(\'cuda\', dtype=torch.bfloat16)); there is no float32 backward for the '
+                                      'decoder: call it under torch.no_grad()')
+        drop = [k for k in ('resid_pdrop', 'embd_pdrop', 'attn_pdrop') if _cfg(self.config, k, 0.0)]
+        if drop and self.training:
+            raise NotImplementedError(f'the decoder has no dropout: config.{" / ".join(drop)} must be 0.0 to train it '
+                                      '(transformers\' GPT2Config defaults them to 0.1), or call .eval()')
+        C.require_device(self.transformer.wte.weight)
+        tr = self.transformer
+        vocab, positions, D = tr.wte.weight.shape[0], tr.wpe.weight.shape[0], tr.embed_dim
+        shape = tuple(input_ids.shape)
+        L = shape[-1]
+        if L > positions:
+            raise ValueError(f'sequence of {L} tokens exceeds the decoder\'s {positions} positions')
+        ids = input_ids.reshape(-1, L).contiguous()
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())
+        if lo < 0 or hi >= vocab:
+            raise IndexError(f'input_ids out of range [0, {vocab}): min {lo}, max {hi}')
+        enc = encoder_hidden_states
+        if enc is not None:
+            enc = ops.lowp(enc)
+            if enc.shape[0] != ids.shape[0] or enc.shape[-1] != D:
+                raise ValueError(f'encoder_hidden_states {tuple(enc.shape)} does not match {ids.shape[0]} sequences of '
+                                 f'width {D}')
+        with ops.model_forward(), torch.autocast('cuda', enabled=False):
+            logits = _train_forward(self, ids, enc).reshape(*shape, vocab)
+            loss = None
+            if labels is not None:                              # gpt2_gated.py:1142-1148
+                loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, vocab).float(), labels[..., 1:].reshape(-1))
         return CausalLMOutput(logits, loss)
 
     def decode_session(self, encoder_hidden_states, max_length, seqs_per_context=1, graph=True):

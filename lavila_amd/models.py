@@ -3,7 +3,7 @@
 `CLIP_OPENAI_TIMESFORMER_{BASE,LARGE,LARGE_336PX}` (:316-491) -- same names, kwargs (unknown kwargs are
 swallowed exactly as the reference's **kwargs do), output dict keys and state_dict keys, so that
 main_pretrain.py / eval_zeroshot.py drive it unchanged. Built: the dual-encoder pretraining path
-and, for inference, the narrator on TimeSformer towers (`VCLM_OPENAI_TIMESFORMER_*`, :887-1198; lavila_amd.narrator +
+and the narrator on TimeSformer towers (`VCLM_OPENAI_TIMESFORMER_*`, :887-1198; lavila_amd.narrator +
 lavila_amd.gpt2_gated). The per-frame ViT narrators (`VCLM_OPENAI_VIT*`), DistilBERT and fine-tuning heads are absent.
 """
 import contextlib
@@ -279,12 +279,19 @@ def get_loss(model, args, tokenizer=None):
     if model.startswith('CLIP'):
         return loss.CLIPLoss(use_vissl=args.contrastive_use_vissl, cache_labels=True, rank=args.rank,
                              world_size=args.world_size)
-    raise NotImplementedError(f'{model}: only the CLIP_* dual-encoder path is built (SURVEY.md section 8)')
+    if model.startswith('VCLM'):
+        if tokenizer is None:
+            raise NotImplementedError(f'{model}: the caption criterion needs the tokenizer\'s pad id: call '
+                                      'get_loss(model, args, tokenizer=tokenizer) (models.py:28-29)')
+        return loss.CaptionLoss(tokenizer=tokenizer)
+    raise NotImplementedError(f'{model}: only the CLIP_* and VCLM_* paths are built (SURVEY.md section 8)')
 
 
 def get_metric_names(model):
     if model.startswith('CLIP'):
         return ['loss', 'clip_loss', 'clip_acc']
+    if model.startswith('VCLM'):
+        return ['loss', 'caption_loss', 'caption_acc', 'ppl']
     raise NotImplementedError(f'{model}: only the CLIP_* dual-encoder path is built (SURVEY.md section 8)')
 
 

@@ -1,4 +1,4 @@
-"""The narrator (BASELINE configs[4] / SURVEY.md section 8f rank 4), MI355X-native, inference only:
+"""The narrator (BASELINE configs[4] / SURVEY.md section 8f rank 4), MI355X-native, inference and bf16 training:
 `VCLM_HF` = video tower (all-token features) -> attention pooling onto `num_img_queries` learned queries -> LayerNorm
 (`encode_image`, narrator.py:63-87) -> gated-cross-attention GPT-2 (`lavila_amd.gpt2_gated`) -> `forward` (teacher-forced
 logits, narrator.py:89-104) and `generate` (multinomial / top-k / top-p sampling with perplexities, narrator.py:106-147),
@@ -8,7 +8,9 @@ context_norm.gamma, to_q.weight, to_kv.weight, to_out.weight}`, `img_attn_pool_n
 
 `CrossAttention` / `LayerNorm` mirror `lavila/models/coca.py:25-131` (same constructor); the pooling core is one
 C-ABI call (lvl_mq_cross_attn_fwd), the projections go through ops.linear (own MFMA GEMMs where the widths tile),
-the LayerNorms through lvl_layernorm_fwd. The pooling core has no backward kernel and says so.
+the LayerNorms through lvl_layernorm_fwd; the pooling core's backward (bf16) is lvl_mq_cross_attn_bwd (softmax recomputed from
+q, kv and the cotangent; the gradients of shared queries are added over the clips in clip order), so `forward` -> CaptionLoss
+-> backward() reaches the tower, the pooler and -- through the decoder's training plan -- every trainable parameter.
 
 `generate` keeps the reference's signature and bookkeeping (nll / entropy accumulation, eos tracking, teacher forcing,
 num_return_sequences) but decodes against a key/value cache, one hipGraph replay per token (gpt2_gated.DecodeSession)
@@ -54,12 +56,26 @@ class _MqCrossAttnFn(torch.autograd.Function):
         out = torch.empty(B, nq, heads * 64, dtype=kv.dtype, device=kv.device)
         C.check(C.lib().lvl_mq_cross_attn_fwd(C.ptr(q), qb, C.ptr(kv), C.ptr(out), B, nq, heads, Tk, C.dtype_code(kv),
                                               C.stream_ptr()), 'lvl_mq_cross_attn_fwd')
+        ctx.save_for_backward(q, kv)
+        ctx.cfg = (qb, heads)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        raise C.HipExtensionError('mq_cross_attention has no backward kernel: the narrator seam is inference-only '
-                                  '(run it under torch.no_grad())')
+        q, kv = ctx.saved_tensors
+        if kv.dtype != torch.bfloat16:          # the narrator trains in bf16 (so does its decoder): float32 stays refused
+            raise C.HipExtensionError('mq_cross_attention backward runs in bf16 (bf16 parameters or torch.autocast(\'cuda\', '
+                                      'dtype=torch.bfloat16)): the float32 narrator seam is inference-only')
+        qb, heads = ctx.cfg
+        B, Tk, _ = kv.shape
+        nq = q.shape[-2]
+        dout = dout.to(kv.dtype).contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        ws = torch.empty(int(C.lib().lvl_mq_cross_attn_bwd_ws(B, nq, heads, int(qb == 0))), dtype=torch.float32,
+                         device=kv.device)
+        C.check(C.lib().lvl_mq_cross_attn_bwd(C.ptr(q), qb, C.ptr(kv), C.ptr(dout), C.ptr(dq), C.ptr(dkv), C.ptr(ws), B, nq,
+                                              heads, Tk, C.dtype_code(kv), C.stream_ptr()), 'lvl_mq_cross_attn_bwd')
+        return dq, dkv, None
 
 
 def mq_cross_attention(q, kv, heads):
@@ -173,8 +189,9 @@ class VCLM_HF(nn.Module):
         else:
             self.text_decoder.gradient_checkpointing_disable()
         text, labels = text[:, :-1], text[:, 1:]
-        image_tokens = self.encode_image(image, use_checkpoint=use_checkpoint)
-        logits = self.text_decoder(text.contiguous(), encoder_hidden_states=image_tokens).logits
+        with ops.model_forward():                 # tower, pooler and decoder share one weight-copy generation per step
+            image_tokens = self.encode_image(image, use_checkpoint=use_checkpoint)
+            logits = self.text_decoder(text.contiguous(), encoder_hidden_states=image_tokens).logits
         return {'text_tokens_logits': logits.permute(0, 2, 1), 'labels': labels}
 
     @staticmethod
