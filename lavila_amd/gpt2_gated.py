@@ -1,15 +1,18 @@
-"""The narrator's text decoder -- GPT-2 with gated cross-attention (lavila/models/gpt2_gated.py), MI355X-native: an
-inference plan and a bf16 training plan (BASELINE configs[4]: captioning).
+"""The narrator's text decoder -- GPT-2 with gated cross-attention (lavila/models/gpt2_gated.py), MI355X-native, for
+inference and bf16 training (BASELINE configs[4]: captioning).
 
 Module and parameter names are the reference's (`transformer.{wte,wpe,ln_f}`, `transformer.h.{i}.{ln_1, attn.{c_attn,
 c_proj}, ln_2, mlp.{c_fc,c_proj}, crossattention.{c_attn,q_attn,c_proj}, ln_cross_attn, mlp_crossattention.{c_fc,c_proj},
 ln_2_crossattention, alpha_cattn, alpha_dense}`, `lm_head`; Conv1D weights stay [in, out]; the `attn.bias` /
 `attn.masked_bias` mask buffers are kept as state) so that `text_decoder.*` of a reference VCLM checkpoint loads with
-strict=True. The modules only HOLD parameters; the computation is laid out for the device instead of module by module:
+strict=True. The modules only HOLD parameters. The computation is ONE plan (`_run_blocks`: the order of Conv1Ds, gates and
+add + LayerNorm hand-overs) over one of two primitive sets, which share `_lay_out`'s role names; every C entry point has
+one call site:
 
-  * the Conv1D GEMMs run on lvl_linear_tn against a packed inference image of the weights (bf16, [out, in], built once per
-    parameter state; the vocabulary is padded to the GEMM's 256-column tiles), f32 models (the parity configuration) on
-    the library GEMM against the masters;
+`_Pack`, inference (everything under torch.no_grad(), teacher-forced or decoding):
+  * the Conv1D GEMMs run on lvl_linear_tn / lvl_linear_skinny against a packed image of the weights (bf16, [out, in], built
+    once per parameter state; the vocabulary is padded to the GEMM's 256-column tiles), f32 models (the parity
+    configuration) on the same kernels' f32-class mode against bf16 term images;
   * every residual add (with its tanh(alpha) gate) is fused with the LayerNorm that reads the sum next
     (lvl_gated_add_layernorm) and, while decoding, both are folded into the prologue of the Conv1D that consumes the
     normalised rows (lvl_linear_skinny_ln); the embedding is one gather (lvl_gpt2_embed);
@@ -21,19 +24,18 @@ strict=True. The modules only HOLD parameters; the computation is laid out for t
     for every step. The reference re-runs the whole prefix per token (narrator.py:118-143, `use_cache=False`): same
     numbers, quadratically more work.
 
-What the reference's vendored HF class offers beyond this path (attention / head masks, token types, past_key_values as
-arguments, pruning, model parallelism, the other heads) raises NotImplementedError.
-
-Training (`GPT2LMHeadModel.forward` with gradients enabled and a trainable decoder parameter, or image tokens that require a
-gradient: the frozen-LM recipe with a trainable pooler): the same order of operations as `_Pack.run`, as small
-torch.autograd.Functions chained by autograd (`_train_forward`) -- Conv1D on lvl_linear_tn / lvl_linear_wgrad (no weight
-gradient for a frozen weight), gated add + LayerNorm (lvl_gated_add_layernorm_train / _bwd), the activations
+`_TrainOps`, training (`GPT2LMHeadModel.forward` with gradients enabled and a trainable decoder parameter, or image tokens
+that require a gradient: the frozen-LM recipe with a trainable pooler): the same primitives as small
+torch.autograd.Functions on the modules' own parameters, chained by autograd -- Conv1D on lvl_linear_tn / lvl_linear_wgrad
+(no weight gradient for a frozen weight), gated add + LayerNorm (lvl_gated_add_layernorm_train / _bwd), the activations
 (lvl_act_fwd / lvl_act_bwd), cross-attention (lvl_cross_attn_rows_fwd / _bwd, at most 256 image tokens), ops.causal_attention,
 the embedding (lvl_text_embed_fwd / _bwd) and the tied lm_head, whose weight gradient adds into wte's. bf16 only (bf16
 parameters, or float32 masters under bf16 autocast): float32 with gradients raises NotImplementedError, and so does a
 non-zero resid / embd / attn_pdrop in training mode (there is no dropout kernel; transformers' GPT2Config defaults the three
-to 0.1, so the reference trains with dropout and this decoder does not). `gradient_checkpointing_enable()` is a no-op: the
-plan keeps its activations. The inference plan, DecodeSession and everything under torch.no_grad() are untouched by it.
+to 0.1, so the reference trains with dropout and this decoder does not). `gradient_checkpointing_enable()` is a no-op.
+
+What the reference's vendored HF class offers beyond this (attention / head masks, token types, past_key_values as
+arguments, pruning, model parallelism, the other heads) raises NotImplementedError.
 """
 import copy
 import os
@@ -69,7 +71,7 @@ def gpt2_config(name='gpt2', **overrides):
         scale_attn_by_inverse_layer_idx=False, reorder_and_upcast_attn=False, tie_word_embeddings=True,
         add_cross_attention=False, bos_token_id=50256, eos_token_id=50256, use_cache=False,
         # transformers' GPT2Config defaults these three to 0.1, so the reference's decoder trains WITH dropout; this decoder
-        # has no dropout kernel and refuses to train with a non-zero value (GPT2LMHeadModel._check_dropout)
+        # has no dropout kernel and refuses to train with a non-zero value (GPT2LMHeadModel._train_ops)
         resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0)
     for k, v in overrides.items():
         setattr(cfg, k, v)
@@ -202,6 +204,38 @@ def _pad_rows(t, multiple):
     return t if n == 0 else torch.cat([t, t.new_zeros(n, *t.shape[1:])])
 
 
+def _tanh_gate(alpha):
+    return None if alpha is None else torch.tanh(alpha.detach().to(torch.float32)).reshape(1)
+
+
+def _lay_out(p, model, conv, ln, gate):
+    """What both primitive sets know of the model: its geometry and, per block, the plan's operands under ONE set of role
+    names. conv(Conv1D), ln(LayerNorm) and gate(alpha parameter or None) give a set's own representation of each."""
+    tr = model.transformer
+    p.D, p.heads, p.eps = tr.embed_dim, tr.h[0].attn.num_heads, float(tr.ln_f.eps)
+    p.vocab, p.positions = tr.wte.weight.shape[0], tr.wpe.weight.shape[0]
+    p.blocks = []
+    for blk in tr.h:
+        e = {'ln_1': ln(blk.ln_1), 'c_attn': conv(blk.attn.c_attn), 'c_proj': conv(blk.attn.c_proj),
+             'ln_2': ln(blk.ln_2), 'fc': conv(blk.mlp.c_fc), 'proj': conv(blk.mlp.c_proj), 'cross': blk.has_cross}
+        if blk.has_cross:
+            e.update({'ln_x': ln(blk.ln_cross_attn), 'xq': conv(blk.crossattention.q_attn),
+                      'xkv': conv(blk.crossattention.c_attn), 'xproj': conv(blk.crossattention.c_proj),
+                      'ln_2x': ln(blk.ln_2_crossattention), 'xfc': conv(blk.mlp_crossattention.c_fc),
+                      'xfproj': conv(blk.mlp_crossattention.c_proj),
+                      'gate_c': gate(getattr(blk, 'alpha_cattn', None)), 'gate_d': gate(getattr(blk, 'alpha_dense', None))})
+        p.blocks.append(e)
+    p.ln_f = ln(tr.ln_f)
+
+
+def cross_attn_rows_raw(q, kv, qrep, heads):
+    """lvl_cross_attn_rows_fwd: rows q [rows, D] over the image keys | values kv [rows / qrep, Tk, 2 D] -> [rows, D]."""
+    out = torch.empty_like(q)
+    C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), q.shape[0], qrep, kv.shape[1], heads,
+                                            C.dtype_code(q), C.stream_ptr()), 'lvl_cross_attn_rows_fwd')
+    return out
+
+
 class _Pack:
     """Inference image of the decoder's parameters for one compute dtype: bf16 -> every Conv1D as a contiguous [out, in]
     bf16 matrix (what lvl_linear_tn streams), the token table padded to a multiple of 256 rows (it doubles as the
@@ -214,15 +248,10 @@ class _Pack:
         tr = model.transformer
         self.dtype = dtype
         self.key = model._param_key()
-        self.D = tr.embed_dim
-        self.heads = tr.h[0].attn.num_heads
-        self.vocab = tr.wte.weight.shape[0]
-        self.positions = tr.wpe.weight.shape[0]
-        self.eps = float(tr.ln_f.eps)
         lowp = dtype == torch.bfloat16
         f32 = lambda p: p.detach().to(torch.float32).contiguous()
         # float32: every Conv1D width is a multiple of the model width (a multiple of 64): the f32-class kernels take them all
-        self.own = (not lowp) and ops.F32_MFMA and self.D % 32 == 0
+        self.own = (not lowp) and ops.F32_MFMA and tr.embed_dim % 32 == 0
 
         def conv(m):      # -> (matrix, bias f32, out, in)
             w = m.weight.detach()
@@ -232,24 +261,7 @@ class _Pack:
                 return (ops.split3(f32(w.t()), 1), f32(m.bias), w.shape[1], w.shape[0])
             return (f32(w), f32(m.bias), w.shape[1], w.shape[0])
 
-        def ln(m):
-            return (f32(m.weight), f32(m.bias))
-
-        def gate(blk, name):
-            return torch.tanh(getattr(blk, name).detach().to(torch.float32)).reshape(1) if hasattr(blk, name) else None
-
-        self.blocks = []
-        for blk in tr.h:
-            e = {'ln_1': ln(blk.ln_1), 'c_attn': conv(blk.attn.c_attn), 'c_proj': conv(blk.attn.c_proj),
-                 'ln_2': ln(blk.ln_2), 'fc': conv(blk.mlp.c_fc), 'proj': conv(blk.mlp.c_proj), 'cross': blk.has_cross}
-            if blk.has_cross:
-                e.update({'ln_x': ln(blk.ln_cross_attn), 'xq': conv(blk.crossattention.q_attn),
-                          'xkv': conv(blk.crossattention.c_attn), 'xproj': conv(blk.crossattention.c_proj),
-                          'ln_2x': ln(blk.ln_2_crossattention), 'xfc': conv(blk.mlp_crossattention.c_fc),
-                          'xfproj': conv(blk.mlp_crossattention.c_proj),
-                          'gate_c': gate(blk, 'alpha_cattn'), 'gate_d': gate(blk, 'alpha_dense')})
-            self.blocks.append(e)
-        self.ln_f = ln(tr.ln_f)
+        _lay_out(self, model, conv, ln=lambda m: (f32(m.weight), f32(m.bias)), gate=_tanh_gate)
         wte, head = tr.wte.weight.detach(), model.lm_head.weight.detach()
         tied = head.data_ptr() == wte.data_ptr()
         if lowp:
@@ -269,7 +281,8 @@ class _Pack:
     def gemm(self, x2, entry, act=None):
         """Conv1D (+ activation). bf16: few rows (decoding) -> lvl_linear_skinny with the activation in its epilogue;
         many rows (teacher-forced captions, the image keys / values) -> lvl_linear_tn, activation in place afterwards;
-        widths neither kernel tiles -> library GEMM (logged). f32: library GEMM against the [in, out] master."""
+        widths neither kernel tiles -> library GEMM (logged). f32: the term images on the own kernels in f32-class mode
+        (ops.linear_f32_rows); the library GEMM against the [in, out] master only with LAVILA_F32_MFMA=0."""
         w, b, n_out, n_in = entry
         rows = x2.shape[0]
         if self.dtype == torch.bfloat16:
@@ -312,35 +325,19 @@ class _Pack:
         return out
 
     def add_ln(self, res, y, gate, ln):
-        """res <- res + gate * y (in place), returns LayerNorm(res)."""
+        """res <- res + gate * y (in place) -> (res, LayerNorm(res))."""
         h = torch.empty_like(res)
         C.check(C.lib().lvl_gated_add_layernorm(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(ln[0]), C.ptr(ln[1]), self.eps,
                                                 C.ptr(res) if y is not None else None, C.ptr(h), res.shape[0], self.D,
                                                 C.dtype_code(res), C.stream_ptr()), 'lvl_gated_add_layernorm')
-        return h
+        return res, h
 
     def act(self, u, which):
         C.check(C.lib().lvl_act_inplace(C.ptr(u), u.numel(), which, C.dtype_code(u), C.stream_ptr()), 'lvl_act_inplace')
         return u
 
     def cross_attn(self, q, kv, qrep):
-        out = torch.empty_like(q)
-        C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), q.shape[0], qrep, kv.shape[1],
-                                                self.heads, C.dtype_code(q), C.stream_ptr()), 'lvl_cross_attn_rows_fwd')
-        return out
-
-    def image_kv(self, enc):
-        """crossattention.c_attn on the image tokens (gpt2_gated.py:330), once per clip and cross-attention block:
-        [Bc, NQ, D] -> list of [Bc, NQ, 2D] (None for blocks without cross-attention)."""
-        enc2 = enc.reshape(-1, enc.shape[-1]).to(self.dtype).contiguous()
-        return [self.gemm(enc2, e['xkv']).reshape(enc.shape[0], enc.shape[1], 2 * self.D) if e['cross'] else None
-                for e in self.blocks]
-
-    def first_ln(self, i, with_image):
-        if i == len(self.blocks):
-            return self.ln_f
-        e = self.blocks[i]
-        return e['ln_x'] if (e['cross'] and with_image) else e['ln_1']
+        return cross_attn_rows_raw(q, kv, qrep, self.heads)
 
     def gemm_ln(self, x, pend, entry, act=None, fuse=True):
         """Conv1D of LayerNorm(x + gate * y) for the pending (y, gate, ln): -> (product, new residual). Few rows in bf16
@@ -363,32 +360,49 @@ class _Pack:
                                                  rows, n_out, n_in, -1 if act is None else act, C.stream_ptr()),
                     'lvl_linear_skinny_ln')
             return out, new_x
-        h = self.add_ln(x, y, gate, ln)
+        x, h = self.add_ln(x, y, gate, ln)
         return self.gemm(h, entry, act), x
 
-    def run(self, x, xkv, qrep, self_attention, fuse_ln=True):
-        """The block stack on rows x [rows, D] -> LayerNorm_f of the final residual. xkv: per block image keys / values
-        or None (no encoder states: plain GPT-2, gpt2_gated.py:432); `self_attention(i, qkv)` -> [rows, D]. Every
-        residual add + LayerNorm is PENDING until the Conv1D that reads it (gemm_ln)."""
-        with_image = xkv is not None
-        pend = (None, None, self.first_ln(0, with_image))
-        for i, e in enumerate(self.blocks):
-            if e['cross'] and with_image:
-                q, x = self.gemm_ln(x, pend, e['xq'], None, fuse_ln)
-                a = self.cross_attn(q, xkv[i], qrep)
-                pend = (self.gemm(a, e['xproj']), e['gate_c'], e['ln_2x'])
-                u, x = self.gemm_ln(x, pend, e['xfc'], C.ACT_SQRELU, fuse_ln)
-                pend = (self.gemm(u, e['xfproj']), e['gate_d'], e['ln_1'])
-            qkv, x = self.gemm_ln(x, pend, e['c_attn'], None, fuse_ln)
-            a = self_attention(i, qkv)
-            pend = (self.gemm(a, e['c_proj']), None, e['ln_2'])
-            u, x = self.gemm_ln(x, pend, e['fc'], C.ACT_GELU_NEW, fuse_ln)
-            pend = (self.gemm(u, e['proj']), None, self.first_ln(i + 1, with_image))
-        return self.add_ln(x, *pend)                     # ln_f feeds lm_head (the 256-column-panel kernel): materialised
+
+# ---- the plan: ONE walk over the blocks, for either primitive set (p: a _Pack, or the _TrainOps defined below) ----------
+def _image_kv(p, enc):
+    """crossattention.c_attn on the image tokens (gpt2_gated.py:330), once per clip and cross-attention block:
+    [Bc, NQ, D] -> list of [Bc, NQ, 2D] (None for blocks without cross-attention)."""
+    enc2 = enc.reshape(-1, enc.shape[-1]).to(p.dtype).contiguous()
+    return [p.gemm(enc2, e['xkv']).reshape(enc.shape[0], enc.shape[1], 2 * p.D) if e['cross'] else None
+            for e in p.blocks]
+
+
+def _run_blocks(p, x, xkv, qrep, self_attention, fuse_ln=True):
+    """The block stack on rows x [rows, D] -> LayerNorm_f of the final residual. xkv: per block image keys / values
+    or None (no encoder states: plain GPT-2, gpt2_gated.py:432); `self_attention(i, qkv)` -> [rows, D]. Every residual
+    add + LayerNorm is PENDING as (y, gate, ln) until the Conv1D that reads it (p.gemm_ln -> (product, new residual))."""
+    with_image = xkv is not None
+
+    def first_ln(i):
+        if i == len(p.blocks):
+            return p.ln_f
+        e = p.blocks[i]
+        return e['ln_x'] if (e['cross'] and with_image) else e['ln_1']
+
+    pend = (None, None, first_ln(0))
+    for i, e in enumerate(p.blocks):
+        if e['cross'] and with_image:
+            q, x = p.gemm_ln(x, pend, e['xq'], None, fuse_ln)
+            a = p.cross_attn(q, xkv[i], qrep)
+            pend = (p.gemm(a, e['xproj']), e['gate_c'], e['ln_2x'])
+            u, x = p.gemm_ln(x, pend, e['xfc'], C.ACT_SQRELU, fuse_ln)
+            pend = (p.gemm(u, e['xfproj']), e['gate_d'], e['ln_1'])
+        qkv, x = p.gemm_ln(x, pend, e['c_attn'], None, fuse_ln)
+        a = self_attention(i, qkv)
+        pend = (p.gemm(a, e['c_proj']), None, e['ln_2'])
+        u, x = p.gemm_ln(x, pend, e['fc'], C.ACT_GELU_NEW, fuse_ln)
+        pend = (p.gemm(u, e['proj']), None, first_ln(i + 1))
+    return p.add_ln(x, *pend)[1]                         # ln_f feeds lm_head (the 256-column-panel kernel): materialised
 
 
 # --------------------------------------------------------------------------------------------------
-# training plan (bf16): the order of operations of _Pack.run as autograd Functions over the own kernels
+# training (bf16): autograd Functions over the own kernels, and the primitive set (_TrainOps) that hands them to the plan
 # --------------------------------------------------------------------------------------------------
 class _Conv1DFn(torch.autograd.Function):
     """y = x W + b for a Conv1D weight W [in, out]: forward and input gradient on lvl_linear_tn, weight gradient on
@@ -440,7 +454,7 @@ class _GatedAddLnFn(torch.autograd.Function):
         res = res if res.is_contiguous() else res.contiguous()
         rows, D = res.shape
         g, b = ops._f32(gamma), ops._f32(beta)
-        gate = None if alpha is None else torch.tanh(alpha.detach().to(torch.float32)).reshape(1)
+        gate = _tanh_gate(alpha)
         if y is not None:
             y = y if y.is_contiguous() else y.contiguous()
         s = torch.empty_like(res) if y is not None else None
@@ -518,9 +532,7 @@ class _CrossAttnRowsFn(torch.autograd.Function):
         q = q if q.is_contiguous() else q.contiguous()
         kv = kv if kv.is_contiguous() else kv.contiguous()
         C.require_device(q, kv)
-        out = torch.empty_like(q)
-        C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), q.shape[0], qrep, kv.shape[1], heads,
-                                                C.dtype_code(q), C.stream_ptr()), 'lvl_cross_attn_rows_fwd')
+        out = cross_attn_rows_raw(q, kv, qrep, heads)
         ctx.save_for_backward(q, kv)
         ctx.cfg = (qrep, heads)
         return out
@@ -574,44 +586,38 @@ class _LmHeadFn(torch.autograd.Function):
         return dh, dw
 
 
-def _train_forward(model, ids, enc):
-    """Teacher-forced logits [B, L, vocab] with a backward: _Pack.run's order of operations on bf16 rows."""
-    tr = model.transformer
-    B, L = ids.shape
-    D, heads, eps = tr.embed_dim, tr.h[0].attn.num_heads, float(tr.ln_f.eps)
-    conv = lambda x2, m: _Conv1DFn.apply(x2, m.weight, m.bias)
-    x = ops.text_embed(ids, tr.wte.weight, tr.wpe.weight, torch.bfloat16)
-    if x is None:                                     # tables the gather kernel does not take (bf16 parameters, width > 2048)
-        x = (F.embedding(ids, tr.wte.weight) + tr.wpe.weight[:L]).to(torch.bfloat16)
-    x = x.reshape(B * L, D)
-    with_image = enc is not None and any(blk.has_cross for blk in tr.h)
-    if with_image:
-        enc2 = enc.reshape(-1, enc.shape[-1]).to(torch.bfloat16)
+class _TrainOps:
+    """The plan's primitives as the autograd Functions above (rows in bf16). A Conv1D / LayerNorm role is the module itself,
+    a gate the alpha parameter (_GatedAddLnFn takes and differentiates its tanh). Nothing is cached: built per forward."""
+    dtype = torch.bfloat16
 
-    def first_ln(i):
-        if i == len(tr.h):
-            return tr.ln_f
-        blk = tr.h[i]
-        return blk.ln_cross_attn if (blk.has_cross and with_image) else blk.ln_1
+    def __init__(self, model):
+        _lay_out(self, model, conv=lambda m: m, ln=lambda m: m, gate=lambda alpha: alpha)
+        self.wte, self.wpe, self.head = model.transformer.wte.weight, model.transformer.wpe.weight, model.lm_head.weight
 
-    ln = first_ln(0)
-    h = _GatedAddLnFn.apply(x, None, None, ln.weight, ln.bias, eps)
-    add_ln = lambda x, y, alpha, ln: _GatedAddLnFn.apply(x, y, alpha, ln.weight, ln.bias, eps)
-    for i, blk in enumerate(tr.h):
-        if blk.has_cross and with_image:
-            xa = blk.crossattention
-            q = conv(h, xa.q_attn)
-            kv = conv(enc2, xa.c_attn).reshape(enc.shape[0], enc.shape[1], 2 * D)
-            a = _CrossAttnRowsFn.apply(q, kv, L, heads)
-            x, h = add_ln(x, conv(a, xa.c_proj), getattr(blk, 'alpha_cattn', None), blk.ln_2_crossattention)
-            u = _ActFn.apply(conv(h, blk.mlp_crossattention.c_fc), C.ACT_SQRELU)
-            x, h = add_ln(x, conv(u, blk.mlp_crossattention.c_proj), getattr(blk, 'alpha_dense', None), blk.ln_1)
-        qkv = conv(h, blk.attn.c_attn)
-        a = ops.causal_attention(qkv.reshape(B, L, 3 * D), heads).reshape(B * L, D)
-        x, h = add_ln(x, conv(a, blk.attn.c_proj), None, blk.ln_2)
-        u = _ActFn.apply(conv(h, blk.mlp.c_fc), C.ACT_GELU_NEW)
-        x, h = add_ln(x, conv(u, blk.mlp.c_proj), None, first_ln(i + 1))
-    return _LmHeadFn.apply(h, model.lm_head.weight).reshape(B, L, -1)
+    def embed(self, ids, L):
+        x = ops.text_embed(ids, self.wte, self.wpe, self.dtype)
+        if x is None:                                 # tables the gather kernel does not take (bf16 parameters, width > 2048)
+            x = (F.embedding(ids, self.wte) + self.wpe[:L]).to(self.dtype)
+        return x.reshape(-1, self.D)
+
+    def gemm(self, x2, m, act=None):
+        y = _Conv1DFn.apply(x2, m.weight, m.bias)
+        return y if act is None else _ActFn.apply(y, act)
+
+    def add_ln(self, res, y, alpha, ln):
+        out = _GatedAddLnFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps)
+        return out if y is not None else (res, out)
+
+    def gemm_ln(self, x, pend, m, act=None, fuse=True):
+        x, h = self.add_ln(x, *pend)
+        return self.gemm(h, m, act), x
+
+    def cross_attn(self, q, kv, qrep):
+        return _CrossAttnRowsFn.apply(q, kv, qrep, self.heads)
+
+    def logits(self, h2):
+        return _LmHeadFn.apply(h2, self.head)
 
 
 class DecodeSession:
@@ -628,7 +634,7 @@ class DecodeSession:
         if self.capacity > pack.positions:
             raise ValueError(f'decode length {self.capacity} exceeds the decoder\'s {pack.positions} positions')
         self.contexts, self.context_len = Bc, image_tokens.shape[1]
-        self.xkv = pack.image_kv(image_tokens)
+        self.xkv = _image_kv(pack, image_tokens)
         self.cache = [torch.zeros(self.rows, self.capacity, 2 * pack.D, dtype=pack.dtype, device=dev) for _ in pack.blocks]
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ids = torch.zeros(self.rows, dtype=torch.int64, device=dev)
@@ -652,7 +658,7 @@ class DecodeSession:
     def _run(self):
         p = self.pack
         x = p.embed(self.ids, 1, self.pos)
-        h = p.run(x, self.xkv, self.qrep, self._self_attention, fuse_ln=not self.graphed)
+        h = _run_blocks(p, x, self.xkv, self.qrep, self._self_attention, fuse_ln=not self.graphed)
         logits = p.logits(h)
         self.pos.add_(1)
         return logits
@@ -690,7 +696,7 @@ class DecodeSession:
         graph reads, the position returns to 0 (cache rows are rewritten before they are read)."""
         if tuple(image_tokens.shape[:2]) != (self.contexts, self.context_len):
             raise ValueError('DecodeSession.rebind: image tokens of another shape need another session')
-        for dst, src in zip(self.xkv, self.pack.image_kv(image_tokens)):
+        for dst, src in zip(self.xkv, _image_kv(self.pack, image_tokens)):
             if dst is not None:
                 dst.copy_(src)
         self.reset()
@@ -809,47 +815,46 @@ class GPT2LMHeadModel(nn.Module):
                                       'not on the narrator path (cached decoding: decode_session())')
         if input_ids is None:
             raise ValueError('You have to specify input_ids')
-        if self._trains(encoder_hidden_states):
-            return self._forward_train(input_ids, encoder_hidden_states, labels)
-        pack = self._pack()
+        train = self._trains(encoder_hidden_states)
+        p = self._train_ops() if train else self._pack()
         shape = tuple(input_ids.shape)
         L = shape[-1]
-        if L > pack.positions:
-            raise ValueError(f'sequence of {L} tokens exceeds the decoder\'s {pack.positions} positions')
-        ids = input_ids.reshape(-1, L)
+        if L > p.positions:
+            raise ValueError(f'sequence of {L} tokens exceeds the decoder\'s {p.positions} positions')
+        ids = input_ids.reshape(-1, L).contiguous()
         B = ids.shape[0]
-        lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())      # ONE read-back; nn.Embedding would
-        # fail on out-of-range ids, the gather kernel clamps
-        if lo < 0 or hi >= pack.vocab:
-            raise IndexError(f'input_ids out of range [0, {pack.vocab}): min {lo}, max {hi}')
-        with torch.no_grad(), torch.autocast('cuda', enabled=False):
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())      # ONE read-back; the gather kernels clamp
+        if lo < 0 or hi >= p.vocab:
+            raise IndexError(f'input_ids out of range [0, {p.vocab}): min {lo}, max {hi}')
+        enc = encoder_hidden_states
+        if enc is not None:
+            enc = ops.lowp(enc)
+            if enc.shape[0] != B or enc.shape[-1] != p.D:
+                raise ValueError(f'encoder_hidden_states {tuple(enc.shape)} does not match {B} sequences of width {p.D}')
+        with (ops.model_forward() if train else torch.no_grad()), torch.autocast('cuda', enabled=False):
             xkv = qrep = None
-            if encoder_hidden_states is not None and any(e['cross'] for e in pack.blocks):
-                enc = ops.lowp(encoder_hidden_states)
-                if enc.shape[0] != B or enc.shape[-1] != pack.D:
-                    raise ValueError(f'encoder_hidden_states {tuple(enc.shape)} does not match {B} sequences of width {pack.D}')
-                xkv, qrep = pack.image_kv(enc), L
-            x = pack.embed(ids, L)
+            if enc is not None and any(e['cross'] for e in p.blocks):
+                xkv, qrep = _image_kv(p, enc), L
 
             def self_attention(i, qkv):
-                return ops.causal_attention(qkv.reshape(B, L, 3 * pack.D), pack.heads).reshape(B * L, pack.D)
-            h = pack.run(x, xkv, qrep, self_attention)
-            logits = pack.logits(h).reshape(*shape, pack.vocab)
+                return ops.causal_attention(qkv.reshape(B, L, 3 * p.D), p.heads).reshape(B * L, p.D)
+            h = _run_blocks(p, p.embed(ids, L), xkv, qrep, self_attention)
+            logits = p.logits(h).reshape(*shape, p.vocab)
             loss = None
             if labels is not None:                              # gpt2_gated.py:1142-1148
-                loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, pack.vocab).float(), labels[..., 1:].reshape(-1))
-        if self.transformer.wte.weight.dtype == torch.float16 and not torch.is_autocast_enabled():
+                loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, p.vocab).float(), labels[..., 1:].reshape(-1))
+        if not train and self.transformer.wte.weight.dtype == torch.float16 and not torch.is_autocast_enabled():
             logits = logits.to(torch.float16)
         return CausalLMOutput(logits, loss)
 
-    # ---- training ----------------------------------------------------------------------------------------
     def _trains(self, encoder_hidden_states):
-        """The training plan runs when gradients are enabled and a decoder parameter or the image tokens require one (the
-        latter: freeze_lm_weights() on everything with a trainable pooler in front)."""
+        """The training primitives run when gradients are enabled and a decoder parameter or the image tokens require one
+        (the latter: freeze_lm_weights() on everything with a trainable pooler in front)."""
         return torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
                                             (encoder_hidden_states is not None and encoder_hidden_states.requires_grad))
 
-    def _forward_train(self, input_ids, encoder_hidden_states, labels):
+    def _train_ops(self):
+        """The training primitive set, after the refusals of what it does not do (raised before any device work)."""
         if self._compute_dtype() != torch.bfloat16:
             raise NotImplementedError('lavila_amd.gpt2_gated trains in bf16 (bf16 parameters, or float32 masters under '
                                       'torch.autocast(\'cuda\', dtype=torch.bfloat16)); there is no float32 backward for the '
@@ -859,28 +864,7 @@ class GPT2LMHeadModel(nn.Module):
             raise NotImplementedError(f'the decoder has no dropout: config.{" / ".join(drop)} must be 0.0 to train it '
                                       '(transformers\' GPT2Config defaults them to 0.1), or call .eval()')
         C.require_device(self.transformer.wte.weight)
-        tr = self.transformer
-        vocab, positions, D = tr.wte.weight.shape[0], tr.wpe.weight.shape[0], tr.embed_dim
-        shape = tuple(input_ids.shape)
-        L = shape[-1]
-        if L > positions:
-            raise ValueError(f'sequence of {L} tokens exceeds the decoder\'s {positions} positions')
-        ids = input_ids.reshape(-1, L).contiguous()
-        lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())
-        if lo < 0 or hi >= vocab:
-            raise IndexError(f'input_ids out of range [0, {vocab}): min {lo}, max {hi}')
-        enc = encoder_hidden_states
-        if enc is not None:
-            enc = ops.lowp(enc)
-            if enc.shape[0] != ids.shape[0] or enc.shape[-1] != D:
-                raise ValueError(f'encoder_hidden_states {tuple(enc.shape)} does not match {ids.shape[0]} sequences of '
-                                 f'width {D}')
-        with ops.model_forward(), torch.autocast('cuda', enabled=False):
-            logits = _train_forward(self, ids, enc).reshape(*shape, vocab)
-            loss = None
-            if labels is not None:                              # gpt2_gated.py:1142-1148
-                loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, vocab).float(), labels[..., 1:].reshape(-1))
-        return CausalLMOutput(logits, loss)
+        return _TrainOps(self)
 
     def decode_session(self, encoder_hidden_states, max_length, seqs_per_context=1, graph=True):
         """Cached decoding against `encoder_hidden_states` [contexts, NQ, D]; see DecodeSession. The last sessions are

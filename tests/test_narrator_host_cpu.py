@@ -28,7 +28,7 @@ def _emulate_device_primitives(monkeypatch):
     def add_ln(self, res, y, gate, ln):
         if y is not None:
             res += (1.0 if gate is None else gate) * y
-        return O.layer_norm(res, ln[0], ln[1], self.eps)
+        return res, O.layer_norm(res, ln[0], ln[1], self.eps)
 
     def act(self, u, which):
         u.copy_(O.gelu_new(u) if which == C.ACT_GELU_NEW else O.sq_relu(u))
@@ -130,6 +130,64 @@ def test_decoder_plan_and_generate_bookkeeping(variant, monkeypatch):
                                           v['bos'], v['eos'], v['pad'], 6, target=odd, teacher_forcing=True, use_cache=False)
         assert torch.equal(a[0], want[0])
         torch.testing.assert_close(a[1], want[1], atol=0, rtol=1e-3)
+
+
+@pytest.mark.parametrize('variant', ['freq1_gated', 'freq2_plain'])
+def test_training_primitives_walk_the_same_plan(variant, monkeypatch):
+    """The training side is the SAME plan function over _TrainOps, the adaptor to the autograd Functions: with every
+    Function replaced by its oracle formula (float32 rows instead of bf16) the teacher-forced logits are the reference's
+    own, within the bounds of the inference side above, and a gradient reaches every decoder parameter and the image
+    tokens -- the roles, the gates and the (residual, normalised rows) hand-over are wired as the plan expects."""
+    from lavila_amd import _cabi as C
+    from lavila_amd import gpt2_gated as G
+    from lavila_amd import ops
+    _emulate_device_primitives(monkeypatch)
+    real_run, walks = G._run_blocks, []
+    monkeypatch.setattr(G, '_run_blocks', lambda p, *a, **k: (walks.append(type(p).__name__), real_run(p, *a, **k))[1])
+    fn = lambda f: types.SimpleNamespace(apply=f)
+
+    def gated_add_ln(res, y, alpha, gamma, beta, eps):
+        if y is None:
+            return O.layer_norm(res, gamma, beta, eps)
+        s = res + (y if alpha is None else torch.tanh(alpha) * y)
+        return s, O.layer_norm(s, gamma, beta, eps)
+
+    def cross_attn(q, kv, qrep, heads):
+        D = q.shape[-1]
+        return O.gpt2_attention_core(q.reshape(kv.shape[0], qrep, D), kv[..., :D], kv[..., D:], heads, causal=False).reshape(-1, D)
+
+    monkeypatch.setattr(G, '_Conv1DFn', fn(lambda x2, w, b: x2 @ w + b))
+    monkeypatch.setattr(G, '_GatedAddLnFn', fn(gated_add_ln))
+    monkeypatch.setattr(G, '_ActFn', fn(lambda u, which: O.gelu_new(u) if which == C.ACT_GELU_NEW else O.sq_relu(u)))
+    monkeypatch.setattr(G, '_CrossAttnRowsFn', fn(cross_attn))
+    monkeypatch.setattr(G, '_LmHeadFn', fn(lambda h2, w: h2 @ w.t()))
+    monkeypatch.setattr(G._TrainOps, 'dtype', torch.float32)
+    monkeypatch.setattr(ops, 'text_embed', lambda *a: None)
+    m, c, d, v = _model(variant)
+    dec = m.text_decoder
+    monkeypatch.setattr(dec, '_compute_dtype', lambda: torch.bfloat16)
+    img = v['image_tokens'].clone().requires_grad_(True)
+    out = dec(v['text'][:, :-1].contiguous(), encoder_hidden_states=img, labels=v['text'][:, :-1].contiguous())
+    assert walks == ['_TrainOps'] and out.logits.requires_grad
+    torch.testing.assert_close(out.logits.detach().permute(0, 2, 1), v['logits'], atol=2e-4, rtol=1e-4)
+    out.loss.backward()
+    assert img.grad is not None and img.grad.abs().max() > 0
+    dead = [k for k, p in dec.named_parameters() if p.grad is None or not p.grad.abs().max() > 0]
+    assert not dead, dead
+
+
+def test_encoder_states_are_checked_whenever_they_are_passed(monkeypatch):
+    """One input path for inference and training: encoder states that do not match the ids (sequences, width) raise a
+    ValueError even when the decoder has no cross-attention block to read them; matching ones are then ignored."""
+    from lavila_amd.gpt2_gated import GPT2LMHeadModel, gpt2_config
+    _emulate_device_primitives(monkeypatch)
+    dec = GPT2LMHeadModel(gpt2_config('gpt2', vocab_size=50, n_positions=16, n_embd=64, n_layer=1, n_head=1)).eval()
+    ids = torch.ones(2, 4, dtype=torch.long)
+    with torch.no_grad():
+        for bad in (torch.zeros(2, 3, 32), torch.zeros(3, 3, 64)):
+            with pytest.raises(ValueError, match='encoder_hidden_states'):
+                dec(ids, encoder_hidden_states=bad)
+        assert torch.equal(dec(ids, encoder_hidden_states=torch.zeros(2, 3, 64)).logits, dec(ids).logits)
 
 
 def test_reference_state_dict_names_and_shapes():
