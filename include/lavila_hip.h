@@ -84,6 +84,33 @@ int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, const float
                       void* dx, void* dx_plain, float* dgamma, float* dbeta, float* dxsum, float* ws,
                       int64_t rows, int cols, int dtype, void* stream);
 
+/* ---- Stochastic depth: per-sample scaled residual add + LayerNorm ------------------------------------
+ * replaces `x = x + self.drop_path(branch)` followed by the next LayerNorm in SpaceTimeBlock.forward
+ * (timesformer.py:192,196; timm's DropPath: branch * bernoulli(keep) / keep, one draw per sample).
+ *
+ * forward:  s = res + c_b * (y + ybias), c_b = scale[row / rows_per_sample];  h = LayerNorm(s) * gamma + beta
+ *   res, y, s_out, h_out: [rows, cols] dtype; ybias (nullable), gamma, beta: [cols] f32; scale:
+ *   [rows / rows_per_sample] f32 (device memory; the values the caller drew, 0 or 1 / keep); mean, rstd: [rows] f32.
+ *   Per element v = fma(c, y, res); v = fma(c, ybias, v), rounded once to dtype when stored to s_out; the
+ *   statistics are those of the rounded value (as lvl_layernorm_fwd with s_out). Hence c = 1 gives
+ *   lvl_layernorm_fwd(res, y, ybias)'s s, h, mean and rstd to the bit, and c = 0 gives s = res to the bit and
+ *   the plain LayerNorm of res. Rows of dropped samples are read like any other row.
+ * backward: from dh, the kept s, the statistics and an optional dadd (the gradient reaching s through s_out):
+ *   ds [rows, cols] = d res, dgamma, dbeta: lvl_layernorm_bwd(dh, s, dadd)'s dx, dgamma, dbeta to the bit;
+ *   dy [rows, cols] = c_b * ds (the stored ds, rounded once more); dysum (nullable) [cols] f32 = the column
+ *   sums of dy as stored (= d ybias, and the column-sum token of y), from partial slabs in a fixed order.
+ *   ws: lvl_workspace_floats("droppath_add_layernorm_bwd", rows, cols).
+ * cols % 8 == 0, cols <= 4096, rows % rows_per_sample == 0, rows < 2^32; rows == 0 is a no-op (the backward then zeroes
+ * dgamma, dbeta and dysum). No allocation, no synchronisation, no atomics; hipGraph-capturable. */
+int lvl_droppath_add_layernorm_fwd(const void* res, const void* y, const float* ybias, const float* scale,
+                                   const float* gamma, const float* beta, void* s_out, void* h_out, float* mean,
+                                   float* rstd, int64_t rows, int64_t rows_per_sample, int cols, float eps,
+                                   int dtype, void* stream);
+int lvl_droppath_add_layernorm_bwd(const void* dh, const void* s, const float* gamma, const float* mean,
+                                   const float* rstd, const float* scale, const void* dadd, void* ds, void* dy,
+                                   float* dgamma, float* dbeta, float* dysum, float* ws, int64_t rows,
+                                   int64_t rows_per_sample, int cols, int dtype, void* stream);
+
 /* ---- LayerNorm output, rebuilt (selective activation recompute) -----------------------------------
  * y = (s - mean[row]) * rstd[row] * gamma + beta with s = x (+ x2) (+ xbias) formed as lvl_layernorm_fwd
  * forms it, and mean / rstd the statistics that call returned: y equals that call's y to the bit (pass

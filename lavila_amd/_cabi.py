@@ -29,6 +29,8 @@ SIGNATURES = {
     'lvl_workspace_floats': (_L, [_c.c_char_p, _L, _L]),
     'lvl_layernorm_fwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P]),
     'lvl_layernorm_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
+    'lvl_droppath_add_layernorm_fwd': (_I, [_P] * 10 + [_L, _L, _I, _F, _I, _P]),
+    'lvl_droppath_add_layernorm_bwd': (_I, [_P] * 13 + [_L, _L, _I, _I, _P]),
     'lvl_layernorm_apply': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'lvl_quickgelu_apply': (_I, [_P, _P, _L, _I, _I, _P]),
     'lvl_bias_quickgelu_fwd': (_I, [_P, _P, _P, _L, _I, _I, _P]),

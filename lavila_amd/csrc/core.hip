@@ -18,6 +18,7 @@ int lvl_gelu_bwd_row_blocks();
 int lvl_qkv_bias_row_blocks();
 int lvl_colsum_mid_rows();
 int lvl_gate_bwd_parts();
+int lvl_dp_dy_parts();
 int64_t lvl_wgrad_workspace_floats(int64_t N, int64_t K);
 int64_t lvl_linear_tn_workspace_floats(int64_t M, int64_t N);
 
@@ -84,6 +85,9 @@ extern "C" int64_t lvl_workspace_floats(const char* op, int64_t rows, int64_t co
   // lvl_layernorm_bwd's workspace + one partial of the gate gradient per workgroup of the dy / dgate pass
   if (!strcmp(op, "gated_add_layernorm_bwd"))
     return (int64_t)(lvl_ln_bwd_parts() + lvl_colsum_mid_rows()) * 3 * cols + lvl_gate_bwd_parts();
+  // lvl_layernorm_bwd's workspace + the partial column-sum slabs of the dy pass and their reduction's intermediate rows
+  if (!strcmp(op, "droppath_add_layernorm_bwd"))
+    return (int64_t)(lvl_ln_bwd_parts() + lvl_colsum_mid_rows()) * 3 * cols + (int64_t)(lvl_dp_dy_parts() + lvl_colsum_mid_rows()) * cols;
   if (!strcmp(op, "bias_quickgelu_bwd")) return (int64_t)(lvl_gelu_bwd_row_blocks() + lvl_colsum_mid_rows()) * cols;
   if (!strcmp(op, "divided_attn_fwd")) return rows * 64 * 66;   // <= 64 CLS-row partial records per (b,h)
   // delta [B*H, T] + the cls token's partial gradient records: <= 64 slots of [192] per (b, h) (one per frame / per

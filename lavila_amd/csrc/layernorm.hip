@@ -432,16 +432,24 @@ __device__ __forceinline__ void ln_bwd_combine(float* smem, float* __restrict__ 
   }
 }
 
+// Stochastic depth (lvl_droppath_add_layernorm_*): the sample of a row. The entries take rows < 2^32, so that this is one
+// 32-bit division: straight-line code (a 64-bit division, or a choice between the two, would put a branch into the row loops)
+__device__ __forceinline__ uint32_t dp_sample(int64_t row, int64_t rps) { return (uint32_t)row / (uint32_t)rps; }
+
 // EXACT-WIDTH backward (cols == VPL * 64 * W; round 6): ln_bwd_kernel with no conditional vector-memory instruction in the
 // row loop (see ln_fwd_exact_kernel: the general kernel's loop waits vmcnt(0) -- for the prefetched next row as well -- in
 // front of every reduction). X2: the normalised row is x + x2 (+ bias, zeros when there is none); DADD: dx = dx_ln + dadd;
 // PLAIN: dx_ln is stored to dx_plain as well. mean / rstd of the next row are prefetched with it.
-template <typename T, int VPL, int W, bool X2, bool DADD, bool PLAIN>
+// DY (stochastic depth, with neither X2 nor PLAIN): dy = scale[sample of the row] * dx is stored beside dx -- formed from
+// dx AS STORED (rounded to T) and rounded once more, which is what the composed form (dp_dy_kernel on the stored dx) gives
+// to the bit -- and the column sums are those of dy as stored instead of dx's. The row's scale is prefetched with the row.
+template <typename T, int VPL, int W, bool X2, bool DADD, bool PLAIN, bool DY = false>
 __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)) void ln_bwd_exact_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ x2,
     const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ mean,
     const float* __restrict__ rstd, const T* __restrict__ dadd, T* __restrict__ dx, T* __restrict__ dx_plain,
-    float* __restrict__ part, int64_t rows) {
+    float* __restrict__ part, int64_t rows, const float* __restrict__ scale, T* __restrict__ dy_out, int64_t rps) {
+  static_assert(!DY || (!X2 && !PLAIN), "the dy output belongs to the kept-sum forms");
   extern __shared__ __attribute__((aligned(16))) float smem[];   // [3 waves][3][cols]
   constexpr int cols = VPL * 64 * W, nvec = VPL * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -467,11 +475,12 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
   struct Row {
     RawVec<T, W> dy[VPL], x[VPL], x2[X2 ? VPL : 1], dadd[DADD ? VPL : 1];
-    float mu, rs;
+    float mu, rs, c;
   } cur, nxt;
   auto load_row = [&](int64_t r, Row& q) {
     q.mu = mean[r];
     q.rs = rstd[r];
+    if constexpr (DY) q.c = scale[dp_sample(r, rps)];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int64_t off = r * cols + (lane + i * 64) * W;
@@ -485,6 +494,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
     load_row(row, cur);
     // everything requested so far has landed before the loop is entered (see ln_fwd_exact_kernel)
     asm volatile("" : "+v"(cur.mu), "+v"(cur.rs));
+    if constexpr (DY) asm volatile("" : "+v"(cur.c));
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       cur.dy[i].pin();
@@ -541,11 +551,20 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
 #pragma unroll
         for (int j = 0; j < W; ++j) o[j] += e[j];
       }
-      if constexpr (!PLAIN) {
+      if constexpr (!PLAIN && !DY) {
 #pragma unroll
         for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
       }
       VecIO<T, W>::store(dx + off, o);
+      if constexpr (DY) {
+        float d[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          d[j] = cur.c * Elem<T>::round(o[j]);
+          ln_bwd_colsum_elem<T>(d[j], ax[i][j]);
+        }
+        VecIO<T, W>::store(dy_out + off, d);
+      }
     }
     cur = nxt;
   }
@@ -645,6 +664,206 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
     cur = nxt;
   }
   ln_bwd_combine<VPL, W>(smem, part, ag, ab, ax, cols, nvec, lane, wave);
+}
+
+// STOCHASTIC DEPTH (lvl_droppath_add_layernorm_*): the row is s = res + c * (y + bias) with one c = scale[sample] per row.
+constexpr int kDpDyParts = 768;           // partial column-sum slabs of the dy pass (one per workgroup)
+
+// Forward: ln_fwd_kernel's two-operand form with the scaled sum, always keeping s. Per element v = fma(c, y, res), then
+// v = fma(c, bias, v): with c = 1 both are the correctly rounded sums ln_fwd_kernel forms (x, += x2, += bias), with c = 0 both
+// return res. s is rounded once when stored and the statistics are those of the rounded value, through the ln_*_elem helpers.
+// EXACT (cols == VPL * 64 * W): no conditional vector-memory instruction in the row loop, as ln_fwd_exact_kernel -- gamma,
+// beta and the bias in registers, everything requested before the loop pinned there. Both forms prefetch the next row (and its
+// sample's scale) unconditionally (the last rows re-read row `rows - 1`) and store mean / rstd from every lane.
+template <typename T, int VPL, int W, bool EXACT, bool BIAS>
+__global__ __launch_bounds__(256) void dp_ln_fwd_kernel(
+    const T* __restrict__ res, const T* __restrict__ y, const float* __restrict__ bias, const float* __restrict__ scale,
+    const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ s_out, T* __restrict__ out,
+    float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int64_t rps, int cols_rt, float eps) {
+  const int cols = EXACT ? VPL * 64 * W : cols_rt;
+  const int nvec = cols / W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float inv_cols = 1.0f / (float)cols;
+  const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
+  int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
+  if (row >= rows) return;
+  auto on = [&](int i) { return EXACT || lane + i * 64 < nvec; };
+  float g[EXACT ? VPL : 1][W], b[EXACT ? VPL : 1][W], bb[EXACT && BIAS ? VPL : 1][W];
+  if constexpr (EXACT) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      VecIO<float, W>::load(gamma + (lane + i * 64) * W, g[i]);
+      VecIO<float, W>::load(beta + (lane + i * 64) * W, b[i]);
+      if constexpr (BIAS) VecIO<float, W>::load(bias + (lane + i * 64) * W, bb[i]);
+    }
+  }
+  struct Row {
+    RawVec<T, W> x[VPL], y[VPL];
+    float c;
+  } cur, nxt;
+  auto load_row = [&](int64_t r, Row& q) {
+    q.c = scale[dp_sample(r, rps)];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+        const int64_t off = r * cols + (lane + i * 64) * W;
+        q.x[i].load(res + off);
+        q.y[i].load(y + off);
+      }
+    }
+  };
+  load_row(row, cur);
+  if constexpr (EXACT) {
+    // everything requested so far has landed before the loop is entered (see ln_fwd_exact_kernel)
+    asm volatile("" : "+v"(cur.c));
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      cur.x[i].pin();
+      cur.y[i].pin();
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        asm volatile("" : "+v"(g[i][j]), "+v"(b[i][j]));
+        if constexpr (BIAS) asm volatile("" : "+v"(bb[i][j]));
+      }
+    }
+  }
+  for (; row < rows; row += stride) {
+    load_row(row + stride < rows ? row + stride : rows - 1, nxt);      // unconditional prefetch
+    const float c = cur.c;
+    float v[VPL][W];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+        float w[W];
+        cur.x[i].unpack(v[i]);
+        cur.y[i].unpack(w);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[i][j] = fmaf(c, w[j], v[i][j]);
+        if constexpr (BIAS) {
+          if constexpr (EXACT) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) v[i][j] = fmaf(c, bb[i][j], v[i][j]);
+          } else {
+            float bv[W];
+            VecIO<float, W>::load(bias + (lane + i * 64) * W, bv);
+#pragma unroll
+            for (int j = 0; j < W; ++j) v[i][j] = fmaf(c, bv[j], v[i][j]);
+          }
+        }
+        // the sum is what downstream residuals read: round it once, then normalise the rounded value
+        VecIO<T, W>::store(s_out + row * cols + (lane + i * 64) * W, v[i]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[i][j] = Elem<T>::round(v[i][j]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) sum += v[i][j];
+      }
+    }
+    const float mu = ln_mean(sum, inv_cols);
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) ln_sq_elem(v[i][j], mu, sq);
+      }
+    }
+    const float rs = ln_rstd(sq, inv_cols, eps);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+        float o[W];
+        if constexpr (EXACT) {
+#pragma unroll
+          for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, g[i][j], b[i][j]);
+        } else {
+          float gv[W], bv[W];
+          VecIO<float, W>::load(gamma + (lane + i * 64) * W, gv);
+          VecIO<float, W>::load(beta + (lane + i * 64) * W, bv);
+#pragma unroll
+          for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, gv[j], bv[j]);
+        }
+        VecIO<T, W>::store(out + row * cols + (lane + i * 64) * W, o);
+      }
+    }
+    mean[row] = mu;          // every lane, one address
+    rstd[row] = rs;
+    cur = nxt;
+  }
+}
+
+// Backward, composed form (float32, widths without an exact kernel), second pass (the first is lvl_layernorm_bwd on the kept
+// sum): dy = c * ds from the stored ds, and one partial slab [cols] per workgroup of the column sums of dy as stored. One
+// wave per row as above, so a row's c is one value per wave.
+template <typename T, int VPL, int W, bool EXACT>
+__global__ __launch_bounds__(256) void dp_dy_kernel(const T* __restrict__ ds, const float* __restrict__ scale,
+                                                    T* __restrict__ dy, float* __restrict__ part, int64_t rows,
+                                                    int64_t rps, int cols_rt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // [3 waves][cols]
+  const int cols = EXACT ? VPL * 64 * W : cols_rt;
+  const int nvec = cols / W;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto on = [&](int i) { return EXACT || lane + i * 64 < nvec; };
+  float ax[VPL][W];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i)
+#pragma unroll
+    for (int j = 0; j < W; ++j) ax[i][j] = 0.f;
+  const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
+  int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
+  struct Row {
+    RawVec<T, W> d[VPL];
+    float c;
+  } cur, nxt;
+  auto load_row = [&](int64_t r, Row& q) {
+    q.c = scale[dp_sample(r, rps)];
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+      if (on(i)) q.d[i].load(ds + r * cols + (lane + i * 64) * W);
+  };
+  if (row < rows) load_row(row, cur);
+  for (; row < rows; row += stride) {
+    load_row(row + stride < rows ? row + stride : rows - 1, nxt);      // unconditional prefetch
+    const float c = cur.c;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+        float v[W], o[W];
+        cur.d[i].unpack(v);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          o[j] = c * v[j];
+          ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
+        }
+        VecIO<T, W>::store(dy + row * cols + (lane + i * 64) * W, o);
+      }
+    }
+    cur = nxt;
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) smem[(size_t)(wave - 1) * cols + (lane + i * 64) * W + j] = ax[i][j];
+      }
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      if (on(i)) {
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+          const int k = (lane + i * 64) * W + j;
+          float a = ax[i][j];
+          for (int w = 0; w < 3; ++w) a += smem[(size_t)w * cols + k];
+          part[(size_t)blockIdx.x * cols + k] = a;
+        }
+      }
+    }
+  }
 }
 
 // Column sums of a partial slab part[nparts][width] (f32), deterministic, in two coalesced stages:
@@ -809,7 +1028,8 @@ int ln_bwd_launch(const T* dy, const T* x, const T* x2, const float* bias, const
                   hipStream_t st) {
   const size_t shmem = (size_t)3 * 3 * cols * sizeof(float);
 #define LN_ARGS blocks, shmem, st, dy, x, x2, bias, gamma, mean, rstd, dadd, dx, dx_plain, ws, rows
-#define LN_E(X2, DADD, PLAIN) ln_launch<ln_bwd_exact_kernel<T, VPL, W, X2, DADD, PLAIN>>(LN_ARGS)
+#define LN_E(X2, DADD, PLAIN) \
+  ln_launch<ln_bwd_exact_kernel<T, VPL, W, X2, DADD, PLAIN>>(LN_ARGS, (const float*)nullptr, (T*)nullptr, (int64_t)1)
   if constexpr (ln_has_exact<T, VPL, W>(true)) {
     if (ln_exact_enabled() && cols == VPL * 64 * W && rows > 0) {
       if (!x2 && !bias && !dx_plain) return dadd ? LN_E(false, true, false) : LN_E(false, false, false);
@@ -919,4 +1139,143 @@ extern "C" int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, 
   LVL_CHECK_LAUNCH("layernorm_bwd");
   return lvl_launch_column_reduce(ws, (int)blocks, 3 * cols, cols, ws + (size_t)kLnBwdParts * 3 * cols, dgamma, dbeta,
                                   dxsum, st);
+}
+
+namespace {
+
+template <typename T, int VPL, int W>
+int dp_ln_fwd_launch(const T* res, const T* y, const float* bias, const float* scale, const float* gamma, const float* beta,
+                     T* s_out, T* out, float* mean, float* rstd, int64_t rows, int64_t rps, int cols, float eps,
+                     int64_t blocks, hipStream_t st) {
+#define DP_F(EXACT, BIAS)                                                                                               \
+  ln_launch<dp_ln_fwd_kernel<T, VPL, W, EXACT, BIAS>>(blocks, 0, st, res, y, bias, scale, gamma, beta, s_out, out, mean, \
+                                                      rstd, rows, rps, cols, eps)
+  if constexpr (ln_has_exact<T, VPL, W>(false)) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W) return bias ? DP_F(true, true) : DP_F(true, false);
+  }
+  return bias ? DP_F(false, true) : DP_F(false, false);
+#undef DP_F
+}
+
+// Where the DY instantiation keeps the waves per SIMD of the instantiation it extends and does not spill (compiler report,
+// DESIGN.md section 4): 768 and 2048 columns, and 1024 columns with dadd. 256 columns with dadd and 512 columns lose a wave,
+// 1024 columns without dadd drop from 4 to 3, 4096 columns spill: those take the composed form.
+template <int VPL, int W, bool DADD>
+constexpr bool dp_fused_ok() { return (VPL == 3 && W == 4) || (VPL == 4 && W == 8) || (VPL == 4 && W == 4 && DADD); }
+
+// The fused backward where there is an exact-width kernel (bf16): ln_bwd_exact_kernel<..., DY = true>; *fused tells.
+template <typename T, int VPL, int W, bool DADD>
+int dp_bwd_fused_launch(const T* dh, const T* s, const float* gamma, const float* mean, const float* rstd, const float* scale,
+                        const T* dadd, T* ds, T* dy, float* ws, int64_t rows, int64_t rps, int cols, int64_t blocks,
+                        hipStream_t st, bool* fused) {
+  *fused = false;
+  if constexpr (ln_has_exact<T, VPL, W>(true) && dp_fused_ok<VPL, W, DADD>()) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W && rows > 0) {
+      *fused = true;
+      const size_t shmem = (size_t)3 * 3 * cols * sizeof(float);
+      return ln_launch<ln_bwd_exact_kernel<T, VPL, W, false, DADD, false, true>>(
+          blocks, shmem, st, dh, s, (const T*)nullptr, (const float*)nullptr, gamma, mean, rstd, dadd, ds, (T*)nullptr, ws,
+          rows, scale, dy, rps);
+    }
+  }
+  return LVL_OK;
+}
+
+template <typename T, int VPL, int W>
+int dp_dy_launch(const T* ds, const float* scale, T* dy, float* part, int64_t rows, int64_t rps, int cols, int64_t blocks,
+                 hipStream_t st) {
+  const size_t shmem = (size_t)3 * cols * sizeof(float);
+  if constexpr (ln_has_exact<T, VPL, W>(false)) {
+    if (ln_exact_enabled() && cols == VPL * 64 * W)
+      return ln_launch<dp_dy_kernel<T, VPL, W, true>>(blocks, shmem, st, ds, scale, dy, part, rows, rps, cols);
+  }
+  return ln_launch<dp_dy_kernel<T, VPL, W, false>>(blocks, shmem, st, ds, scale, dy, part, rows, rps, cols);
+}
+
+}  // namespace
+
+int lvl_dp_dy_parts() { return kDpDyParts; }
+
+extern "C" int lvl_droppath_add_layernorm_fwd(const void* res, const void* y, const float* ybias, const float* scale,
+                                              const float* gamma, const float* beta, void* s_out, void* h_out,
+                                              float* mean, float* rstd, int64_t rows, int64_t rows_per_sample, int cols,
+                                              float eps, int dtype, void* stream) {
+  LVL_REQUIRE(rows == 0 || (res && y && scale && gamma && beta && s_out && h_out && mean && rstd),
+              "droppath_add_layernorm_fwd: null pointer");
+  LVL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 4096,
+              "droppath_add_layernorm_fwd: cols=%d must be a multiple of 8, <= 4096", cols);
+  LVL_REQUIRE(rows_per_sample > 0 && rows % rows_per_sample == 0,
+              "droppath_add_layernorm_fwd: rows=%lld must be a multiple of rows_per_sample=%lld", (long long)rows,
+              (long long)rows_per_sample);
+  LVL_REQUIRE(rows < ((int64_t)1 << 32), "droppath_add_layernorm_fwd: rows=%lld must be below 2^32", (long long)rows);
+  LVL_REQUIRE(lvl_aligned16(res) && lvl_aligned16(y) && lvl_aligned16(ybias) && lvl_aligned16(s_out) &&
+                  lvl_aligned16(h_out) && lvl_aligned16(gamma) && lvl_aligned16(beta),
+              "droppath_add_layernorm_fwd: pointers must be 16-byte aligned");
+  if (rows == 0) return LVL_OK;
+  int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  if (blocks > 3072) blocks = 3072;       // the grid of lvl_layernorm_fwd's two-operand form
+#define DP_FWD(VPL, W)                                                                                                  \
+  if (int rc = dp_ln_fwd_launch<T, VPL, W>((const T*)res, (const T*)y, ybias, scale, gamma, beta, (T*)s_out, (T*)h_out,   \
+                                           mean, rstd, rows, rows_per_sample, cols, eps, blocks, (hipStream_t)stream))    \
+  return rc
+  LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, DP_FWD));
+#undef DP_FWD
+  LVL_CHECK_LAUNCH("droppath_add_layernorm_fwd");
+  return LVL_OK;
+}
+
+extern "C" int lvl_droppath_add_layernorm_bwd(const void* dh, const void* s, const float* gamma, const float* mean,
+                                              const float* rstd, const float* scale, const void* dadd, void* ds,
+                                              void* dy, float* dgamma, float* dbeta, float* dysum, float* ws,
+                                              int64_t rows, int64_t rows_per_sample, int cols, int dtype, void* stream) {
+  LVL_REQUIRE((rows == 0 || (scale && dy)) && dgamma && dbeta && ws, "droppath_add_layernorm_bwd: null pointer");
+  LVL_REQUIRE(rows >= 0 && rows_per_sample > 0 && rows % rows_per_sample == 0,
+              "droppath_add_layernorm_bwd: rows=%lld must be a multiple of rows_per_sample=%lld", (long long)rows,
+              (long long)rows_per_sample);
+  LVL_REQUIRE(rows < ((int64_t)1 << 32), "droppath_add_layernorm_bwd: rows=%lld must be below 2^32", (long long)rows);
+  LVL_REQUIRE((rows == 0 || (dh && s && mean && rstd && ds)) && gamma, "droppath_add_layernorm_bwd: null pointer");
+  LVL_REQUIRE(cols > 0 && cols % 8 == 0 && cols <= 4096,
+              "droppath_add_layernorm_bwd: cols=%d must be a multiple of 8, <= 4096", cols);
+  LVL_REQUIRE(lvl_aligned16(dh) && lvl_aligned16(s) && lvl_aligned16(dadd) && lvl_aligned16(ds) && lvl_aligned16(dy) &&
+                  lvl_aligned16(gamma),
+              "droppath_add_layernorm_bwd: pointers must be 16-byte aligned");
+  {
+    // the fused form: lvl_layernorm_bwd's exact-width kernel on its grid, storing dy beside ds
+    int64_t nb = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+    if (nb > kLnBwdParts) nb = kLnBwdParts;
+    bool fused = false;
+#define DP_BWD(VPL, W)                                                                                                    \
+  if (int rc = dadd ? dp_bwd_fused_launch<T, VPL, W, true>((const T*)dh, (const T*)s, gamma, mean, rstd, scale,            \
+                                                           (const T*)dadd, (T*)ds, (T*)dy, ws, rows, rows_per_sample,     \
+                                                           cols, nb, (hipStream_t)stream, &fused)                         \
+                    : dp_bwd_fused_launch<T, VPL, W, false>((const T*)dh, (const T*)s, gamma, mean, rstd, scale,           \
+                                                            (const T*)nullptr, (T*)ds, (T*)dy, ws, rows, rows_per_sample, \
+                                                            cols, nb, (hipStream_t)stream, &fused))                        \
+  return rc
+    LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, DP_BWD));
+#undef DP_BWD
+    if (fused) {
+      LVL_CHECK_LAUNCH("droppath_add_layernorm_bwd");
+      return lvl_launch_column_reduce(ws, (int)nb, 3 * cols, cols, ws + (size_t)kLnBwdParts * 3 * cols, dgamma, dbeta, dysum,
+                                      (hipStream_t)stream);
+    }
+  }
+  // the composed form: the one LayerNorm backward on the kept sum, then dy and its column sums
+  if (int rc = lvl_layernorm_bwd(dh, s, nullptr, nullptr, gamma, mean, rstd, dadd, ds, nullptr, dgamma, dbeta, nullptr, ws,
+                                 rows, cols, dtype, stream))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = ws + lvl_workspace_floats("layernorm_bwd", rows, cols);
+  int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  if (blocks > kDpDyParts) blocks = kDpDyParts;
+  if (blocks < 1) blocks = 1;
+#define DP_DY(VPL, W)                                                                                                  \
+  if (int rc = dp_dy_launch<T, VPL, W>((const T*)ds, scale, (T*)dy, part, rows, rows_per_sample, cols, blocks, st)) \
+  return rc
+  LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, DP_DY));
+#undef DP_DY
+  LVL_CHECK_LAUNCH("droppath_add_layernorm_bwd");
+  if (dysum == nullptr) return LVL_OK;
+  return lvl_launch_column_reduce(part, (int)blocks, cols, cols, part + (size_t)kDpDyParts * cols, dysum, nullptr, nullptr,
+                                  st);
 }

@@ -4,7 +4,8 @@
 swallowed exactly as the reference's **kwargs do), output dict keys and state_dict keys, so that
 main_pretrain.py / eval_zeroshot.py drive it unchanged. Built: the dual-encoder pretraining path
 and the narrator on TimeSformer towers (`VCLM_OPENAI_TIMESFORMER_*`, :887-1198; lavila_amd.narrator +
-lavila_amd.gpt2_gated). The per-frame ViT narrators (`VCLM_OPENAI_VIT*`), DistilBERT and fine-tuning heads are absent.
+lavila_amd.gpt2_gated) and the classification fine-tune's `VideoClassifier` / `VideoClassifierMultiHead` (:24-72). The
+per-frame ViT narrators (`VCLM_OPENAI_VIT*`) and DistilBERT are absent.
 """
 import contextlib
 import os
@@ -44,6 +45,114 @@ def _half_out(x, *given):
             any(g.dtype == torch.float16 for g in given):
         return x.to(torch.float16)
     return x
+
+
+_HEAD_TILE = 256          # lvl_linear_tn tiles its output columns in 256s
+
+
+def _pad_to(t, dim, multiple):
+    """Zero rows / columns up to a multiple (exact in every GEMM that reads them); part of the autograd graph."""
+    n = -t.shape[dim] % multiple
+    return t if n == 0 else F.pad(t, (0, n) if dim == t.dim() - 1 else (0, 0, 0, n))
+
+
+class _ClassifierHeadFn(torch.autograd.Function):
+    """logits = x W^T + b for a classification head W [classes, D] on bf16 features x [B, D]. The class counts of the
+    fine-tune (97 / 300 / 3806) do not tile the GEMMs: the class rows are padded with zeros to lvl_linear_tn's 256-column
+    tiles for the forward, the input-gradient and the weight-gradient GEMM (as the narrator's lm_head pads its vocabulary),
+    and the padded columns / rows are dropped again. The padded bf16 images are cast per forward from the current
+    parameter: nothing cached, nothing stale. Widths that are no multiple of 256 get the input gradient through zero rows
+    of the transposed weight in the same way."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        n, D = weight.shape
+        rows = x.shape[0]
+        w = _pad_to(weight.detach().to(torch.bfloat16), 0, _HEAD_TILE)
+        wt = _pad_to(w.t(), 0, _HEAD_TILE).contiguous()                   # [D padded, classes padded]
+        b = None if bias is None else _pad_to(bias.detach().float(), 0, _HEAD_TILE)
+        ctx.own = ops._tn_ok(rows, w.shape[0], D) and ops._tn_ok(rows, wt.shape[0], wt.shape[1])
+        x = x if x.is_contiguous() else x.contiguous()
+        ctx.save_for_backward(x, wt)
+        ctx.meta = (n, D, weight.dtype, None if bias is None else bias.dtype)
+        if ctx.own:
+            return ops.linear_tn_raw(x, w, b, ops.C.EPI_BIAS)[:, :n]
+        ops.warn_once(('fc_cls', n, D), f'classifier head [{D}->{n}] on {rows} rows runs on the library GEMM')
+        with torch.autocast('cuda', enabled=False):
+            return F.linear(x, w[:n], None if b is None else b[:n].to(x.dtype))
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, wt = ctx.saved_tensors
+        n, D, wdt, bdt = ctx.meta
+        dl = torch.zeros(x.shape[0], wt.shape[1], dtype=torch.bfloat16, device=x.device)
+        dl[:, :n] = dlogits
+        dx = dw = db = None
+        with torch.autocast('cuda', enabled=False):
+            if ctx.needs_input_grad[0]:
+                dx = (ops.linear_tn_raw(dl, wt, None, ops.C.EPI_BIAS) if ctx.own else dl @ wt.t())[:, :D]
+            if ctx.needs_input_grad[1]:
+                dw = ops._wgrad(dl, x, wdt)[:n]
+            if bdt is not None and ctx.needs_input_grad[2]:
+                db = dlogits.sum(0, dtype=torch.float32).to(bdt)
+        return dx, dw, db
+
+
+def _classifier_head(x, fc):
+    """fc(x) for an nn.Linear head on [B, D] features: the padded own GEMMs in bf16, ops.linear otherwise (float32)."""
+    x = ops._act(x)
+    if x.dtype == torch.bfloat16 and x.is_cuda and x.dim() == 2 and fc.weight.shape[1] % 64 == 0:
+        return _ClassifierHeadFn.apply(x, fc.weight, fc.bias)
+    return ops.linear(x, fc.weight, fc.bias)
+
+
+def _features(visual, image, use_checkpoint):
+    if not image.is_cuda:
+        ops.C.require_device(image)              # raises HipExtensionError: there is no CPU path
+    image_embed = visual(image, use_checkpoint=use_checkpoint)
+    if isinstance(image_embed, list):
+        assert len(image_embed) == 1
+        image_embed = image_embed[0]
+    return image_embed
+
+
+class VideoClassifier(nn.Module):
+    """models.py:24-45: `fc_cls(dropout(visual(image)))`, the single-head model of main_finetune_classification.py (EGTEA,
+    EK-100 actions). Same attribute / parameter names and initialisation; fp16 parameters or input give fp16 logits."""
+
+    def __init__(self, vision_model: nn.Module, dropout: float, num_classes: int, **kwargs):
+        super().__init__()
+        self.visual = vision_model
+        self.dropout = nn.Dropout(dropout)
+        self.fc_cls = nn.Linear(vision_model.num_features, num_classes, bias=True)
+        self.fc_cls.weight.data.normal_(mean=0.0, std=0.01)
+        self.fc_cls.bias.data.zero_()
+
+    def forward(self, image, use_checkpoint=False):
+        with ops.model_forward(), _amp_region():
+            image_embed = _features(self.visual, image, use_checkpoint)
+            logit = _classifier_head(self.dropout(image_embed), self.fc_cls)
+            return _half_out(logit, image, self.fc_cls.weight)
+
+
+class VideoClassifierMultiHead(nn.Module):
+    """models.py:48-72: one head per label set (EK-100 verbs / nouns / actions) on one feature vector; returns the list of
+    logits. Every head draws its own dropout mask, in head order, as the reference's list comprehension does."""
+
+    def __init__(self, vision_model: nn.Module, dropout: float, num_classes_list: list, **kwargs):
+        super().__init__()
+        self.visual = vision_model
+        self.dropout = nn.Dropout(dropout)
+        self.fc_cls = nn.ModuleList(
+            [nn.Linear(vision_model.num_features, num_classes, bias=True) for num_classes in num_classes_list])
+        for m in self.fc_cls:
+            m.weight.data.normal_(mean=0.0, std=0.01)
+            m.bias.data.zero_()
+
+    def forward(self, image, use_checkpoint=False):
+        with ops.model_forward(), _amp_region():
+            image_embed = _features(self.visual, image, use_checkpoint)
+            return [_half_out(_classifier_head(self.dropout(image_embed), m), image, m.weight) for m in self.fc_cls]
 
 
 _TEXT_STREAM = os.environ.get('LAVILA_TEXT_STREAM', '1') != '0'

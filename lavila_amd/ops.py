@@ -1050,6 +1050,82 @@ def add_layer_norm(res, y, ybias, weight, bias, eps, keep_sum=True, recipe=False
 
 
 # --------------------------------------------------------------------------------------------------
+# Stochastic depth: per-sample scaled residual add + LayerNorm
+# --------------------------------------------------------------------------------------------------
+def droppath_add_layernorm_fwd_raw(res, y, ybias, scale, rows_per_sample, gamma, beta, eps):
+    """One lvl_droppath_add_layernorm_fwd call: (h, s, mean, rstd) with s = res + scale[sample] * (y + ybias)."""
+    C.require_device(res, y, ybias, scale, gamma, beta)
+    rows, cols = _rows_cols(res)
+    s, h = torch.empty_like(res), torch.empty_like(res)
+    mean = torch.empty(rows, dtype=torch.float32, device=res.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+    C.check(C.lib().lvl_droppath_add_layernorm_fwd(C.ptr(res), C.ptr(y), C.ptr(ybias), C.ptr(scale), C.ptr(gamma),
+                                                   C.ptr(beta), C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows,
+                                                   int(rows_per_sample), cols, float(eps), C.dtype_code(res),
+                                                   C.stream_ptr()), 'lvl_droppath_add_layernorm_fwd')
+    return h, s, mean, rstd
+
+
+def droppath_add_layernorm_bwd_raw(dh, s, gamma, mean, rstd, scale, dadd, rows_per_sample, want_dysum):
+    """One lvl_droppath_add_layernorm_bwd call: (ds, dy, dgamma, dbeta, dysum)."""
+    C.require_device(dh, s, gamma, mean, rstd, scale, dadd)
+    rows, cols = _rows_cols(s)
+    ds, dy = torch.empty_like(s), torch.empty_like(s)
+    dgamma = torch.empty(cols, dtype=torch.float32, device=s.device)
+    dbeta = torch.empty(cols, dtype=torch.float32, device=s.device)
+    dysum = torch.empty(cols, dtype=torch.float32, device=s.device) if want_dysum else None
+    ws = C.workspace('droppath_add_layernorm_bwd', rows, cols, s.device)
+    C.check(C.lib().lvl_droppath_add_layernorm_bwd(C.ptr(dh), C.ptr(s), C.ptr(gamma), C.ptr(mean), C.ptr(rstd),
+                                                   C.ptr(scale), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma),
+                                                   C.ptr(dbeta), C.ptr(dysum), C.ptr(ws), rows, int(rows_per_sample),
+                                                   cols, C.dtype_code(s), C.stream_ptr()),
+            'lvl_droppath_add_layernorm_bwd')
+    return ds, dy, dgamma, dbeta, dysum
+
+
+class _ScaledAddLayerNormFn(torch.autograd.Function):
+    """(s, h) = (res + c_b * (y + ybias), LN(s)) with one c_b per sample (stochastic depth: timesformer.py:192,196 and the
+    LayerNorm that reads the sum). s is always kept: the backward runs on it. d scale is None (the mask is a constant)."""
+
+    @staticmethod
+    def forward(ctx, res, y, ybias, scale, rows_per_sample, weight, bias, eps, ytoken=None):
+        res, y = res.contiguous(), y.contiguous()
+        yb, g, b, c = _f32(ybias), _f32(weight), _f32(bias), _f32(scale)
+        h, s, mean, rstd = droppath_add_layernorm_fwd_raw(res, y, yb, c, rows_per_sample, g, b, eps)
+        ctx.save_for_backward(s, g, mean, rstd, c)
+        ctx.rps = int(rows_per_sample)
+        ctx.has_ybias = ybias is not None
+        ctx.has_token = ytoken is not None
+        ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
+        ctx.set_materialize_grads(False)        # an unused s (the final norm) or h (a closing add) arrives as None
+        return s, h
+
+    @staticmethod
+    def backward(ctx, ds, dh):
+        s, g, mean, rstd, c = ctx.saved_tensors
+        if ds is None and dh is None:
+            return (None,) * 9
+        want_tok = ctx.has_token and ctx.needs_input_grad[8]
+        dh = torch.zeros_like(s) if dh is None else dh.contiguous()
+        dres, dy, dg, db, dysum = droppath_add_layernorm_bwd_raw(dh, s, g, mean, rstd, c,
+                                                                 None if ds is None else ds.contiguous(),
+                                                                 ctx.rps, ctx.has_ybias or want_tok)
+        dyb = dysum.to(ctx.pdt[2]) if ctx.has_ybias else None
+        return dres, dy, dyb, None, None, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, (dysum if want_tok else None)
+
+
+def scaled_add_layer_norm(res, y, ybias, scale, rows_per_sample, weight, bias, eps, ytoken=None):
+    """Returns (s, h) with s = res + scale[sample] * (y (+ ybias)) and h = LayerNorm(s); rows r of the flattened res belong
+    to sample r // rows_per_sample and scale is one float32 per sample (DropPath.sample_scale: 0 or 1 / keep).
+    ytoken: the column-sum token of y (see COLSUM_TOKENS); without one the producer of y reduces its gradient itself."""
+    res = lowp(res)
+    if y.dtype != res.dtype:
+        y, ytoken = y.to(res.dtype), None
+    s, h = _ScaledAddLayerNormFn.apply(res, y, ybias, scale, rows_per_sample, weight, bias, eps, ytoken)
+    return s, _narrow(h)
+
+
+# --------------------------------------------------------------------------------------------------
 # bias + QuickGELU
 # --------------------------------------------------------------------------------------------------
 class _BiasQuickGELUFn(torch.autograd.Function):

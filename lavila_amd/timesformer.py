@@ -72,6 +72,13 @@ class DropPath(nn.Module):
         super().__init__()
         self.drop_prob = float(drop_prob)
 
+    def sample_scale(self, batch, device):
+        """[batch] float32 of bernoulli(keep) / keep, drawn from the device generator (torch.manual_seed reproduces a run, no
+        host read-back): the per-sample factors of one stochastic-depth site, as lvl_droppath_add_layernorm_* take them. The
+        only place the fused residual chain draws a mask."""
+        keep = 1.0 - self.drop_prob
+        return torch.empty(batch, dtype=torch.float32, device=device).bernoulli_(keep).div_(keep)
+
     def forward(self, x):
         if self.drop_prob == 0.0 or not self.training:
             return x
@@ -242,9 +249,28 @@ class PendingMlp:
         return ops.mlp_quickgelu(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, ln=self.ln)
 
 
+class ScaledBranch:
+    """A branch output that is still to be added as `res + scale[sample] * (y + bias)`: the MLP branch of a block with
+    stochastic depth (timesformer.py:196). Travels in the `pend` slot of the fused residual chain like a tensor; whoever
+    closes the add (_close_pending, the final norm, SpaceTimeBlock.forward) does it with ops.scaled_add_layer_norm."""
+
+    __slots__ = ('y', 'scale')
+
+    def __init__(self, y, scale):
+        self.y, self.scale = y, scale       # scale: [B] float32 (DropPath.sample_scale)
+
+
+def _rows_per_sample(x):
+    return 1 if x.dim() == 2 else x.numel() // (x.shape[0] * x.shape[-1])
+
+
 def _close_pending(res, pend, pend_bias, norm, selective=False):
-    """(s, h) = (res + pend + pend_bias, norm(s)) for a tensor or a PendingMlp in the `pend` slot. selective: (s, h, recipe)
-    with the ops.LnRecipe of h, for the Linear that consumes h; a PendingMlp's own recipe travels with it."""
+    """(s, h) = (res + pend + pend_bias, norm(s)) for a tensor, a PendingMlp or a ScaledBranch in the `pend` slot. selective:
+    (s, h, recipe) with the ops.LnRecipe of h, for the Linear that consumes h; a PendingMlp's own recipe travels with it (a
+    scaled sum has no recipe: (s, h), and the Linear keeps h)."""
+    if isinstance(pend, ScaledBranch):
+        return ops.scaled_add_layer_norm(res, pend.y, pend_bias, pend.scale, _rows_per_sample(res), norm.weight, norm.bias,
+                                         norm.eps)
     if isinstance(pend, PendingMlp):
         m = pend.mlp
         fused = ops.mlp_residual_layer_norm(pend.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, pend_bias, res, norm.weight,
@@ -288,10 +314,21 @@ class SpaceTimeBlock(nn.Module):
         self.attention_style = attention_style
 
     def _dropping(self):
-        """Stochastic depth or MLP dropout live in this training forward: the branches are then materialised (own
-        GEMMs, separate bias / drop passes) instead of riding on the fused chain (timesformer.py:52-58,192-196)."""
-        return self.training and ((isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0.) or
-                                  self.mlp.drop.p > 0.)
+        """MLP dropout lives in this training forward: the branches are then materialised (own GEMMs, separate bias / drop
+        passes) instead of riding on the fused chain (timesformer.py:52-58,192-196)."""
+        return self.training and self.mlp.drop.p > 0.
+
+    def _stochastic(self):
+        """Stochastic depth (and no MLP dropout) lives in this training forward: the block stays on the fused chain and its
+        two per-sample scaled adds run in the LayerNorm kernels that read them (ops.scaled_add_layer_norm)."""
+        return (self.training and isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0.
+                and not self._dropping())
+
+    def _mlp_branch(self, h2):
+        """fc2(act(fc1(h2))) without fc2's bias, which stays pending."""
+        if self.mlp._fused_act:
+            return ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight)
+        return ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight)
 
     def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False, selective=False):
         """One block on the fused residual chain.
@@ -302,10 +339,12 @@ class SpaceTimeBlock(nn.Module):
         selective (use_checkpoint='selective'): the same kernels in the same order, but norm3 / norm1 / norm2's outputs and
         the MLP hidden activation are not kept for backward: every LayerNorm hands out the recipe of its output
         (ops.LnRecipe) and the Linear that consumes the output keeps that instead. A block that is dropping (stochastic
-        depth, MLP dropout) runs its plain path."""
+        depth, MLP dropout) keeps every activation: with stochastic depth it runs the scaled adds below, with MLP
+        dropout its plain path."""
         if self.attention_style != 'frozen-in-time':
             raise NotImplementedError
-        sel = bool(selective) and not self._dropping()
+        stoch = self._stochastic()
+        sel = bool(selective) and not self._dropping() and not stoch
         n3, n1, n2 = self.norm3, self.norm1, self.norm2
         r3 = r1 = r2 = None
         if pend is None:
@@ -331,6 +370,16 @@ class SpaceTimeBlock(nn.Module):
         # norm1's backward kernel instead of a separate add
         x, h1, *r1 = ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y, recipe=sel)
         r1 = r1[0] if r1 else None
+        if stoch:
+            # x1 = x + c_space * (proj(o_s) + bias) inside norm2's kernel, the MLP branch left pending with its own scale: the
+            # time branch above carries no drop path in the reference (timesformer.py:183-196). Masks in the reference's order.
+            c_s = self.drop_path.sample_scale(x.shape[0], x.device)
+            c_m = self.drop_path.sample_scale(x.shape[0], x.device)
+            o_s = sa.core(h1, 'space', frames, n_per_frame)
+            del h1
+            x1, h2 = ops.scaled_add_layer_norm(x, ops.linear(o_s, sa.proj.weight), sa.proj.bias, c_s, _rows_per_sample(x),
+                                               n2.weight, n2.bias, n2.eps)
+            return x1, ScaledBranch(self._mlp_branch(h2), c_m), self.mlp.fc2.bias
         fused = None
         if not self._dropping():
             # ops.RESIDUAL_EPILOGUE: x1 leaves the projection GEMM (residual epilogue), norm2 reads it
@@ -391,6 +440,12 @@ class SpaceTimeBlock(nn.Module):
         q = ops.linear(h1[:, 0].contiguous(), w[:D], bq)                         # [B, D]
         o_cls = ops.cls_attention(q, kv, sa.num_heads, bias=bias)                # [B, D]
         y_s = ops.linear(o_cls, sa.proj.weight)                                  # [B, D]
+        if self._stochastic():
+            # the two scaled adds of `chain` on the cls rows: one row per sample
+            c_s = self.drop_path.sample_scale(x.shape[0], x.device)
+            c_m = self.drop_path.sample_scale(x.shape[0], x.device)
+            x1, h2 = ops.scaled_add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, c_s, 1, n2.weight, n2.bias, n2.eps)
+            return x1, ScaledBranch(self._mlp_branch(h2), c_m), self.mlp.fc2.bias
         x1, h2 = ops.add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, n2.weight, n2.bias, n2.eps, keep_sum=True)
         if self.mlp._fused_act:
             return x1, ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight), self.mlp.fc2.bias
@@ -401,13 +456,33 @@ class SpaceTimeBlock(nn.Module):
         """Reference signature (timesformer.py:173-174); materialises the block output."""
         frames, n = int(space_f), int(time_n)
         mode = _video_checkpoint_mode(use_checkpoint)
-        if mode == 'block':
+        if mode == 'block' and self._stochastic():
+            x1, y, b, c = checkpoint.checkpoint(_chain_flat, self.chain, x, None, None, None, frames, n, use_reentrant=False)
+            y = ScaledBranch(y, c)
+        elif mode == 'block':
             x1, y, b = checkpoint.checkpoint(self.chain, x, None, None, frames, n, use_reentrant=False)
         elif mode == 'selective':
             x1, y, b = self.chain(x, None, None, frames, n, selective=True)
         else:
             x1, y, b = self.chain(x, None, None, frames, n)
+        if isinstance(y, ScaledBranch):
+            # the closing add through the scaled kernel; nothing reads its normalised rows here
+            n3 = self.norm3
+            out = ops.scaled_add_layer_norm(x1, y.y, b, y.scale, _rows_per_sample(x1), n3.weight.detach(), n3.bias.detach(),
+                                            n3.eps)[0]
+            return _like_caller(out, x)
         return _like_caller(x1 + (y if b is None else y + b.to(y.dtype)), x)
+
+
+def _chain_flat(fn, res, pend, pend_b, pend_c, frames, n):
+    """`fn` (SpaceTimeBlock.chain / chain_cls) with a ScaledBranch taken apart into tensors on the way in and out: what
+    torch.utils.checkpoint carries across a block boundary. Returns (res, pend, pend_bias, pend_scale or None)."""
+    if pend_c is not None:
+        pend = ScaledBranch(pend, pend_c)
+    res, pend, pend_b = fn(res, pend, pend_b, frames, n)
+    if isinstance(pend, ScaledBranch):
+        return res, pend.y, pend_b, pend.scale
+    return res, pend, pend_b, None
 
 
 class SpaceTimeTransformer(nn.Module):
@@ -520,6 +595,9 @@ class SpaceTimeTransformer(nn.Module):
         res, pend, pend_b = x, None, None
         hook = after_block
         last = len(self.blocks) - 1
+        # with stochastic depth in the tower no MLP waits for the next block: block checkpointing closes every add in the
+        # composed form, and the two modes then run the same kernels (equal to the bit under one seed)
+        stochastic = any(blk._stochastic() for blk in self.blocks)
         for i, blk in enumerate(self.blocks):
             # the last block of a cls-pooled forward only has to produce its cls rows (SpaceTimeBlock.chain_cls)
             fn = blk.chain_cls if (cls_at_last and i == last and CLS_ONLY_LAST_BLOCK and not blk._dropping()
@@ -527,14 +605,21 @@ class SpaceTimeTransformer(nn.Module):
             if mode == 'block':
                 if isinstance(pend, PendingMlp):
                     pend = pend.materialize()
-                res, pend, pend_b = checkpoint.checkpoint(fn, res, pend, pend_b, frames, n, use_reentrant=False)
+                if isinstance(pend, ScaledBranch) or blk._stochastic():
+                    y, c = (pend.y, pend.scale) if isinstance(pend, ScaledBranch) else (pend, None)
+                    res, pend, pend_b, c = checkpoint.checkpoint(_chain_flat, fn, res, y, pend_b, c, frames, n,
+                                                                 use_reentrant=False)
+                    if c is not None:
+                        pend = ScaledBranch(pend, c)
+                else:
+                    res, pend, pend_b = checkpoint.checkpoint(fn, res, pend, pend_b, frames, n, use_reentrant=False)
             elif mode == 'selective':
                 # the plain step's kernels in the plain step's order; what is kept for backward differs (SpaceTimeBlock.chain)
                 if fn == blk.chain and i != last:
                     res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True, selective=True)
                 else:
                     res, pend, pend_b = fn(res, pend, pend_b, frames, n, selective=True)
-            elif fn == blk.chain and i != last:
+            elif fn == blk.chain and i != last and not stochastic:
                 # the block's MLP may wait for the next block's norm3 (ops.RESIDUAL_EPILOGUE: residual add in fc2's epilogue)
                 res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True)
             else:
@@ -547,12 +632,18 @@ class SpaceTimeTransformer(nn.Module):
             r0 = res if res.dim() == 2 else res[:, 0].contiguous()
             if pend is None:
                 out = ops.layer_norm(r0, nm.weight, nm.bias, nm.eps)
+            elif isinstance(pend, ScaledBranch):
+                p0 = pend.y if pend.y.dim() == 2 else pend.y[:, 0].contiguous()
+                out = ops.scaled_add_layer_norm(r0, p0, pend_b, pend.scale, 1, nm.weight, nm.bias, nm.eps)[1]
             else:
                 p0 = pend if pend.dim() == 2 else pend[:, 0].contiguous()
                 _, out = ops.add_layer_norm(r0, p0, pend_b, nm.weight, nm.bias, nm.eps, keep_sum=False)
             return self.pre_logits(out)
         if pend is None:
             return ops.layer_norm(res, nm.weight, nm.bias, nm.eps)
+        if isinstance(pend, ScaledBranch):
+            return ops.scaled_add_layer_norm(res, pend.y, pend_b, pend.scale, _rows_per_sample(res), nm.weight, nm.bias,
+                                             nm.eps)[1]
         return ops.add_layer_norm(res, pend, pend_b, nm.weight, nm.bias, nm.eps, keep_sum=False)[1]
 
     def forward_features(self, x, use_checkpoint=False, cls_at_last=True):
