@@ -100,7 +100,7 @@ def causal_layout(L):
 
 @dataclass
 class Problem:
-    kind: str                 # 'space' | 'time' | 'causal' | 'cls'
+    kind: str                 # 'space' | 'time' | 'causal' | 'cls' | 'cross' | 'mq'
     shape: tuple
     heads: int
     qkv: torch.Tensor         # [B, T, 3D] float64, bf16- and (q, k) e4m3-exact
@@ -121,6 +121,27 @@ class Problem:
         """cls-only operands: q [B, D] (token 0's q), kv [B, T, 2D]; reference out [B, D], dq [B, D], dkv [B, T, 2D]."""
         D = self.heads * 64
         return (self.qkv[:, 0, :D], self.qkv[:, :, D:], self.out[:, 0], self.dqkv[:, 0, :D], self.dqkv[:, :, D:])
+
+    def as_cross(self):
+        """'cross' operands in the C-ABI layout: q [contexts*qrep, D], kv [contexts, Tk, 2D], dout [contexts*qrep, D];
+        reference out and dq [contexts*qrep, D], dkv [contexts, Tk, 2D]. Tokens 0..qrep-1 of a context are its query
+        rows, the Tk tokens behind them its keys."""
+        D = self.heads * 64
+        qrep = self.shape[1]
+        rows = lambda x: x[:, :qrep].reshape(-1, D)                       # noqa: E731
+        return (rows(self.qkv[..., :D]), self.qkv[:, qrep:, D:], rows(self.dout), rows(self.out),
+                rows(self.dqkv[..., :D]), self.dqkv[:, qrep:, D:])
+
+    def as_mq(self):
+        """'mq' operands of the pooler: q [B, NQ, H*64] (shared: [NQ, H*64], the same rows in every clip),
+        kv [B, Tk, 128], dout [B, NQ, H*64]; reference out [B, NQ, H*64], dq like q (shared: the sum over the clips),
+        dkv [B, Tk, 128]. Query token n*H + h of the single-head problem is head h of query n."""
+        B, NQ, H, Tk, shared = self.shape
+        fold = lambda x: x[:, :NQ * H].reshape(B, NQ, H * 64)            # noqa: E731
+        q, dq = fold(self.qkv[..., :64]), fold(self.dqkv[..., :64])
+        if shared:
+            q, dq = q[0], dq.sum(0)
+        return q, self.qkv[:, NQ * H:, 64:], fold(self.dout), fold(self.out), dq, self.dqkv[:, NQ * H:, 64:]
 
 
 def _bf16_exact(x):
@@ -174,18 +195,25 @@ def _reference(q, k, v, dO, blocks):
     return out, lse, dq, dk, dv, (nq_, nk_, nv_, no_), probs
 
 
-def _build(kind, shape, B, H, T, blocks, tok_class, tok_rank, class_size, class_groups, seed, group_slots=None):
+def _build(kind, shape, B, H, T, blocks, tok_class, tok_rank, class_size, class_groups, seed, group_slots=None,
+           shared_q=False):
     """tok_class / tok_rank [T]: tie class and rank of every token (class sizes are group-local for divided attention;
-    class 0 is the cls class there). Queries pick their target class in _targets; everything else follows here."""
+    class 0 is the cls class there). Queries pick their target class in _targets; everything else follows here.
+    shared_q: every sample uses the codes and targets of sample 0, so q is the same tensor in all of them (v, the
+    private offsets and dout still differ)."""
     g = torch.Generator().manual_seed(seed)
     C = int(class_size.numel())
     codes = _codes()
     assert C <= codes.shape[0], f'{C} tie classes need more than {codes.shape[0]} codes'
     # per (b, h): a random code per class, a random v dim per class, random offset dims
     code_of = torch.argsort(torch.rand(B, H, codes.shape[0], generator=g), -1)[..., :C]          # [B,H,C]
+    if shared_q:
+        code_of = code_of[:1].expand(B, H, C)
     ab = codes[code_of]                                                                          # [B,H,C,2]
     vdim = torch.randint(0, 64, (B, H, C), generator=g)
     target = _targets(kind, B, H, T, blocks, tok_class, class_size, class_groups, g)             # [B,H,T]
+    if shared_q:
+        target = target[:1].expand(B, H, T).contiguous()
 
     def code_vec(cab, val):
         x = torch.zeros(*cab.shape[:-1], 64, dtype=torch.float64)
@@ -271,6 +299,17 @@ def _targets(kind, B, H, T, blocks, tok_class, class_size, class_groups, g):
                 t = tok_class[qidx].expand(B, H, G, nq)
             target[:, :, qidx.reshape(-1)] = t.reshape(B, H, -1)
         return target
+    if kind in ('cross', 'mq'):
+        # round-robin over the tied classes, from a start that differs per (b, h) -- (0, 0) starts at class 0, the one
+        # of the first and the last key: with at least as many queries as tied classes every tied key is some query's
+        # target, and a class collects at most ceil(queries / classes) queries
+        (qidx, _, _), = blocks
+        cand = torch.nonzero(tied).flatten()
+        if cand.numel():
+            start = torch.randint(0, cand.numel(), (B, H), generator=g)
+            start[0, 0] = 0
+            target[:, :, qidx[0]] = cand[(torch.arange(qidx.shape[1]) + start[..., None]) % cand.numel()]
+        return target
     # causal: count of each class visible to query t
     C = class_size.numel()
     vis = torch.zeros(T, C, dtype=torch.long)
@@ -317,6 +356,17 @@ def _check(p, probs, rows_q):
     assert not tied_q.any() or dq_nz[tied_q].double().mean().item() >= 0.9, \
         'fewer than 90 % of the tied query rows have dq != 0'
     tied_k = p.key_tied[None, :, None].expand_as(dk[..., 0])
+    if p.kind in ('cross', 'mq'):
+        # fewer queries than tied classes (5 rows over 256 keys) leave classes that no softmax of this (b, h) ties: the
+        # tied keys are those some query gives 1/2 or 1/4 -- all of key_tied once the queries go round
+        (qidx, kidx, _), = p.blocks
+        hit = ((probs[0] > 0) & (probs[0] < 1)).any(-2)[:, :, 0]                                   # [B, H, nk]
+        tied_k = torch.zeros_like(tied_k)
+        tied_k[:, kidx[0]] = hit.permute(0, 2, 1)
+        assert bool((tied_k <= p.key_tied[None, :, None]).all())
+        if qidx.shape[1] >= p.tok_class[p.key_tied].unique().numel():
+            assert torch.equal(tied_k, p.key_tied[None, :, None].expand_as(tied_k)), 'a tied key is no query\'s target'
+        assert not p.key_tied.any() or bool(tied_k.any(1).all()), 'a (b, h) without a tied key'
     dk_nz = (dk != 0).any(-1)
     if p.kind != 'cls':
         assert dk_nz[tied_k].double().mean().item() >= 0.9, 'fewer than 90 % of the tied keys have dk != 0'
@@ -367,6 +417,45 @@ def cls_problem(B, T, H, seed=0):
     blocks = [(torch.zeros(1, 1, dtype=torch.long), torch.arange(T)[None], False)]
     return _build('cls', (B, T, H), B, H, T, blocks, cls, rank, size, None, seed)
 
+
+def _query_key_problem(kind, shape, B, H, nq, Tk, seed, shared_q=False):
+    """nq query tokens (0..nq-1, one untied class of their own that is no key) over Tk key tokens laid out by
+    group_layout(Tk): partners mirrored around the middle, so they straddle every 16- and 64-key boundary."""
+    lcls, lrank, lsize = group_layout(Tk)
+    tok_class = torch.cat([torch.full((nq,), lsize.numel()), lcls])
+    tok_rank = torch.cat([torch.zeros(nq, dtype=torch.long), lrank])
+    class_size = torch.cat([lsize, torch.ones(1, dtype=torch.long)])
+    blocks = [(torch.arange(nq)[None], nq + torch.arange(Tk)[None], False)]
+    return _build(kind, shape, B, H, nq + Tk, blocks, tok_class, tok_rank, class_size, None, seed, shared_q=shared_q)
+
+
+def cross_problem(contexts, qrep, H, Tk, seed=0):
+    """Decoder cross-attention: qrep query rows per context over that context's Tk keys (Problem.as_cross())."""
+    return _query_key_problem('cross', (contexts, qrep, H, Tk), contexts, H, qrep, Tk, seed)
+
+
+def mq_problem(B, NQ, H, Tk, shared, seed=0):
+    """The pooler: ONE 64-channel key / value head for all H query heads -- a single-head problem with NQ * H queries
+    per clip (Problem.as_mq()). shared: one [NQ, H*64] query tensor for every clip; its reference dq is the sum over the
+    clips, which must meet the same preconditions as every other reference value."""
+    p = _query_key_problem('mq', (B, NQ, H, Tk, bool(shared)), B, 1, NQ * H, Tk, seed, shared_q=bool(shared))
+    if shared:
+        nq = NQ * H
+        q = p.qkv[:, :nq, :64]
+        assert torch.equal(q, q[:1].expand_as(q)), 'shared queries differ between the clips'
+        dq, nb = p.dqkv[:, :nq, :64].sum(0), p.noise[:, :nq, :64].sum(0)
+        assert _bf16_exact(dq), 'the summed dq is not bf16-exact'
+        nz = dq != 0
+        if bool(nz.any()):
+            assert dq[nz].abs().min().item() >= MIN_QUANTUM
+            assert bool((nb[nz] <= _ulp_bf16(dq[nz]) / 4).all()), 'summed dq: P noise reaches a quarter bf16 ulp'
+        assert nb[~nz].numel() == 0 or nb[~nz].max().item() <= ZERO_SLACK / 4
+        tied_q = p.mult[:, 0, :nq].max(0).values > 1
+        assert not tied_q.any() or nz.any(-1)[tied_q].double().mean().item() >= 0.9, \
+            'fewer than 90 % of the tied shared queries have a summed dq != 0'
+    return p
+
+
 # --------------------------------------------------------------------------------------------------------------------
 # the shapes of tests/test_gpu_attention_ties.py (one list per kernel family; the CPU suite builds every one of them)
 # --------------------------------------------------------------------------------------------------------------------
@@ -382,6 +471,16 @@ TIME_GENERIC = [(2, 6, 5, 3)]
 F32_GENERIC = [('space', (2, 2, 31, 1)), ('time', (2, 3, 7, 1))]
 CAUSAL = [(2, 5, 2), (3, 77, 8), (2, 130, 12), (2, 256, 2), (2, 272, 2)]    # (B, L, H)
 CLS = [(2, 1, 2), (2, 99, 2), (2, 785, 12), (2, 3137, 12)]                 # (B, T, H)
+# the shapes of tests/test_gpu_narrator_ties.py
+# (contexts, qrep, H, Tk) of lvl_cross_attn_rows_fwd, one per dispatch branch and tail
+CROSS_FWD_BF16 = [(2, 2, 1, 2), (2, 16, 2, 16), (2, 17, 1, 33), (1, 65, 2, 255), (2, 5, 3, 256),    # MFMA kernel
+                  (2, 4, 2, 300), (1, 2, 1, 600),           # keys of a context in LDS, 257..600 of them
+                  (2, 3, 2, 601), (3, 1, 2, 37)]            # one workgroup per row: past LDS with qrep >= 2, qrep = 1
+CROSS_FWD_F32 = [(2, 5, 2, 37), (1, 2, 1, 300), (2, 3, 1, 301), (3, 1, 2, 37)]
+# lvl_cross_attn_rows_bwd: the MFMA shapes of the forward, three rounds with 2 rows in the last, twelve heads at 256 keys
+CROSS_BWD = [s for s in CROSS_FWD_BF16 if s[3] <= 256 and s[1] >= 2] + [(1, 130, 1, 200), (2, 64, 12, 256)]
+MQ = [(2, 5, 3, 9), (2, 24, 4, 65), (1, 11, 3, 33), (2, 32, 8, 128)]         # (B, NQ, H, Tk), shared and per-sample
+DECODE = [(2, 5, 2, 5), (3, 77, 8, 77), (2, 130, 2, 160)]                      # (B, L, H, cache capacity)
 
 
 def all_cases():
@@ -393,10 +492,22 @@ def all_cases():
             [('causal', s) for s in CAUSAL] + [('cls', s) for s in CLS])
 
 
+def narrator_cases():
+    """(kind, shape) of every problem tests/test_gpu_narrator_ties.py builds."""
+    cross = dict.fromkeys(CROSS_FWD_BF16 + CROSS_FWD_F32 + CROSS_BWD)
+    causal = [s[:3] for s in DECODE if s[:3] not in CAUSAL]
+    return ([('cross', s) for s in cross] + [('mq', s + (sh,)) for s in MQ for sh in (False, True)] +
+            [('causal', s) for s in causal])
+
+
 def make(kind, shape, seed=0):
     if kind in ('space', 'time'):
         B, F, N, H = shape
         return divided_problem(B, F, N, H, kind, seed)
     if kind == 'causal':
         return causal_problem(*shape, seed=seed)
+    if kind == 'cross':
+        return cross_problem(*shape, seed=seed)
+    if kind == 'mq':
+        return mq_problem(*shape, seed=seed)
     return cls_problem(*shape, seed=seed)

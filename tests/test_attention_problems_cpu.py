@@ -27,9 +27,36 @@ def _oracle(p):
     return out.detach(), x.grad
 
 
-@pytest.mark.parametrize('kind,shape', AP.all_cases(), ids=lambda v: str(v).replace(' ', ''))
+CASES = AP.all_cases() + AP.narrator_cases()
+
+
+def _cross_or_mq_oracle(p):
+    """The narrator's two query / key kinds through their own accessors (the C-ABI layouts) and the oracle's cores:
+    (out, dq, dkv) of the oracle and of the builder."""
+    if p.kind == 'cross':
+        contexts, qrep, H, Tk = p.shape
+        D = 64 * H
+        q, kv, dout, out, dq, dkv = p.as_cross()
+        qo, kvo = q.clone().requires_grad_(True), kv.clone().requires_grad_(True)
+        oo = O.gpt2_attention_core(qo.reshape(contexts, qrep, D), kvo[..., :D], kvo[..., D:], H, causal=False)
+        oo.backward(dout.reshape(contexts, qrep, D))
+        return (oo.detach().reshape(-1, D), qo.grad, kvo.grad), (out, dq, dkv)
+    B, NQ, H, Tk, shared = p.shape
+    q, kv, dout, out, dq, dkv = p.as_mq()
+    qo, kvo = q.clone().requires_grad_(True), kv.clone().requires_grad_(True)
+    oo = O.mq_cross_attention_core(qo[None].expand(B, -1, -1) if shared else qo, kvo, H)
+    oo.backward(dout)
+    return (oo.detach(), qo.grad, kvo.grad), (out, dq, dkv)
+
+
+@pytest.mark.parametrize('kind,shape', CASES, ids=lambda v: str(v).replace(' ', ''))
 def test_builder_matches_the_oracle(kind, shape):
     p = AP.make(kind, shape)
+    if kind in ('cross', 'mq'):
+        got, want = _cross_or_mq_oracle(p)
+        assert (got[0] - want[0]).abs().max().item() < 1e-12
+        assert (got[1] - want[1]).abs().max().item() < 1e-9 and (got[2] - want[2]).abs().max().item() < 1e-9
+        return
     out, grad = _oracle(p)
     want_out = p.out[:, 0] if kind == 'cls' else p.out
     # the oracle keeps the exp(-480) residue the builder flushes: agreement to far below the 2^-6 quantum
@@ -39,7 +66,7 @@ def test_builder_matches_the_oracle(kind, shape):
     assert torch.equal(p.dbias[D:2 * D], torch.zeros(D, dtype=torch.float64))
 
 
-@pytest.mark.parametrize('kind,shape', AP.all_cases(), ids=lambda v: str(v).replace(' ', ''))
+@pytest.mark.parametrize('kind,shape', CASES, ids=lambda v: str(v).replace(' ', ''))
 def test_builder_preconditions(kind, shape):
     """What the builder asserts, spelled out once more on the returned problem (a builder whose _check went soft would
     fail here)."""
@@ -61,6 +88,43 @@ def test_builder_preconditions(kind, shape):
         assert (dk != 0).any(-1)[tied].double().mean().item() >= 0.9
         tied_q = p.mult.permute(0, 2, 1) > 1
         assert (dq != 0).any(-1)[tied_q].double().mean().item() >= 0.9
+    if kind in ('cross', 'mq'):
+        _check_query_key_problem(p)
+
+
+def _check_query_key_problem(p):
+    """'cross' / 'mq' through the accessors the GPU tests use: every reference tensor bf16-exact and at least 2^-6 where
+    nonzero; at least 90 % of the tied rows have dq != 0; the keys that some query of their (context, head) ties are
+    exactly the members of whole tie classes, at least 90 % of them have dk != 0 and no other key has; once there are
+    as many queries as tied classes, that is every tied key of the layout, the last key among them."""
+    nq, Tk = (p.shape[1], p.shape[3]) if p.kind == 'cross' else (p.shape[1] * p.shape[2], p.shape[3])
+    H, B = p.heads, p.qkv.shape[0]
+    q, kv, dout, out, dq, dkv = p.as_cross() if p.kind == 'cross' else p.as_mq()
+    for x in (q, kv, dout, out, dq, dkv):
+        assert torch.equal(x.to(torch.bfloat16).double(), x)
+        assert x[x != 0].numel() == 0 or x[x != 0].abs().min().item() >= 2.0 ** -6
+    cls, _, size = AP.group_layout(Tk)
+    tied_cls = (size == 2) | (size == 4)
+    target = torch.full((B, H, len(size) + 1), False)
+    # the class a query targets is the class of the keys that share its code: read it back from q . k == 0
+    qh = p.qkv[:, :nq, :64 * H].reshape(B, nq, H, 64).permute(0, 2, 1, 3)
+    kh = p.qkv[:, nq:, 64 * H:128 * H].reshape(B, Tk, H, 64).permute(0, 2, 1, 3)
+    hit = (qh @ kh.transpose(-1, -2)) == 0                                            # [B, H, nq, Tk]
+    assert bool((hit.sum(-1) == size[cls][hit.int().argmax(-1)]).all()), 'a query scores 0 on part of a class'
+    tied_k = (hit & tied_cls[cls]).any(2)                                             # [B, H, Tk]
+    if nq >= int(tied_cls.sum()):
+        assert bool((tied_k == tied_cls[cls]).all())
+    if Tk >= 2:
+        assert bool(tied_k[0, 0, 0]) and bool(tied_k[0, 0, Tk - 1]), 'head (0, 0) must tie the first and the last key'
+    dk = p.dqkv[:, nq:, 64 * H:128 * H].reshape(B, Tk, H, 64).permute(0, 2, 1, 3)
+    dk_nz = (dk != 0).any(-1)
+    assert bool((dk_nz <= tied_k).all())
+    assert not tied_k.any() or dk_nz[tied_k].double().mean().item() >= 0.9
+    dqh = p.dqkv[:, :nq, :64 * H].reshape(B, nq, H, 64).permute(0, 2, 1, 3)
+    tied_q = p.mult[:, :, :nq] > 1
+    assert not tied_q.any() or (dqh != 0).any(-1)[tied_q].double().mean().item() >= 0.9
+    if p.kind == 'mq' and p.shape[4] and tied_q.any():
+        assert (dq.reshape(nq, 64) != 0).any(-1)[tied_q[0, 0]].double().mean().item() >= 0.9
 
 
 @pytest.mark.parametrize('kind,shape', [('space', (2, 4, 196, 12)), ('time', (1, 16, 196, 12)), ('time', (2, 5, 9, 4)),
@@ -113,6 +177,32 @@ def test_causal_tie_partners_cross_16_key_tiles(L):
         slots = torch.nonzero(cls == c).flatten()
         cross += int(slots.numel() > 1 and (slots // 16).unique().numel() > 1)
     assert cross >= 0.7 * size.numel()
+
+
+@pytest.mark.parametrize('Tk', [33, 65, 128, 200, 255, 256])
+def test_cross_tie_partners_straddle_the_key_tiles(Tk):
+    """Keys of a context / clip: the first and the last key share a class, and classes straddle the 16-key tiles of the
+    MFMA kernels, the 32-key grid of the pooler's backward and the 64 keys a wave owns in the decoder's backward."""
+    cls, size = _slot_classes(Tk)
+    assert int(size[cls[0]]) in (2, 4) and cls[0] == cls[Tk - 1]
+    lo = torch.full((size.numel(),), Tk).scatter_reduce(0, cls, torch.arange(Tk), 'amin')
+    hi = torch.full((size.numel(),), -1).scatter_reduce(0, cls, torch.arange(Tk), 'amax')
+    for tile in (16, 32, 64):
+        for b in range(tile, Tk, tile):
+            assert int(((lo < b) & (hi >= b)).sum()) >= min(b, Tk - b) // 2
+
+
+@pytest.mark.parametrize('B,L,H,cap', AP.DECODE)
+def test_decode_tie_partners_sit_in_different_key_slots(B, L, H, cap):
+    """lvl_decode_self_attn walks the cache with 32 key slots (key j in slot j % 32): the partners of causal_layout are 17
+    apart, so (almost) every tie is merged across slots, and past 32 keys a slot holds more than one key."""
+    cls, _, size = AP.causal_layout(L)
+    assert cap >= L
+    split = 0
+    for c in range(size.numel()):
+        slots = torch.nonzero(cls == c).flatten() % 32
+        split += int(slots.unique().numel() == slots.numel())
+    assert split == size.numel()
 
 
 def test_divided_problem_ties_the_cls_key_in_every_group():
