@@ -84,6 +84,30 @@ int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, const float
                       void* dx, void* dx_plain, float* dgamma, float* dbeta, float* dxsum, float* ws,
                       int64_t rows, int cols, int dtype, void* stream);
 
+/* ---- LayerNorm on the float32 residual stream under autocast: every operand in the dtype it has -------
+ * The two calls above on a float32 stream x (s_out, dadd, dx: float32) whose branch x2 and normalised rows are bf16:
+ * what `lvl_layernorm_fwd(LVL_F32)` on the widened branch followed by one rounding of y to bf16 gives, and what
+ * `lvl_layernorm_bwd(LVL_F32)` on the widened dy followed by one rounding of the branch gradient gives -- to the bit,
+ * without the widening and narrowing passes (the reference's AMP keeps the stream float32: timesformer.py:183-196,
+ * 353-366).
+ * forward:  x f32, x2 (nullable) bf16, xbias (nullable), gamma, beta f32; the row is x, += x2, += xbias in f32;
+ *   s_out (nullable) f32 receives it, y bf16 is the f32 result rounded once (nearest even); mean, rstd as above.
+ * backward: dy bf16, x f32, x2 (nullable) bf16, dadd (nullable) f32; dx f32 = the normalisation's input gradient
+ *   (+ dadd); dx2 (nullable) bf16 = dx rounded once, or with LVL_LN_PLAIN that gradient WITHOUT dadd rounded once
+ *   (dx_plain above; dxsum then sums that one). dgamma, dbeta, dxsum (nullable) sum the float32 values, over the same
+ *   partial slabs as lvl_layernorm_bwd: bit-equal to its LVL_F32 results. ws: lvl_workspace_floats("layernorm_bwd").
+ * flags: LVL_LN_GENERAL sends the call to the general kernel where an exact-width one exists (512, 768, 1024
+ *   columns; the two agree to the bit); LVL_LN_PLAIN (backward only, needs dx2) as above.
+ * cols, alignment and rows == 0 as lvl_layernorm_fwd / lvl_layernorm_bwd. */
+enum { LVL_LN_PLAIN = 1, LVL_LN_GENERAL = 2 };
+int lvl_layernorm_fwd_mixed(const float* x, const void* x2, const float* xbias, const float* gamma,
+                            const float* beta, float* s_out, void* y, float* mean, float* rstd,
+                            int64_t rows, int cols, float eps, int flags, void* stream);
+int lvl_layernorm_bwd_mixed(const void* dy, const float* x, const void* x2, const float* xbias,
+                            const float* gamma, const float* mean, const float* rstd, const float* dadd,
+                            float* dx, void* dx2, float* dgamma, float* dbeta, float* dxsum, float* ws,
+                            int64_t rows, int cols, int flags, void* stream);
+
 /* ---- Stochastic depth: per-sample scaled residual add + LayerNorm ------------------------------------
  * replaces `x = x + self.drop_path(branch)` followed by the next LayerNorm in SpaceTimeBlock.forward
  * (timesformer.py:192,196; timm's DropPath: branch * bernoulli(keep) / keep, one draw per sample).

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'liblavila_hip.so')
 LVL_F32, LVL_BF16 = 0, 1
 ATTN_SPACE, ATTN_TIME = 0, 1
 EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_QUICKGELU_BWD, EPI_BIAS_RESIDUAL, EPI_BIAS_QUICKGELU_DERIV, EPI_MUL_AUX_COLSUM = 0, 1, 2, 3, 4, 5
+LN_PLAIN, LN_GENERAL = 1, 2          # flags of lvl_layernorm_*_mixed
 ACT_GELU_NEW, ACT_SQRELU = 0, 1
 
 _c = ctypes
@@ -29,6 +30,8 @@ SIGNATURES = {
     'lvl_workspace_floats': (_L, [_c.c_char_p, _L, _L]),
     'lvl_layernorm_fwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P]),
     'lvl_layernorm_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
+    'lvl_layernorm_fwd_mixed': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P]),
+    'lvl_layernorm_bwd_mixed': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'lvl_droppath_add_layernorm_fwd': (_I, [_P] * 10 + [_L, _L, _I, _F, _I, _P]),
     'lvl_droppath_add_layernorm_bwd': (_I, [_P] * 13 + [_L, _L, _I, _I, _P]),
     'lvl_layernorm_apply': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),

@@ -49,10 +49,14 @@ __device__ __forceinline__ void ln_bwd_colsum_elem(float o, float& ax) { ax += E
 
 // X2: the row is x + x2 (compile time: the plain LayerNorm then carries no registers for the second operand's two rows in
 // flight -- 76 -> 64 VGPRs for 768 columns = 8 instead of 6 waves per SIMD, round 6)
-template <typename T, int VPL, int W, bool X2>
+// TB / TH (here and below): the element types of the branch x2 (and of its gradient) and of the normalised rows y (and of their
+// gradient dy) where they differ from the stream's T -- the mixed family (lvl_layernorm_*_mixed: float32 stream, bf16 branch,
+// bf16 normalised rows). Every operand is read and written in the type it has; the row arithmetic is the same f32 code.
+template <typename T, int VPL, int W, bool X2, typename TB = T>
 struct LnFwdRow {
-  RawVec<T, W> x[VPL], x2[X2 ? VPL : 1];
-  __device__ __forceinline__ void load(const T* __restrict__ px, const T* __restrict__ px2, int64_t row, int cols,
+  RawVec<T, W> x[VPL];
+  RawVec<TB, W> x2[X2 ? VPL : 1];
+  __device__ __forceinline__ void load(const T* __restrict__ px, const TB* __restrict__ px2, int64_t row, int cols,
                                        int lane, int nvec) {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -66,18 +70,18 @@ struct LnFwdRow {
 };
 
 // software-pipelined like the backward: the next row's packed operands are requested before this row is reduced
-template <typename T, int VPL, int W, bool X2>
+template <typename T, int VPL, int W, bool X2, typename TB = T, typename TH = T>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(
-    const T* __restrict__ x, const T* __restrict__ x2, const float* __restrict__ bias,
+    const T* __restrict__ x, const TB* __restrict__ x2, const float* __restrict__ bias,
     const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ s_out,
-    T* __restrict__ out, float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int cols,
+    TH* __restrict__ out, float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int cols,
     float eps) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nvec = cols / W;
   const float inv_cols = 1.0f / (float)cols;
   const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
   int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
-  LnFwdRow<T, VPL, W, X2> cur, nxt;
+  LnFwdRow<T, VPL, W, X2, TB> cur, nxt;
   if (row < rows) cur.load(x, x2, row, cols, lane, nvec);
   for (; row < rows; row += stride) {
     if (row + stride < rows) nxt.load(x, x2, row + stride, cols, lane, nvec);
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
         VecIO<float, W>::load(beta + c * W, b);
 #pragma unroll
         for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, g[j], b[j]);
-        VecIO<T, W>::store(out + row * cols + c * W, o);
+        VecIO<TH, W>::store(out + row * cols + c * W, o);
       }
     }
     if (lane == 0) {
@@ -140,19 +144,28 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(
   }
 }
 
-// EXACT-WIDTH forward (cols == VPL * 64 * W, no s_out; round 6): ln_fwd_kernel with NO conditional vector-memory instruction
-// in the row loop. Why it exists: the compiler's s_waitcnt insertion merges its counters conservatively over branches, and
+// EXACT-WIDTH forward (cols == VPL * 64 * W; s_out with SOUT only; round 6): ln_fwd_kernel with NO conditional vector-memory
+// instruction in the row loop. Why it exists: the compiler's s_waitcnt insertion merges its counters conservatively over branches, and
 // ln_fwd_kernel's per-chunk `c < nvec` / `row + stride < rows` / nullable-pointer branches
 // left the row loop with `s_waitcnt vmcnt(0)` in front of the reductions (the prefetched NEXT row was waited for too) and
 // behind each per-row reload of gamma / beta (three dependent L2 round trips per row). Here gamma, beta (and the optional
 // bias) live in registers, the prefetch is unconditional (the last rows re-read row `rows - 1`), mean / rstd are stored by every
 // lane (one address), and every wait the compiler places is a counted one: the next row's loads and this row's stores stay in
 // flight across the reductions.
-template <typename T, int VPL, int W, bool X2, bool BIAS>
-__global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
-    const T* __restrict__ x, const T* __restrict__ x2, const float* __restrict__ bias,
-    const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ out, float* __restrict__ mean,
-    float* __restrict__ rstd, int64_t rows, float eps) {
+// The mixed forms are held to the waves per SIMD of the float32 instantiation they replace (the compiler's report, DESIGN.md
+// section 4: the float32 exact forward without s_out, ln_fwd_kernel<float> with it); left alone the branch's unpacking costs
+// the forms with a branch and no bias a wave or two. 1 = no demand, as for every same-type instantiation.
+template <typename T, typename TB, int VPL, int W, bool X2, bool BIAS, bool SOUT>
+constexpr int ln_fwd_exact_waves() {
+  if (sizeof(T) == sizeof(TB) || W != 4 || !X2 || SOUT) return 1;
+  return BIAS ? 1 : VPL == 4 ? 6 : 8;
+}
+
+template <typename T, int VPL, int W, bool X2, bool BIAS, typename TB = T, typename TH = T, bool SOUT = false>
+__global__ __launch_bounds__(256, (ln_fwd_exact_waves<T, TB, VPL, W, X2, BIAS, SOUT>())) void ln_fwd_exact_kernel(
+    const T* __restrict__ x, const TB* __restrict__ x2, const float* __restrict__ bias,
+    const float* __restrict__ gamma, const float* __restrict__ beta, TH* __restrict__ out, float* __restrict__ mean,
+    float* __restrict__ rstd, int64_t rows, float eps, T* __restrict__ s_out) {
   constexpr int cols = VPL * 64 * W;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float inv_cols = 1.0f / (float)cols;
@@ -166,8 +179,9 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
     VecIO<float, W>::load(beta + (lane + i * 64) * W, b[i]);
     if constexpr (BIAS) VecIO<float, W>::load(bias + (lane + i * 64) * W, bb[i]);
   }
-  RawVec<T, W> cur[VPL], cur2[X2 ? VPL : 1], nxt[VPL], nxt2[X2 ? VPL : 1];
-  auto load_row = [&](int64_t r, RawVec<T, W> (&a)[VPL], RawVec<T, W> (&a2)[X2 ? VPL : 1]) {
+  RawVec<T, W> cur[VPL], nxt[VPL];
+  RawVec<TB, W> cur2[X2 ? VPL : 1], nxt2[X2 ? VPL : 1];
+  auto load_row = [&](int64_t r, RawVec<T, W> (&a)[VPL], RawVec<TB, W> (&a2)[X2 ? VPL : 1]) {
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       a[i].load(x + r * cols + (lane + i * 64) * W);
@@ -204,6 +218,11 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
 #pragma unroll
         for (int j = 0; j < W; ++j) v[i][j] += bb[i][j];
       }
+      if constexpr (SOUT) {          // as ln_fwd_kernel: the sum is stored, and normalised as stored
+        VecIO<T, W>::store(s_out + row * cols + (lane + i * 64) * W, v[i]);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[i][j] = Elem<T>::round(v[i][j]);
+      }
 #pragma unroll
       for (int j = 0; j < W; ++j) sum += v[i][j];
     }
@@ -219,7 +238,7 @@ __global__ __launch_bounds__(256) void ln_fwd_exact_kernel(
       float o[W];
 #pragma unroll
       for (int j = 0; j < W; ++j) o[j] = ln_norm_elem(v[i][j], mu, rs, g[i][j], b[i][j]);
-      VecIO<T, W>::store(out + row * cols + (lane + i * 64) * W, o);
+      VecIO<TH, W>::store(out + row * cols + (lane + i * 64) * W, o);
     }
     mean[row] = mu;          // every lane, one address: no exec-masked (conditional) store in the loop; both non-null here
     rstd[row] = rs;
@@ -365,12 +384,15 @@ __global__ __launch_bounds__(256) void ln_apply_exact_kernel(
 // The row loop is software-pipelined: the packed operands of the NEXT row (and its mean/rstd) are requested before
 // the current row is reduced, so each wave keeps two rows of loads in flight (4 waves/SIMD would otherwise leave
 // HBM idle during the two cross-lane reductions).
-template <typename T, int VPL, int W>
+template <typename T, int VPL, int W, typename TB = T, typename TH = T>
 struct LnBwdRow {
-  RawVec<T, W> dy[VPL], x[VPL], x2[VPL], dadd[VPL];
+  RawVec<TH, W> dy[VPL];
+  RawVec<T, W> x[VPL];
+  RawVec<TB, W> x2[VPL];
+  RawVec<T, W> dadd[VPL];
   float mu, rs;
-  __device__ __forceinline__ void load(const T* __restrict__ pdy, const T* __restrict__ px,
-                                       const T* __restrict__ px2, const T* __restrict__ pdadd,
+  __device__ __forceinline__ void load(const TH* __restrict__ pdy, const T* __restrict__ px,
+                                       const TB* __restrict__ px2, const T* __restrict__ pdadd,
                                        const float* __restrict__ mean, const float* __restrict__ rstd, int64_t row,
                                        int cols, int lane, int nvec) {
     mu = mean[row];
@@ -443,13 +465,17 @@ __device__ __forceinline__ uint32_t dp_sample(int64_t row, int64_t rps) { return
 // DY (stochastic depth, with neither X2 nor PLAIN): dy = scale[sample of the row] * dx is stored beside dx -- formed from
 // dx AS STORED (rounded to T) and rounded once more, which is what the composed form (dp_dy_kernel on the stored dx) gives
 // to the bit -- and the column sums are those of dy as stored instead of dx's. The row's scale is prefetched with the row.
-template <typename T, int VPL, int W, bool X2, bool DADD, bool PLAIN, bool DY = false>
+// DUP (the mixed family, not with PLAIN): dx is stored to dx_plain as well, rounded once to the branch's type -- the branch
+// gradient where the stream's gradient is dx itself.
+template <typename T, int VPL, int W, bool X2, bool DADD, bool PLAIN, bool DY = false, typename TB = T, typename TH = T,
+          bool DUP = false>
 __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)) void ln_bwd_exact_kernel(
-    const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ x2,
+    const TH* __restrict__ dy, const T* __restrict__ x, const TB* __restrict__ x2,
     const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const T* __restrict__ dadd, T* __restrict__ dx, T* __restrict__ dx_plain,
+    const float* __restrict__ rstd, const T* __restrict__ dadd, T* __restrict__ dx, TB* __restrict__ dx_plain,
     float* __restrict__ part, int64_t rows, const float* __restrict__ scale, T* __restrict__ dy_out, int64_t rps) {
   static_assert(!DY || (!X2 && !PLAIN), "the dy output belongs to the kept-sum forms");
+  static_assert(!DUP || (!PLAIN && !DY), "dx_plain holds one gradient");
   extern __shared__ __attribute__((aligned(16))) float smem[];   // [3 waves][3][cols]
   constexpr int cols = VPL * 64 * W, nvec = VPL * 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -474,7 +500,10 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
   int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
   struct Row {
-    RawVec<T, W> dy[VPL], x[VPL], x2[X2 ? VPL : 1], dadd[DADD ? VPL : 1];
+    RawVec<TH, W> dy[VPL];
+    RawVec<T, W> x[VPL];
+    RawVec<TB, W> x2[X2 ? VPL : 1];
+    RawVec<T, W> dadd[DADD ? VPL : 1];
     float mu, rs, c;
   } cur, nxt;
   auto load_row = [&](int64_t r, Row& q) {
@@ -543,7 +572,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
       if constexpr (PLAIN) {           // the normalisation's own input gradient leaves separately, and is what is summed
 #pragma unroll
         for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
-        VecIO<T, W>::store(dx_plain + off, o);
+        VecIO<TB, W>::store(dx_plain + off, o);
       }
       if constexpr (DADD) {
         float e[W];
@@ -556,6 +585,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
         for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
       }
       VecIO<T, W>::store(dx + off, o);
+      if constexpr (DUP) VecIO<TB, W>::store(dx_plain + off, o);
       if constexpr (DY) {
         float d[W];
 #pragma unroll
@@ -571,11 +601,12 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   ln_bwd_combine<VPL, W>(smem, part, ag, ab, ax, cols, nvec, lane, wave);
 }
 
-template <typename T, int VPL, int W>
+// DUP (the mixed family): dx_plain receives dx itself, rounded once to the branch's type, instead of the gradient without dadd
+template <typename T, int VPL, int W, typename TB = T, typename TH = T, bool DUP = false>
 __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)) void ln_bwd_kernel(
-    const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ x2,
+    const TH* __restrict__ dy, const T* __restrict__ x, const TB* __restrict__ x2,
     const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ mean,
-    const float* __restrict__ rstd, const T* __restrict__ dadd, T* __restrict__ dx, T* __restrict__ dx_plain,
+    const float* __restrict__ rstd, const T* __restrict__ dadd, T* __restrict__ dx, TB* __restrict__ dx_plain,
     float* __restrict__ part, int64_t rows, int cols) {
   extern __shared__ __attribute__((aligned(16))) float smem[];   // [3 waves][3][cols]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -601,7 +632,7 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
   }
   const int64_t stride = (int64_t)gridDim.x * kRowsPerBlock;
   int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + wave;
-  LnBwdRow<T, VPL, W> cur, nxt;
+  LnBwdRow<T, VPL, W, TB, TH> cur, nxt;
   if (row < rows) cur.load(dy, x, x2, dadd, mean, rstd, row, cols, lane, nvec);
   for (; row < rows; row += stride) {
     if (row + stride < rows) nxt.load(dy, x, x2, dadd, mean, rstd, row + stride, cols, lane, nvec);
@@ -643,10 +674,10 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
         cur.dy[i].unpack(dv);
 #pragma unroll
         for (int j = 0; j < W; ++j) o[j] = ln_bwd_dx_elem(dv[j], xh[j], g[i][j], rs, c1, c2);
-        if (dx_plain != nullptr) {
+        if (!DUP && dx_plain != nullptr) {
 #pragma unroll
           for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
-          VecIO<T, W>::store(dx_plain + row * cols + c * W, o);
+          VecIO<TB, W>::store(dx_plain + row * cols + c * W, o);
         }
         if (dadd != nullptr) {
           float e[W];
@@ -654,11 +685,12 @@ __global__ __launch_bounds__(256, (VPL * W <= 12 ? (sizeof(T) == 2 ? 3 : 2) : 1)
 #pragma unroll
           for (int j = 0; j < W; ++j) o[j] += e[j];
         }
-        if (dx_plain == nullptr) {
+        if (DUP || dx_plain == nullptr) {
 #pragma unroll
           for (int j = 0; j < W; ++j) ln_bwd_colsum_elem<T>(o[j], ax[i][j]);
         }
         VecIO<T, W>::store(dx + row * cols + c * W, o);
+        if constexpr (DUP) VecIO<TB, W>::store(dx_plain + row * cols + c * W, o);
       }
     }
     cur = nxt;
@@ -995,7 +1027,8 @@ template <typename T, int VPL, int W>
 int ln_fwd_launch(const T* x, const T* x2, const float* bias, const float* gamma, const float* beta, T* s_out, T* y,
                   float* mean, float* rstd, int64_t rows, int cols, float eps, int64_t blocks, hipStream_t st) {
 #define LN_E(X2, BIAS) \
-  ln_launch<ln_fwd_exact_kernel<T, VPL, W, X2, BIAS>>(blocks, 0, st, x, x2, bias, gamma, beta, y, mean, rstd, rows, eps)
+  ln_launch<ln_fwd_exact_kernel<T, VPL, W, X2, BIAS>>(blocks, 0, st, x, x2, bias, gamma, beta, y, mean, rstd, rows, eps, \
+                                                      (T*)nullptr)
 #define LN_G(X2) \
   ln_launch<ln_fwd_kernel<T, VPL, W, X2>>(blocks, 0, st, x, x2, bias, gamma, beta, s_out, y, mean, rstd, rows, cols, eps)
   if constexpr (ln_has_exact<T, VPL, W>(false)) {
@@ -1042,6 +1075,69 @@ int ln_bwd_launch(const T* dy, const T* x, const T* x2, const float* bias, const
 #undef LN_ARGS
 }
 
+// THE MIXED FAMILY (lvl_layernorm_*_mixed): the float32 residual stream under autocast. T = float for x, s_out, dadd and dx;
+// bf16 for the branch x2 and its gradient dx2, for the normalised rows y and for their gradient dy. The kernels are the ones
+// above with TB = TH = bf16_t: the lane layout (VPL, W) is the float32 instantiation's, so every sum is formed in its order.
+// An exact-width form is built for 256-1024 columns (W = 4) where the compiler's resource report gives it, without scratch, the
+// waves per SIMD of the float32 instantiation it replaces (profiles/ln_mixed_resource_usage_after.txt): the
+// float32 exact forward of the same operands, ln_fwd_kernel<float> where the sum is kept, and in the backward -- float32 has no
+// exact backward -- ln_bwd_kernel<float>. One form misses that: 768 columns with branch and bias and no kept sum (7 waves only
+// with scratch); it takes the general kernel.
+template <int VPL, int W>
+constexpr bool ln_mixed_exact() { return W == 4 && ln_has_exact<float, VPL, W>(false); }
+template <int VPL, int W, bool X2, bool BIAS, bool SOUT>
+constexpr bool ln_mixed_fwd_exact() { return ln_mixed_exact<VPL, W>() && !(VPL == 3 && X2 && BIAS && !SOUT); }
+
+template <int VPL, int W, bool X2, bool BIAS, bool SOUT>
+int ln_fwd_mixed_form(const float* x, const bf16_t* x2, const float* bias, const float* gamma, const float* beta,
+                      float* s_out, bf16_t* y, float* mean, float* rstd, int64_t rows, int cols, float eps, int64_t blocks,
+                      bool general, hipStream_t st) {
+  if constexpr (ln_mixed_fwd_exact<VPL, W, X2, BIAS, SOUT>()) {
+    if (!general && ln_exact_enabled() && cols == VPL * 64 * W && mean && rstd)
+      return ln_launch<ln_fwd_exact_kernel<float, VPL, W, X2, BIAS, bf16_t, bf16_t, SOUT>>(
+          blocks, 0, st, x, x2, bias, gamma, beta, y, mean, rstd, rows, eps, s_out);
+  }
+  return ln_launch<ln_fwd_kernel<float, VPL, W, X2, bf16_t, bf16_t>>(blocks, 0, st, x, x2, bias, gamma, beta, s_out, y, mean,
+                                                                     rstd, rows, cols, eps);
+}
+
+template <int VPL, int W>
+int ln_fwd_mixed_launch(const float* x, const bf16_t* x2, const float* bias, const float* gamma, const float* beta,
+                        float* s_out, bf16_t* y, float* mean, float* rstd, int64_t rows, int cols, float eps,
+                        int64_t blocks, bool general, hipStream_t st) {
+#define LN_F(X2, BIAS, SOUT, GENERAL)                                                                                 \
+  ln_fwd_mixed_form<VPL, W, X2, BIAS, SOUT>(x, x2, bias, gamma, beta, s_out, y, mean, rstd, rows, cols, eps, blocks, GENERAL, st)
+  if (!x2) return LN_F(false, false, false, general || bias || s_out);      // the exact plain form has neither
+  if (s_out) return bias ? LN_F(true, true, true, general) : LN_F(true, false, true, general);
+  return bias ? LN_F(true, true, false, general) : LN_F(true, false, false, general);
+#undef LN_F
+}
+
+// dx2 with `plain`: the gradient without dadd (ln_bwd_kernel's dx_plain); without: dx itself (DUP). The exact-width kernel for
+// the operand combinations of the training step, the general kernel otherwise.
+template <int VPL, int W>
+int ln_bwd_mixed_launch(const bf16_t* dy, const float* x, const bf16_t* x2, const float* bias, const float* gamma,
+                        const float* mean, const float* rstd, const float* dadd, float* dx, bf16_t* dx2, float* ws,
+                        int64_t rows, int cols, int64_t blocks, bool plain, bool general, hipStream_t st) {
+  const size_t shmem = (size_t)3 * 3 * cols * sizeof(float);
+#define LN_ARGS blocks, shmem, st, dy, x, x2, bias, gamma, mean, rstd, dadd, dx, dx2, ws, rows
+#define LN_E(X2, DADD, PLAIN, DUP)                                                                  \
+  ln_launch<ln_bwd_exact_kernel<float, VPL, W, X2, DADD, PLAIN, false, bf16_t, bf16_t, DUP>>(       \
+      LN_ARGS, (const float*)nullptr, (float*)nullptr, (int64_t)1)
+  if constexpr (ln_mixed_exact<VPL, W>()) {
+    if (!general && ln_exact_enabled() && cols == VPL * 64 * W && rows > 0) {
+      if (!x2 && !bias && !dadd && !dx2) return LN_E(false, false, false, false);
+      if (!x2 && !bias && dx2 && !plain) return dadd ? LN_E(false, true, false, true) : LN_E(false, false, false, true);
+      if (x2 && !dadd && dx2 && !plain) return LN_E(true, false, false, true);
+      if (x2 && dadd && dx2 && plain) return LN_E(true, true, true, false);
+    }
+  }
+  if (dx2 && !plain) return ln_launch<ln_bwd_kernel<float, VPL, W, bf16_t, bf16_t, true>>(LN_ARGS, cols);
+  return ln_launch<ln_bwd_kernel<float, VPL, W, bf16_t, bf16_t>>(LN_ARGS, cols);
+#undef LN_E
+#undef LN_ARGS
+}
+
 }  // namespace
 
 int lvl_ln_bwd_parts() { return kLnBwdParts; }
@@ -1066,6 +1162,17 @@ int lvl_launch_column_reduce(const float* part, int nparts, int width, int seg, 
   return lvl_launch_column_reduce_tail(part, nparts, width, seg, mid, out0, out1, out2, nullptr, nullptr, nullptr, 0, st);
 }
 
+// workgroups of a forward launch (lvl_layernorm_fwd and lvl_layernorm_fwd_mixed, whose forms take the registers of their
+// float32 instantiation or fewer)
+static int64_t ln_fwd_blocks(int64_t rows, const void* x2) {
+  const int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  // long per-wave row chains: 2 x the resident workgroups at 6 waves/SIMD for the two-operand form (76 VGPRs); the plain form
+  // (56 VGPRs, 8 waves/SIMD) measured best with 4 x its resident workgroups (0.136 ms at 8192 against 0.142 at 3072 and 0.176
+  // at 2048 for 200 960 rows of 768: profiles/r06_rowops_ln_fwd.txt)
+  const int64_t cap = x2 == nullptr ? 8192 : 3072;
+  return blocks > cap ? cap : blocks;
+}
+
 extern "C" int lvl_layernorm_fwd(const void* x, const void* x2, const float* xbias, const float* gamma,
                                  const float* beta, void* s_out, void* y, float* mean, float* rstd, int64_t rows,
                                  int cols, float eps, int dtype, void* stream) {
@@ -1076,12 +1183,7 @@ extern "C" int lvl_layernorm_fwd(const void* x, const void* x2, const float* xbi
                   lvl_aligned16(s_out) && lvl_aligned16(gamma) && lvl_aligned16(beta),
               "layernorm_fwd: pointers must be 16-byte aligned");
   if (rows == 0) return LVL_OK;
-  int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
-  // long per-wave row chains: 2 x the resident workgroups at 6 waves/SIMD for the two-operand form (76 VGPRs); the plain form
-  // (56 VGPRs, 8 waves/SIMD) measured best with 4 x its resident workgroups (0.136 ms at 8192 against 0.142 at 3072 and 0.176
-  // at 2048 for 200 960 rows of 768: profiles/r06_rowops_ln_fwd.txt)
-  const int64_t cap = x2 == nullptr ? 8192 : 3072;
-  if (blocks > cap) blocks = cap;
+  const int64_t blocks = ln_fwd_blocks(rows, x2);
 #define LN_FWD(VPL, W)                                                                                               \
   if (int rc = ln_fwd_launch<T, VPL, W>((const T*)x, (const T*)x2, xbias, gamma, beta, (T*)s_out, (T*)y, mean, rstd, rows, \
                                         cols, eps, blocks, (hipStream_t)stream))                                       \
@@ -1137,6 +1239,56 @@ extern "C" int lvl_layernorm_bwd(const void* dy, const void* x, const void* x2, 
   LVL_DISPATCH_DTYPE(dtype, LN_DISPATCH(cols, LN_BWD));
 #undef LN_BWD
   LVL_CHECK_LAUNCH("layernorm_bwd");
+  return lvl_launch_column_reduce(ws, (int)blocks, 3 * cols, cols, ws + (size_t)kLnBwdParts * 3 * cols, dgamma, dbeta,
+                                  dxsum, st);
+}
+
+extern "C" int lvl_layernorm_fwd_mixed(const float* x, const void* x2, const float* xbias, const float* gamma,
+                                       const float* beta, float* s_out, void* y, float* mean, float* rstd, int64_t rows,
+                                       int cols, float eps, int flags, void* stream) {
+  LVL_REQUIRE(rows == 0 || (x && gamma && beta && y), "layernorm_fwd_mixed: null pointer");
+  LVL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 4096,
+              "layernorm_fwd_mixed: cols=%d must be a multiple of 8, <= 4096", cols);
+  LVL_REQUIRE((flags & ~LVL_LN_GENERAL) == 0, "layernorm_fwd_mixed: unknown flags %d", flags);
+  LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(x2) && lvl_aligned16(xbias) && lvl_aligned16(y) &&
+                  lvl_aligned16(s_out) && lvl_aligned16(gamma) && lvl_aligned16(beta),
+              "layernorm_fwd_mixed: pointers must be 16-byte aligned");
+  if (rows == 0) return LVL_OK;
+  const int64_t blocks = ln_fwd_blocks(rows, x2);
+#define LN_FWD(VPL, W)                                                                                                  \
+  if (int rc = ln_fwd_mixed_launch<VPL, W>(x, (const bf16_t*)x2, xbias, gamma, beta, s_out, (bf16_t*)y, mean, rstd, rows, \
+                                           cols, eps, blocks, (flags & LVL_LN_GENERAL) != 0, (hipStream_t)stream))        \
+  return rc
+  LN_DISPATCH(cols, LN_FWD);
+#undef LN_FWD
+  LVL_CHECK_LAUNCH("layernorm_fwd_mixed");
+  return LVL_OK;
+}
+
+extern "C" int lvl_layernorm_bwd_mixed(const void* dy, const float* x, const void* x2, const float* xbias,
+                                       const float* gamma, const float* mean, const float* rstd, const float* dadd,
+                                       float* dx, void* dx2, float* dgamma, float* dbeta, float* dxsum, float* ws,
+                                       int64_t rows, int cols, int flags, void* stream) {
+  LVL_REQUIRE((rows == 0 || (dy && x && mean && rstd && dx)) && gamma && ws, "layernorm_bwd_mixed: null pointer");
+  LVL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 4096,
+              "layernorm_bwd_mixed: cols=%d must be a multiple of 8, <= 4096", cols);
+  LVL_REQUIRE((flags & ~(LVL_LN_GENERAL | LVL_LN_PLAIN)) == 0, "layernorm_bwd_mixed: unknown flags %d", flags);
+  LVL_REQUIRE(!(flags & LVL_LN_PLAIN) || rows == 0 || dx2, "layernorm_bwd_mixed: LVL_LN_PLAIN needs dx2");
+  LVL_REQUIRE(lvl_aligned16(dy) && lvl_aligned16(x) && lvl_aligned16(x2) && lvl_aligned16(xbias) &&
+                  lvl_aligned16(dadd) && lvl_aligned16(dx) && lvl_aligned16(dx2) && lvl_aligned16(gamma),
+              "layernorm_bwd_mixed: pointers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  int64_t blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  if (blocks > kLnBwdParts) blocks = kLnBwdParts;
+  if (blocks < 1) blocks = 1;
+#define LN_BWD(VPL, W)                                                                                                  \
+  if (int rc = ln_bwd_mixed_launch<VPL, W>((const bf16_t*)dy, x, (const bf16_t*)x2, xbias, gamma, mean, rstd, dadd, dx,   \
+                                           (bf16_t*)dx2, ws, rows, cols, blocks, (flags & LVL_LN_PLAIN) != 0,             \
+                                           (flags & LVL_LN_GENERAL) != 0, st))                                            \
+  return rc
+  LN_DISPATCH(cols, LN_BWD);
+#undef LN_BWD
+  LVL_CHECK_LAUNCH("layernorm_bwd_mixed");
   return lvl_launch_column_reduce(ws, (int)blocks, 3 * cols, cols, ws + (size_t)kLnBwdParts * 3 * cols, dgamma, dbeta,
                                   dxsum, st);
 }

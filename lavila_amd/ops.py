@@ -777,16 +777,68 @@ def layernorm_bwd_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, wan
     return dx, dgamma, dbeta, dxsum
 
 
+def _mixed_dtypes(x, x2, dy=None, dadd=None):
+    # the mixed entry points take no dtype tag: a tensor of another element size would be read past its end
+    for name, t, dt in (('x', x, torch.float32), ('x2', x2, torch.bfloat16), ('dy', dy, torch.bfloat16),
+                        ('dadd', dadd, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f'layernorm (mixed): {name} must be a contiguous {dt} tensor, got {t.dtype}')
+    for name, t in (('x2', x2), ('dy', dy), ('dadd', dadd)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f'layernorm (mixed): {name} has {t.numel()} elements, x has {x.numel()}')
+
+
+def layernorm_fwd_mixed_raw(x, x2, xbias, gamma, beta, eps, keep_sum, general=False):
+    """One lvl_layernorm_fwd_mixed call: x float32 (the residual stream), x2 bf16 or None. Returns y in bf16, the sum in
+    float32 (keep_sum) and the statistics: layernorm_fwd_raw on x and x2.float() with y rounded once, to the bit.
+    general: the general kernel also where there is an exact-width one (they agree to the bit)."""
+    C.require_device(x, x2, xbias, gamma, beta)
+    _mixed_dtypes(x, x2)
+    rows, cols = _rows_cols(x)
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    s = torch.empty_like(x) if keep_sum else None
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    C.check(C.lib().lvl_layernorm_fwd_mixed(C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(beta), C.ptr(s),
+                                            C.ptr(y), C.ptr(mean), C.ptr(rstd), rows, cols, float(eps),
+                                            C.LN_GENERAL if general else 0, C.stream_ptr()), 'lvl_layernorm_fwd_mixed')
+    return y, s, mean, rstd
+
+
+def layernorm_bwd_mixed_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_dx2=False, plain=False,
+                            general=False):
+    """One lvl_layernorm_bwd_mixed call: dy bf16, x float32, x2 bf16 or None, dadd float32 or None. Returns
+    (dx, dgamma, dbeta, dxsum, dx2): dx float32 (dadd added); dx2 (want_dx2 or plain) the branch gradient in bf16 -- dx
+    rounded once, or with plain the gradient without dadd rounded once (dxsum then sums that one, in float32)."""
+    C.require_device(dy, x, x2, xbias, gamma, mean, rstd, dadd)
+    _mixed_dtypes(x, x2, dy, dadd)
+    rows, cols = _rows_cols(x)
+    dx = torch.empty_like(x)
+    dx2 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if (want_dx2 or plain) else None
+    dgamma = torch.empty(cols, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(cols, dtype=torch.float32, device=x.device)
+    dxsum = torch.empty(cols, dtype=torch.float32, device=x.device) if want_dxsum else None
+    ws = C.workspace('layernorm_bwd', rows, cols, x.device)
+    flags = (C.LN_PLAIN if plain else 0) | (C.LN_GENERAL if general else 0)
+    C.check(C.lib().lvl_layernorm_bwd_mixed(C.ptr(dy), C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(mean),
+                                            C.ptr(rstd), C.ptr(dadd), C.ptr(dx), C.ptr(dx2), C.ptr(dgamma),
+                                            C.ptr(dbeta), C.ptr(dxsum), C.ptr(ws), rows, cols, flags,
+                                            C.stream_ptr()), 'lvl_layernorm_bwd_mixed')
+    return dx, dgamma, dbeta, dxsum, dx2
+
+
 class _LayerNormFn(torch.autograd.Function):
-    """y = LN(x) ; see lvl_layernorm_fwd/bwd."""
+    """y = LN(x) ; see lvl_layernorm_fwd/bwd. mixed (here and in the two fused forms below): the lvl_layernorm_*_mixed
+    pair -- float32 stream, bf16 normalised rows and branch, no cast node on either side (_mixed_ln)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, rec=None):
+    def forward(ctx, x, weight, bias, eps, rec=None, mixed=False):
         x = x.contiguous()
         g, b = _f32(weight), _f32(bias)
-        y, _, mean, rstd = layernorm_fwd_raw(x, None, None, g, b, eps, False)
+        y, _, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(x, None, None, g, b, eps, False)
         ctx.save_for_backward(x, g, mean, rstd)
         ctx.pdt = (weight.dtype, bias.dtype)
+        ctx.mixed = mixed
         if rec is not None:
             rec.fill(x, None, None, g, b, mean, rstd)
         return y
@@ -794,16 +846,18 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, g, mean, rstd = ctx.saved_tensors
-        dx, dg, db, _ = layernorm_bwd_raw(dy.contiguous(), x, None, None, g, mean, rstd, None, False)
-        return dx, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None
+        bwd = layernorm_bwd_mixed_raw if ctx.mixed else layernorm_bwd_raw
+        dx, dg, db = bwd(dy.contiguous(), x, None, None, g, mean, rstd, None, False)[:3]
+        return dx, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None
 
 
 # Residual stream dtype under autocast. Default: the autocast dtype (bf16) from the patch embedding to the final norm
 # (INTEGRATION.md section 3). LAVILA_RESIDUAL_F32=1 (or ops.RESIDUAL_F32 = True) keeps the stream -- and its gradient --
 # in float32 as the reference's AMP does (timesformer.py:353-366, 183-196: cat with the f32 cls_token, f32 LayerNorm
-# outputs, only GEMM outputs are half): the LayerNorm kernels then run in their f32 instantiation, branch outputs are
-# widened on the way in and the normalised rows narrowed on the way out (two extra element-wise passes per site: a
-# fidelity mode, not a fast path).
+# outputs, only GEMM outputs are half): the LayerNorm sites then run the mixed kernels (lvl_layernorm_*_mixed), which read
+# the float32 stream and the bf16 branch and write bf16 normalised rows -- and in backward the float32 stream gradient
+# and the bf16 branch gradient -- themselves: the bits of the float32 kernels between a widening and a narrowing pass,
+# without those passes. The stochastic-depth sites stay composed that way.
 RESIDUAL_F32 = os.environ.get('LAVILA_RESIDUAL_F32', '0') == '1'
 
 
@@ -817,12 +871,20 @@ def _narrow(h):
     return h.to(lp) if (lp is not None and h.dtype == torch.float32) else h
 
 
+def _mixed_ln(x, y=None):
+    """Does this LayerNorm site take the mixed kernels? A float32 stream x, a bf16 branch y (if any), and a consumer that
+    wants bf16 rows."""
+    return (x.dtype == torch.float32 and x.is_cuda and (y is None or y.dtype == torch.bfloat16)
+            and _gemm_input_dtype() == torch.bfloat16)
+
+
 def layer_norm(x, weight, bias, eps, stream=False, recipe=False):
     """stream=True: the output IS the residual stream (ln_pre): it keeps the dtype of x.
     recipe=True (here and in the fused forms below): the result is followed by the LnRecipe from which the Linear that
     consumes the normalised rows rebuilds them instead of keeping them (`ln=` of linear / mlp_quickgelu / ...)."""
     rec = LnRecipe() if recipe else None
-    y = _LayerNormFn.apply(lowp(x), weight, bias, eps, rec)
+    x = lowp(x)
+    y = _LayerNormFn.apply(x, weight, bias, eps, rec, not stream and _mixed_ln(x))
     y = y if stream else _narrow(y)
     return (y, rec) if recipe else y
 
@@ -831,10 +893,10 @@ class _AddLayerNormFn(torch.autograd.Function):
     """(s, h) = (res + y + ybias, LN(res + y + ybias)); s is only materialised when keep_sum."""
 
     @staticmethod
-    def forward(ctx, res, y, ybias, weight, bias, eps, keep_sum, rec=None):
+    def forward(ctx, res, y, ybias, weight, bias, eps, keep_sum, rec=None, mixed=False):
         res, y = res.contiguous(), y.contiguous()
         yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
-        h, s, mean, rstd = layernorm_fwd_raw(res, y, yb, g, b, eps, keep_sum)
+        h, s, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(res, y, yb, g, b, eps, keep_sum)
         if rec is not None:
             rec.fill(*((s, None, None) if keep_sum else (res, y, yb)), g, b, mean, rstd)
         if keep_sum:
@@ -842,6 +904,7 @@ class _AddLayerNormFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(res, y, yb, g, mean, rstd)
         ctx.keep_sum = keep_sum
+        ctx.mixed = mixed
         ctx.has_ybias = ybias is not None
         ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
         if keep_sum:
@@ -854,13 +917,17 @@ class _AddLayerNormFn(torch.autograd.Function):
     def backward(ctx, ds, dh):
         if ctx.keep_sum:
             s, g, mean, rstd = ctx.saved_tensors
-            dadd = ds.contiguous() if ds is not None else None
-            dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), s, None, None, g, mean, rstd, dadd, ctx.has_ybias)
+            operands = (s, None, None, g, mean, rstd, ds.contiguous() if ds is not None else None)
         else:
             res, y, yb, g, mean, rstd = ctx.saved_tensors
-            dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), res, y, yb, g, mean, rstd, None, ctx.has_ybias)
+            operands = (res, y, yb, g, mean, rstd, None)
+        if ctx.mixed:      # the branch's gradient is the stream's, rounded once by the kernel
+            dx, dg, db, dsum, dy = layernorm_bwd_mixed_raw(dh.contiguous(), *operands, ctx.has_ybias, want_dx2=True)
+        else:
+            dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), *operands, ctx.has_ybias)
+            dy = dx
         dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
-        return dx, dx, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None
+        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None, None
 
 
 # Residual adds in GEMM epilogues (LVL_EPI_BIAS_RESIDUAL; LAVILA_RESIDUAL_EPILOGUE=0 restores the composed form): the space
@@ -1001,13 +1068,14 @@ class _AddLayerNormPassFn(torch.autograd.Function):
     (dx = dx_plain + d_res_out) instead of by a separate full-size add of the autograd engine."""
 
     @staticmethod
-    def forward(ctx, res, y, ybias, weight, bias, eps, ytoken=None, rec=None):
+    def forward(ctx, res, y, ybias, weight, bias, eps, ytoken=None, rec=None, mixed=False):
         res, y = res.contiguous(), y.contiguous()
         yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
-        h, _, mean, rstd = layernorm_fwd_raw(res, y, yb, g, b, eps, False)
+        h, _, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(res, y, yb, g, b, eps, False)
         if rec is not None:
             rec.fill(res, y, yb, g, b, mean, rstd)
         ctx.save_for_backward(res, y, yb, g, mean, rstd)
+        ctx.mixed = mixed
         ctx.has_ybias = ybias is not None
         ctx.has_token = ytoken is not None
         ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
@@ -1017,7 +1085,11 @@ class _AddLayerNormPassFn(torch.autograd.Function):
     def backward(ctx, dres, dh):
         res, y, yb, g, mean, rstd = ctx.saved_tensors
         want_sum = ctx.has_ybias or (ctx.has_token and ctx.needs_input_grad[6])     # column sums of dy
-        if dres is None:
+        if ctx.mixed:
+            dadd = None if dres is None else dres.contiguous()
+            dx, dg, db, dsum, dy = layernorm_bwd_mixed_raw(dh.contiguous(), res, y, yb, g, mean, rstd, dadd, want_sum,
+                                                           want_dx2=True, plain=dadd is not None)
+        elif dres is None:
             dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), res, y, yb, g, mean, rstd, None, want_sum)
             dy = dx
         else:
@@ -1025,27 +1097,29 @@ class _AddLayerNormPassFn(torch.autograd.Function):
                                                      want_sum, want_plain=True)
         dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
         dtok = dsum if (ctx.has_token and ctx.needs_input_grad[6]) else None      # token rule: sum_rows(dy) itself
-        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, dtok, None
+        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, dtok, None, None
 
 
 def add_layer_norm_pass(res, y, ybias, weight, bias, eps, ytoken=None, recipe=False):
     """Returns (res_again, h) with h = LayerNorm(res + y (+ ybias)); use res_again for the next consumer of res.
     ytoken: the column-sum token of y (see COLSUM_TOKENS)."""
     res = lowp(res)
-    if y.dtype != res.dtype:
-        y, ytoken = y.to(res.dtype), None
+    mixed = _mixed_ln(res, y)
+    if y.dtype != res.dtype:       # the token stands for column sums of a y of the stream's dtype
+        y, ytoken = (y if mixed else y.to(res.dtype)), None
     rec = LnRecipe() if recipe else None
-    r, h = _AddLayerNormPassFn.apply(res, y, ybias, weight, bias, eps, ytoken, rec)
+    r, h = _AddLayerNormPassFn.apply(res, y, ybias, weight, bias, eps, ytoken, rec, mixed)
     return (r, _narrow(h), rec) if recipe else (r, _narrow(h))
 
 
 def add_layer_norm(res, y, ybias, weight, bias, eps, keep_sum=True, recipe=False):
     """Returns (s, h) with s = res + y (+ ybias) and h = LayerNorm(s). With keep_sum=False s is None."""
     res = lowp(res)
-    if y.dtype != res.dtype:
+    mixed = _mixed_ln(res, y)
+    if y.dtype != res.dtype and not mixed:
         y = y.to(res.dtype)
     rec = LnRecipe() if recipe else None
-    s, h = _AddLayerNormFn.apply(res, y, ybias, weight, bias, eps, keep_sum, rec)
+    s, h = _AddLayerNormFn.apply(res, y, ybias, weight, bias, eps, keep_sum, rec, mixed)
     return ((s if keep_sum else None), _narrow(h)) + ((rec,) if recipe else ())
 
 
