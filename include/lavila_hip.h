@@ -477,6 +477,53 @@ int lvl_act_bwd(const void* u, const void* da, void* du, int64_t n, int act, int
 int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows, int qrep,
                             int Tk, int H, int dtype, void* stream);
 
+/* Dropout of the narrator decoder in training (gpt2_gated.py:186-187, 230, 354, 389-395, 737, 899), generated INSIDE the
+ * kernels that already touch the data: no mask tensor is stored, the backward regenerates the mask. ONE definition
+ * (csrc/dropout.h): Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85); for a
+ * 64-bit seed, a 32-bit site, a 64-bit element index e and p in [0, 1):
+ *   g = e >> 2, ctr = (g & 0xffffffff, g >> 32, site, 0), key = (seed & 0xffffffff, seed >> 32),
+ *   w = philox4x32_10(ctr, key)[e & 3], T = min(2^32 - 1, floor(p * 2^32 + 0.5)), keep iff w >= T, scale = 1.0f / (1.0f - p).
+ * p = 0 keeps everything with scale 1. Row sites over [rows, D]: e = row * D + col. Attention sites:
+ * e = (((ctx * H + h) * qrep + i) << 8) | j for query i of its context and key j < 256. Sites follow the reference's
+ * execution order: 0 = embedding; block i: 1 + 6 i + {0 cross-attention probabilities, 1 cross c_proj output,
+ * 2 mlp_crossattention output, 3 self-attention probabilities, 4 self c_proj output, 5 mlp output}.
+ *
+ * lvl_dropout_mask: out[i] = keep(elem0 + i) as a byte, i < n -- the masks of the fused kernels (same device function),
+ *   for tests and golden tools.
+ * lvl_dropout_apply: out = keep ? scale * x : 0 over n elements (e = index; n % 8 == 0); out may be x. The embedding site,
+ *   and its own backward when applied to the gradient.
+ * lvl_gated_add_layernorm_train_drop: lvl_gated_add_layernorm_train with dropout on y: c = (*gate) * scale (gate NULL = 1),
+ *   s = round(fma(keep ? c : 0, y, res)), h = LayerNorm(s); a dropped element leaves s == res to the bit; p = 0 gives the
+ *   bits of lvl_gated_add_layernorm_train. y and sum_out are required.
+ * lvl_gated_add_layernorm_bwd_drop: ds, dgamma, dbeta as lvl_gated_add_layernorm_bwd; dy = (keep ? c : 0) * ds is written
+ *   for ungated sites too (gate NULL); with a gate, *dgate = sum ds * (keep ? scale * y : 0) over ordered partial slots
+ *   (no atomics). ws: lvl_workspace_floats("gated_add_layernorm_bwd", rows, D).
+ * lvl_attn_rows_drop_fwd / _bwd: the rows attention of lvl_cross_attn_rows_fwd / _bwd (one workgroup per (context, head),
+ *   single-pass softmax over <= 256 keys) with dropout on the probabilities and an optional causal mask. q: contexts * qrep
+ *   rows q_stride elements apart; k, v: per context Tk rows kv_stride apart, contexts kv_ctx_stride apart -- the image
+ *   keys | values [ctx, Tk, 2D] (v = k + D, strides 2D and Tk * 2D) or the k and v thirds of qkv [B L, 3D] (q_stride =
+ *   kv_stride = 3D, kv_ctx_stride = L * 3D, qrep = Tk = L, causal = 1: key j <= query i). out, dout: [rows, H*64]
+ *   contiguous; dq is laid out as q, dk / dv as k / v. P = softmax(S) over all unmasked keys, Pd = keep ? scale * P : 0
+ *   (rounded to bf16 where P is), O = Pd V; backward: dP = keep ? scale * (dO V^T) : 0, delta = sum_j P dP,
+ *   dS = P o (dP - delta), dV = Pd^T dO. Non-causal with p == 0 on the image layout IS lvl_cross_attn_rows_fwd / _bwd (same
+ *   kernels, same bits). bf16 and 1 <= Tk <= 256 only, else LVL_ENOSYS. No workspace, no atomics, bit-reproducible. */
+int lvl_dropout_mask(uint8_t* out, int64_t n, uint64_t elem0, uint64_t seed, uint32_t site, float p, void* stream);
+int lvl_dropout_apply(const void* x, void* out, int64_t n, uint64_t seed, uint32_t site, float p, int dtype, void* stream);
+int lvl_gated_add_layernorm_train_drop(const void* res, const void* y, const float* gate, const float* gamma,
+                                       const float* beta, float eps, void* sum_out, void* h_out, float* mean, float* rstd,
+                                       int rows, int D, uint64_t seed, uint32_t site, float p, int dtype, void* stream);
+int lvl_gated_add_layernorm_bwd_drop(const void* dh, const void* s, const void* y, const float* gate, const float* gamma,
+                                     const float* mean, const float* rstd, const void* dadd, void* ds, void* dy,
+                                     float* dgamma, float* dbeta, float* dgate, float* ws, int rows, int D, uint64_t seed,
+                                     uint32_t site, float p, int dtype, void* stream);
+int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* v, void* out, int contexts, int qrep, int Tk, int H,
+                           int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride, int causal, uint64_t seed,
+                           uint32_t site, float p, int dtype, void* stream);
+int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv,
+                           int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                           int64_t kv_ctx_stride, int causal, uint64_t seed, uint32_t site, float p, int dtype,
+                           void* stream);
+
 /* lvl_sample_next_token: everything VCLM_HF.generate does with one step's logits (narrator.py:122-137 and the warpers
  * of :368-389 = transformers' Temperature / TopK / TopP logits warpers with min_tokens_to_keep = 1), one workgroup per
  * caption, the row resident in LDS as 16-bit keys -- no sort, no [rows, vocab] temporaries:

@@ -20,6 +20,7 @@ ACT_GELU_NEW, ACT_SQRELU = 0, 1
 
 _c = ctypes
 _P, _I, _L, _F = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float
+_U64, _U32 = _c.c_uint64, _c.c_uint32
 
 # name -> (restype, argtypes); must list every function of include/lavila_hip.h
 SIGNATURES = {
@@ -96,6 +97,12 @@ SIGNATURES = {
     'lvl_cross_attn_rows_bwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'lvl_decode_self_attn': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'lvl_cross_attn_rows_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'lvl_dropout_mask': (_I, [_P, _L, _U64, _U64, _U32, _F, _P]),
+    'lvl_dropout_apply': (_I, [_P, _P, _L, _U64, _U32, _F, _I, _P]),
+    'lvl_gated_add_layernorm_train_drop': (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_gated_add_layernorm_bwd_drop': (_I, [_P] * 14 + [_I, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_attn_rows_drop_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_attn_rows_drop_bwd': (_I, [_P] * 7 + [_I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
 }
 
 _lib = None

@@ -13,7 +13,15 @@
 // workgroups, no atomics, and two runs are bit-identical. dK (x 0.125) and dV are rounded once to bf16 at the end.
 // Tails: key rows >= Tk are zero in the images and masked in the softmax; query rows >= qrep are never read (zero operands,
 // so they add exact zeros in phase B) and never written.
+//
+// The kernel is a template over DROP and CAUSAL like the forward's (lvl_attn_rows_drop_bwd; <false, false> is
+// lvl_cross_attn_rows_bwd's kernel to the bit), with the same pointer + stride operands, so that dq / dk / dv of the causal
+// self-attention land in the thirds of dqkv [B L, 3D]. DROP regenerates the forward's mask (dropout.h) once per round into
+// 64 bits per lane (16 fragments x 4 keys; the kernel already holds 4 x 64 accumulator registers per lane):
+//   dPd = dO . V^T,  dP = keep ? dPd / (1 - p) : 0,  delta = sum_j P dP (= dO . O),  dS = P o (dP - delta),
+//   dV += Pd^T . dO with Pd = keep ? P / (1 - p) : 0 (the P^T image holds Pd);  dQ, dK from dS as before.
 #include "attn_mfma_common.h"
+#include "dropout.h"
 
 using namespace attn_mfma;
 
@@ -23,12 +31,22 @@ constexpr int XW = 4;          // waves per workgroup
 constexpr int NKT = 16;        // key tiles of 16: up to 256 keys
 constexpr int QR = 16 * XW;    // query rows per round
 
-__global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint16_t* __restrict__ q,
-                                                                      const uint16_t* __restrict__ kv,
-                                                                      const uint16_t* __restrict__ dout,
+struct AttnDrop {
+  uint64_t seed;
+  uint32_t site, thr;
+  float scale;
+};
+
+// q / dq rows `qs` elements apart, keys / values / dk / dv rows `kvs` apart and contexts `kvctx` apart; dout [rows, D]
+template <bool DROP, bool CAUSAL>
+__global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint16_t* __restrict__ q, size_t qs,
+                                                                      const uint16_t* __restrict__ kp,
+                                                                      const uint16_t* __restrict__ vp, size_t kvs,
+                                                                      size_t kvctx, const uint16_t* __restrict__ dout,
                                                                       uint16_t* __restrict__ dq,
-                                                                      uint16_t* __restrict__ dkv, int Tk, int H,
-                                                                      int qrep) {
+                                                                      uint16_t* __restrict__ dk,
+                                                                      uint16_t* __restrict__ dv, int Tk, int H,
+                                                                      int qrep, AttnDrop drop) {
   extern __shared__ __align__(16) uint16_t xb_smem[];
   uint16_t* Ks = xb_smem;
   uint16_t* Vs = Ks + NKT * 16 * RS;
@@ -41,8 +59,8 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
   const int c = lane & 15, g = lane >> 4;
   const int h = blockIdx.x % H, ctx = blockIdx.x / H;
   const int D = H * 64;
-  const uint16_t* kb = kv + (size_t)ctx * Tk * 2 * D + h * 64;
-  stage_rows2<PrecBf16, 64 * XW, NKT / 2>(Ks, kb, (size_t)2 * D, nullptr, Vs, kb + D, (size_t)2 * D, nullptr, NKT * 16, Tk, tid, 0);
+  const size_t kvoff = (size_t)ctx * kvctx + h * 64;
+  stage_rows2<PrecBf16, 64 * XW, NKT / 2>(Ks, kp + kvoff, kvs, nullptr, Vs, vp + kvoff, kvs, nullptr, NKT * 16, Tk, tid, 0);
   __syncthreads();
   constexpr float kExp2 = 0.125f * 1.4426950408889634f;
   const FragOff fo = frag_offsets(lane);
@@ -65,8 +83,9 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     uint4 qf0 = make_uint4(0, 0, 0, 0), qf1 = qf0, df0 = qf0, df1 = qf0;
     if (qrow < qrep) {
       const size_t off = ((size_t)ctx * qrep + qrow) * D + h * 64 + g * 8;
-      qf0 = *reinterpret_cast<const uint4*>(q + off);
-      qf1 = *reinterpret_cast<const uint4*>(q + off + 32);
+      const size_t qoff = ((size_t)ctx * qrep + qrow) * qs + h * 64 + g * 8;
+      qf0 = *reinterpret_cast<const uint4*>(q + qoff);
+      qf1 = *reinterpret_cast<const uint4*>(q + qoff + 32);
       df0 = *reinterpret_cast<const uint4*>(dout + off);
       df1 = *reinterpret_cast<const uint4*>(dout + off + 32);
     }
@@ -90,7 +109,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k * 16 + g * 4 + r;
-        acc[k][r] = key < Tk ? acc[k][r] : -INFINITY;
+        acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
         m = fmaxf(m, acc[k][r]);
       }
     }
@@ -110,6 +129,17 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     const float linv = 1.f / l;
+    uint64_t keep = 0;                             // DROP: bit 4 k + r = keep of key k*16 + g*4 + r for this lane's query
+    if constexpr (DROP) {
+      const uint64_t dgrp = (((uint64_t)(ctx * H + h) * qrep + qrow) << 6) | (uint64_t)g;
+#pragma unroll
+      for (int k = 0; k < NKT; ++k) {
+        const uint32_t kb = lvl_drop::group_keep(drop.seed, drop.site, dgrp + 4 * k, drop.thr);
+        keep |= (uint64_t)kb << (4 * k);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dp[k][r] = ((kb >> r) & 1u) ? drop.scale * dp[k][r] : 0.f;     // dPd -> dP
+      }
+    }
     float delta = 0.f;
 #pragma unroll
     for (int k = 0; k < NKT; ++k) {
@@ -128,7 +158,10 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
         dp[k][r] = acc[k][r] * (dp[k][r] - delta);            // dS; masked keys: P = 0
         const int key = k * 16 + g * 4 + r;
         const int off = key * RS + ((((qcol >> 3) ^ (key & 7)) << 3) | (qcol & 7));
-        Pi[off] = f32_to_bf16(acc[k][r]);
+        if constexpr (DROP)
+          Pi[off] = f32_to_bf16(((keep >> (4 * k + r)) & 1ull) ? drop.scale * acc[k][r] : 0.f);      // Pd
+        else
+          Pi[off] = f32_to_bf16(acc[k][r]);
         Di[off] = f32_to_bf16(dp[k][r]);
       }
     }
@@ -151,7 +184,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     }
     // o[dt][r] = dQ[query g*4+r][channel dt*16 + c] / 0.125
     store_tile_rows<PrecBf16>(
-        ot, o, 0.125f, lane, [&](int row) { return dq + ((size_t)ctx * qrep + q0 + row) * D + h * 64; },
+        ot, o, 0.125f, lane, [&](int row) { return dq + ((size_t)ctx * qrep + q0 + row) * qs + h * 64; },
         [&](int row) { return q0 + row < qrep; });
     __syncthreads();
     // ---- phase B: the wave's own 64 keys against the round's 64 query rows -------------------------------------------
@@ -177,16 +210,17 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     __syncthreads();                               // the next round overwrites the images
   }
   // dK[kk][dt][r] = dK[key (wave*4+kk)*16 + g*4 + r][channel dt*16 + c] / 0.125, dV alike
-  uint16_t* ob = dkv + (size_t)ctx * Tk * 2 * D + h * 64;
+  uint16_t* okb = dk + kvoff;
+  uint16_t* ovb = dv + kvoff;
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) {
     const int k0 = (wave * 4 + kk) * 16;
     if (k0 < Tk) {
       store_tile_rows<PrecBf16>(
-          ot, dK[kk], 0.125f, lane, [&](int row) { return ob + (size_t)(k0 + row) * 2 * D; },
+          ot, dK[kk], 0.125f, lane, [&](int row) { return okb + (size_t)(k0 + row) * kvs; },
           [&](int row) { return k0 + row < Tk; });
       store_tile_rows<PrecBf16>(
-          ot, dV[kk], 1.f, lane, [&](int row) { return ob + (size_t)(k0 + row) * 2 * D + D; },
+          ot, dV[kk], 1.f, lane, [&](int row) { return ovb + (size_t)(k0 + row) * kvs; },
           [&](int row) { return k0 + row < Tk; });
     }
   }
@@ -206,10 +240,52 @@ extern "C" int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void
                     NKT * 16, dtype, Tk);
   if (rows == 0) return LVL_OK;
   const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel>()) return rc;
-  hipLaunchKernelGGL(cross_attn_bwd_mfma_kernel, dim3((unsigned)((rows / qrep) * H)), dim3(64 * XW), lds,
-                     (hipStream_t)stream, (const uint16_t*)q, (const uint16_t*)kv, (const uint16_t*)dout, (uint16_t*)dq,
-                     (uint16_t*)dkv, Tk, H, qrep);
+  const size_t D = (size_t)H * 64;
+  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<false, false>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<false, false>), dim3((unsigned)((rows / qrep) * H)), dim3(64 * XW), lds,
+                     (hipStream_t)stream, (const uint16_t*)q, D, (const uint16_t*)kv, (const uint16_t*)kv + D, 2 * D,
+                     (size_t)Tk * 2 * D, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dkv, (uint16_t*)dkv + D, Tk, H,
+                     qrep, AttnDrop{});
   LVL_CHECK_LAUNCH("cross_attn_rows_bwd");
+  return LVL_OK;
+}
+
+// backward of lvl_attn_rows_drop_fwd: dq laid out as q, dk and dv as k and v (same strides); dout [rows, H*64]
+extern "C" int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk,
+                                      void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                                      int64_t kv_ctx_stride, int causal, uint64_t seed, uint32_t site, float p, int dtype,
+                                      void* stream) {
+  LVL_REQUIRE(contexts == 0 || (q && k && v && dout && dq && dk && dv), "attn_rows_drop_bwd: null pointer");
+  LVL_REQUIRE(contexts >= 0 && qrep > 0 && Tk > 0 && H > 0, "attn_rows_drop_bwd: bad shape contexts=%d qrep=%d Tk=%d H=%d",
+              contexts, qrep, Tk, H);
+  const int64_t D = (int64_t)H * 64;
+  LVL_REQUIRE(q_stride >= D && kv_stride >= D && q_stride % 8 == 0 && kv_stride % 8 == 0 && kv_ctx_stride % 8 == 0 &&
+                  kv_ctx_stride >= 0, "attn_rows_drop_bwd: strides must be multiples of 8 elements, rows at least H*64 apart");
+  LVL_REQUIRE(!causal || qrep == Tk, "attn_rows_drop_bwd: the causal form needs qrep == Tk (got %d, %d)", qrep, Tk);
+  LVL_REQUIRE(p >= 0.f && p < 1.f, "attn_rows_drop_bwd: p = %g must be in [0, 1)", (double)p);
+  LVL_REQUIRE((int64_t)contexts * qrep * H < (1ll << 31), "attn_rows_drop_bwd: rows * heads must stay below 2^31");
+  LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(dout) && lvl_aligned16(dq) &&
+                  lvl_aligned16(dk) && lvl_aligned16(dv), "attn_rows_drop_bwd: pointers must be 16-byte aligned");
+  if (dtype != LVL_BF16 || Tk > NKT * 16)
+    return lvl_fail(LVL_ENOSYS, "attn_rows_drop_bwd: built for bf16 and 1 <= Tk <= %d keys per context (got dtype %d, Tk=%d)",
+                    NKT * 16, dtype, Tk);
+  if (contexts == 0) return LVL_OK;
+  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p)};
+#define LVL_AR(DR, CA)                                                                                                 \
+  do {                                                                                                                 \
+    if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<DR, CA>>()) return rc;                                       \
+    hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<DR, CA>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds,       \
+                       (hipStream_t)stream, (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, \
+                       (size_t)kv_stride, (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk,  \
+                       (uint16_t*)dv, Tk, H, qrep, drop);                                                              \
+  } while (0)
+  if (p > 0.f) {
+    if (causal) LVL_AR(true, true); else LVL_AR(true, false);
+  } else {
+    if (causal) LVL_AR(false, true); else LVL_AR(false, false);
+  }
+#undef LVL_AR
+  LVL_CHECK_LAUNCH("attn_rows_drop_bwd");
   return LVL_OK;
 }

@@ -8,7 +8,16 @@
 //   O   = P . V        P packed to bf16 in registers (two key tiles = one 32-deep contraction), V through the LDS
 //                      transpose read (ds_read_tr16_b64): no transposed copy is staged
 // The VALU form (cls_attn.hip) spends 1.3 us per extra query row on 8-lane dot products; here a row tile costs 64 MFMAs.
+//
+// The kernel is a template over DROP and CAUSAL (lvl_attn_rows_drop_fwd, the training decoder with attn_pdrop > 0); the
+// <false, false> instantiation is lvl_cross_attn_rows_fwd's kernel, to the bit. Keys and values come through two pointers
+// with a row and a context stride, so they are either the image keys | values [ctx, Tk, 2D] or the k and v thirds of the
+// decoder's own qkv [B L, 3D] (qrep = Tk = L, CAUSAL: key j <= query i, masked like the Tk tail).
+//   DROP: P = softmax(S) over all unmasked keys, Pd = keep ? P / (1 - p) : 0 rounded to bf16 where P is, O = Pd . V.
+//         The mask is dropout.h's over e = (((ctx * H + h) * qrep + i) << 8) | j: the four keys a lane holds in one score
+//         fragment (j = k*16 + g*4 + r) share one Philox call, generated where the fragment is packed; nothing is stored.
 #include "attn_mfma_common.h"
+#include "dropout.h"
 
 using namespace attn_mfma;
 
@@ -17,9 +26,19 @@ namespace {
 constexpr int XW = 4;          // waves per workgroup
 constexpr int NKT = 16;        // key tiles of 16: up to 256 keys (the narrator pools every clip onto 256 image tokens)
 
-__global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t* __restrict__ q,
-                                                                  const uint16_t* __restrict__ kv,
-                                                                  uint16_t* __restrict__ out, int Tk, int H, int qrep) {
+struct AttnDrop {
+  uint64_t seed;
+  uint32_t site, thr;
+  float scale;
+};
+
+// q rows at q + row * qs, keys at kp + ctx * kvctx + j * kvs (+ head), values at vp alike; out [rows, D]
+template <bool DROP, bool CAUSAL>
+__global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t* __restrict__ q, size_t qs,
+                                                                  const uint16_t* __restrict__ kp,
+                                                                  const uint16_t* __restrict__ vp, size_t kvs,
+                                                                  size_t kvctx, uint16_t* __restrict__ out, int Tk, int H,
+                                                                  int qrep, AttnDrop drop) {
   extern __shared__ __align__(16) uint16_t xa_smem[];
   uint16_t* Ks = xa_smem;
   uint16_t* Vs = Ks + NKT * 16 * RS;
@@ -28,8 +47,8 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
   const int c = lane & 15, g = lane >> 4;
   const int h = blockIdx.x % H, ctx = blockIdx.x / H;
   const int D = H * 64;
-  const uint16_t* kb = kv + (size_t)ctx * Tk * 2 * D + h * 64;
-  stage_rows2<PrecBf16, 64 * XW, NKT / 2>(Ks, kb, (size_t)2 * D, nullptr, Vs, kb + D, (size_t)2 * D, nullptr, NKT * 16, Tk, tid, 0);
+  const size_t kvoff = (size_t)ctx * kvctx + h * 64;
+  stage_rows2<PrecBf16, 64 * XW, NKT / 2>(Ks, kp + kvoff, kvs, nullptr, Vs, vp + kvoff, kvs, nullptr, NKT * 16, Tk, tid, 0);
   __syncthreads();
   constexpr float kScale = 0.125f, kExp2 = 0.125f * 1.4426950408889634f;
   const FragOff fo = frag_offsets(lane);
@@ -38,7 +57,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
 #pragma unroll 1
   for (int qt = wave; qt < ntiles; qt += XW) {
     const int qrow = qt * 16 + c;
-    const uint16_t* qp = q + ((size_t)ctx * qrep + (qrow < qrep ? qrow : qrep - 1)) * D + h * 64 + g * 8;
+    const uint16_t* qp = q + ((size_t)ctx * qrep + (qrow < qrep ? qrow : qrep - 1)) * qs + h * 64 + g * 8;
     const uint4 qf0 = *reinterpret_cast<const uint4*>(qp);
     const uint4 qf1 = *reinterpret_cast<const uint4*>(qp + 32);
     f32x4 acc[NKT];
@@ -53,7 +72,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k * 16 + g * 4 + r;
-        acc[k][r] = key < Tk ? acc[k][r] : -INFINITY;
+        acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
         m = fmaxf(m, acc[k][r]);
       }
     }
@@ -73,8 +92,19 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
     f32x4 o[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // element group of (this query, key tile k, lane group g): e >> 2 with e = (query id << 8) | key
+    const uint64_t dgrp = (((uint64_t)(ctx * H + h) * qrep + qrow) << 6) | (uint64_t)g;
 #pragma unroll
     for (int j = 0; j < NKT / 2; ++j) {
+      if constexpr (DROP) {                        // l above is the sum over ALL unmasked keys
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int k = 2 * j + t;
+          const uint32_t keep = lvl_drop::group_keep(drop.seed, drop.site, dgrp + 4 * k, drop.thr);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[k][r] = ((keep >> r) & 1u) ? drop.scale * acc[k][r] : 0.f;
+        }
+      }
       uint4 pa;
       pa.x = pack_bf16x2(acc[2 * j][0], acc[2 * j][1]);
       pa.y = pack_bf16x2(acc[2 * j][2], acc[2 * j][3]);
@@ -113,9 +143,54 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
 int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
                                hipStream_t st) {
   const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel>()) return rc;
-  hipLaunchKernelGGL(cross_attn_mfma_kernel, dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st, (const uint16_t*)q,
-                     (const uint16_t*)kv, (uint16_t*)out, Tk, H, qrep);
+  const size_t D = (size_t)H * 64;
+  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<false, false>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_mfma_kernel<false, false>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
+                     (const uint16_t*)q, D, (const uint16_t*)kv, (const uint16_t*)kv + D, 2 * D, (size_t)Tk * 2 * D,
+                     (uint16_t*)out, Tk, H, qrep, AttnDrop{});
   LVL_CHECK_LAUNCH("cross_attn_rows_fwd (mfma)");
+  return LVL_OK;
+}
+
+// The dropout-capable rows attention of the training decoder: q [contexts * qrep rows, stride q_stride], keys k and values
+// v [contexts][Tk rows, stride kv_stride] with contexts kv_ctx_stride apart (strides in elements), out [rows, H*64].
+extern "C" int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* v, void* out, int contexts, int qrep, int Tk,
+                                      int H, int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride, int causal,
+                                      uint64_t seed, uint32_t site, float p, int dtype, void* stream) {
+  LVL_REQUIRE(contexts == 0 || (q && k && v && out), "attn_rows_drop_fwd: null pointer");
+  LVL_REQUIRE(contexts >= 0 && qrep > 0 && Tk > 0 && H > 0, "attn_rows_drop_fwd: bad shape contexts=%d qrep=%d Tk=%d H=%d",
+              contexts, qrep, Tk, H);
+  const int64_t D = (int64_t)H * 64;
+  LVL_REQUIRE(q_stride >= D && kv_stride >= D && q_stride % 8 == 0 && kv_stride % 8 == 0 && kv_ctx_stride % 8 == 0 &&
+                  kv_ctx_stride >= 0, "attn_rows_drop_fwd: strides must be multiples of 8 elements, rows at least H*64 apart");
+  LVL_REQUIRE(!causal || qrep == Tk, "attn_rows_drop_fwd: the causal form needs qrep == Tk (got %d, %d)", qrep, Tk);
+  LVL_REQUIRE(p >= 0.f && p < 1.f, "attn_rows_drop_fwd: p = %g must be in [0, 1)", (double)p);
+  LVL_REQUIRE((int64_t)contexts * qrep * H < (1ll << 31), "attn_rows_drop_fwd: rows * heads must stay below 2^31");
+  LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(out),
+              "attn_rows_drop_fwd: pointers must be 16-byte aligned");
+  if (dtype != LVL_BF16 || Tk > NKT * 16)
+    return lvl_fail(LVL_ENOSYS, "attn_rows_drop_fwd: built for bf16 and 1 <= Tk <= %d keys per context (got dtype %d, Tk=%d)",
+                    NKT * 16, dtype, Tk);
+  if (contexts == 0) return LVL_OK;
+  // no dropout, no mask, the image layout: exactly today's call (which has a kernel of its own for qrep == 1)
+  if (!causal && p == 0.f && q_stride == D && kv_stride == 2 * D && kv_ctx_stride == (int64_t)Tk * 2 * D &&
+      (const uint16_t*)v == (const uint16_t*)k + D)
+    return lvl_cross_attn_rows_fwd(q, k, out, contexts * qrep, qrep, Tk, H, dtype, stream);
+  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p)};
+#define LVL_AR(DR, CA)                                                                                                 \
+  do {                                                                                                                 \
+    if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<DR, CA>>()) return rc;                                           \
+    hipLaunchKernelGGL((cross_attn_mfma_kernel<DR, CA>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds,           \
+                       (hipStream_t)stream, (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, \
+                       (size_t)kv_stride, (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, drop);                   \
+  } while (0)
+  if (p > 0.f) {
+    if (causal) LVL_AR(true, true); else LVL_AR(true, false);
+  } else {
+    if (causal) LVL_AR(false, true); else LVL_AR(false, false);
+  }
+#undef LVL_AR
+  LVL_CHECK_LAUNCH("attn_rows_drop_fwd");
   return LVL_OK;
 }

@@ -30,13 +30,27 @@ torch.autograd.Functions on the modules' own parameters, chained by autograd -- 
 (no weight gradient for a frozen weight), gated add + LayerNorm (lvl_gated_add_layernorm_train / _bwd), the activations
 (lvl_act_fwd / lvl_act_bwd), cross-attention (lvl_cross_attn_rows_fwd / _bwd, at most 256 image tokens), ops.causal_attention,
 the embedding (lvl_text_embed_fwd / _bwd) and the tied lm_head, whose weight gradient adds into wte's. bf16 only (bf16
-parameters, or float32 masters under bf16 autocast): float32 with gradients raises NotImplementedError, and so does a
-non-zero resid / embd / attn_pdrop in training mode (there is no dropout kernel; transformers' GPT2Config defaults the three
-to 0.1, so the reference trains with dropout and this decoder does not). `gradient_checkpointing_enable()` is a no-op.
+parameters, or float32 masters under bf16 autocast): float32 with gradients raises NotImplementedError.
+`gradient_checkpointing_enable()` is a no-op.
+
+Dropout (transformers' GPT2Config defaults resid_pdrop, embd_pdrop and attn_pdrop to 0.1, so the reference's narrators were
+trained with all three: gpt2_gated.py:186-187, 230, 354, 389-395, 737, 899) is OPT-IN: LAVILA_DECODER_DROPOUT=1 in the
+environment or `gpt2_gated.DECODER_DROPOUT = True`, read when a forward or gpt2_config() runs. Off (the default) a non-zero
+probability in training mode raises NotImplementedError as before and gpt2_config() defaults the three to 0.0. On,
+gpt2_config() defaults them to transformers' values and the training plan applies them inside the kernels that already
+touch the data: the embedding (lvl_dropout_apply), every residual add (lvl_gated_add_layernorm_train_drop / _bwd_drop) and
+the probabilities of both attentions (lvl_attn_rows_drop_fwd / _bwd, which then also takes the causal self-attention, at most
+256 positions). No mask is stored: forward and backward regenerate it from (seed, site, element) -- csrc/dropout.h,
+Philox4x32-10; sites in the reference's execution order: 0 the embedding, block i 1 + 6 i + {0 cross-attention
+probabilities, 1 cross c_proj, 2 mlp_crossattention, 3 self-attention probabilities, 4 self c_proj, 5 mlp}. One 64-bit seed
+per training forward comes from torch's CPU generator (torch.manual_seed reproduces a run; no device read-back);
+`fixed_dropout_seed(seed)` pins it. The distribution is the reference's, the random stream is not. A
+probability of 0 takes exactly the path without dropout; inference, decoding, .eval() and no_grad never drop.
 
 What the reference's vendored HF class offers beyond this (attention / head masks, token types, past_key_values as
 arguments, pruning, model parallelism, the other heads) raises NotImplementedError.
 """
+import contextlib
 import copy
 import os
 import types
@@ -61,18 +75,56 @@ _SIZES = {  # hidden, layers, heads of the published GPT-2 checkpoints (models.p
 }
 
 
+# Decoder dropout switch: None = follow LAVILA_DECODER_DROPOUT in the environment, True / False = set here. Read per call
+# (decoder_dropout_enabled), never cached.
+DECODER_DROPOUT = None
+# what transformers.GPT2Config() holds for resid_pdrop / embd_pdrop / attn_pdrop (tests/test_decoder_dropout_cpu.py compares
+# them with the installed transformers)
+_HF_PDROP = {'resid_pdrop': 0.1, 'embd_pdrop': 0.1, 'attn_pdrop': 0.1}
+ATTN_DROP_MAX_KEYS = 256
+_fixed_seed = None
+
+
+def decoder_dropout_enabled():
+    if DECODER_DROPOUT is not None:
+        return bool(DECODER_DROPOUT)
+    return os.environ.get('LAVILA_DECODER_DROPOUT', '0') == '1'
+
+
+@contextlib.contextmanager
+def fixed_dropout_seed(seed):
+    """Every training forward inside draws `seed` (64 bits) instead of a fresh seed from torch's generator."""
+    global _fixed_seed
+    prev, _fixed_seed = _fixed_seed, int(seed) & 0xffffffffffffffff
+    try:
+        yield
+    finally:
+        _fixed_seed = prev
+
+
+def _draw_seed():
+    """One 64-bit seed per training forward from torch's CPU generator: torch.manual_seed reproduces it, ranks seeded
+    differently differ, and nothing is read back from the device."""
+    if _fixed_seed is not None:
+        return _fixed_seed
+    lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+    return (hi << 32) | lo
+
+
 def gpt2_config(name='gpt2', **overrides):
     """The fields of transformers' GPT2Config that the decoder reads, for the published sizes -- so that the VCLM_*
     constructors work without the hub (there is no network here). A real GPT2Config is accepted everywhere instead."""
     width, layers, heads = _SIZES[name]
+    pdrop = _HF_PDROP if decoder_dropout_enabled() else dict.fromkeys(_HF_PDROP, 0.0)
     cfg = types.SimpleNamespace(
         vocab_size=50257, n_positions=1024, n_embd=width, n_layer=layers, n_head=heads, n_inner=None,
         activation_function='gelu_new', layer_norm_epsilon=1e-5, initializer_range=0.02, scale_attn_weights=True,
         scale_attn_by_inverse_layer_idx=False, reorder_and_upcast_attn=False, tie_word_embeddings=True,
         add_cross_attention=False, bos_token_id=50256, eos_token_id=50256, use_cache=False,
-        # transformers' GPT2Config defaults these three to 0.1, so the reference's decoder trains WITH dropout; this decoder
-        # has no dropout kernel and refuses to train with a non-zero value (GPT2LMHeadModel._train_ops)
-        resid_pdrop=0.0, embd_pdrop=0.0, attn_pdrop=0.0)
+        # transformers' GPT2Config defaults these three to 0.1, so the reference's decoder trains WITH dropout; here that is
+        # opt-in (decoder_dropout_enabled): off, they default to 0.0 and a non-zero value refuses to train
+        # (GPT2LMHeadModel._train_ops)
+        **pdrop)
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg
@@ -376,7 +428,10 @@ def _image_kv(p, enc):
 def _run_blocks(p, x, xkv, qrep, self_attention, fuse_ln=True):
     """The block stack on rows x [rows, D] -> LayerNorm_f of the final residual. xkv: per block image keys / values
     or None (no encoder states: plain GPT-2, gpt2_gated.py:432); `self_attention(i, qkv)` -> [rows, D]. Every residual
-    add + LayerNorm is PENDING as (y, gate, ln) until the Conv1D that reads it (p.gemm_ln -> (product, new residual))."""
+    add + LayerNorm is PENDING as (y, gate, ln) until the Conv1D that reads it (p.gemm_ln -> (product, new residual)).
+    Before every primitive that has a dropout site the plan sets `p.site`: of the pending add's y, or of the attention
+    probabilities -- 1 + 6 i + k in the reference's execution order (k: 0 cross-attention probabilities, 1 cross c_proj,
+    2 mlp_crossattention, 3 self-attention probabilities, 4 self c_proj, 5 mlp). Only the training primitives read it."""
     with_image = xkv is not None
 
     def first_ln(i):
@@ -385,19 +440,26 @@ def _run_blocks(p, x, xkv, qrep, self_attention, fuse_ln=True):
         e = p.blocks[i]
         return e['ln_x'] if (e['cross'] and with_image) else e['ln_1']
 
-    pend = (None, None, first_ln(0))
+    def conv_of_pending(entry, act):                     # -> (Conv1D of LayerNorm(x + gate * y), new residual)
+        p.site = pend_site
+        return p.gemm_ln(x, pend, entry, act, fuse_ln)
+
+    pend, pend_site = (None, None, first_ln(0)), None
     for i, e in enumerate(p.blocks):
+        site = 1 + 6 * i
         if e['cross'] and with_image:
-            q, x = p.gemm_ln(x, pend, e['xq'], None, fuse_ln)
+            q, x = conv_of_pending(e['xq'], None)
+            p.site = site
             a = p.cross_attn(q, xkv[i], qrep)
-            pend = (p.gemm(a, e['xproj']), e['gate_c'], e['ln_2x'])
-            u, x = p.gemm_ln(x, pend, e['xfc'], C.ACT_SQRELU, fuse_ln)
-            pend = (p.gemm(u, e['xfproj']), e['gate_d'], e['ln_1'])
-        qkv, x = p.gemm_ln(x, pend, e['c_attn'], None, fuse_ln)
-        a = self_attention(i, qkv)
-        pend = (p.gemm(a, e['c_proj']), None, e['ln_2'])
-        u, x = p.gemm_ln(x, pend, e['fc'], C.ACT_GELU_NEW, fuse_ln)
-        pend = (p.gemm(u, e['proj']), None, first_ln(i + 1))
+            pend, pend_site = (p.gemm(a, e['xproj']), e['gate_c'], e['ln_2x']), site + 1
+            u, x = conv_of_pending(e['xfc'], C.ACT_SQRELU)
+            pend, pend_site = (p.gemm(u, e['xfproj']), e['gate_d'], e['ln_1']), site + 2
+        qkv, x = conv_of_pending(e['c_attn'], None)
+        a = self_attention(i, qkv)                       # its dropout site: site + 3
+        pend, pend_site = (p.gemm(a, e['c_proj']), None, e['ln_2']), site + 4
+        u, x = conv_of_pending(e['fc'], C.ACT_GELU_NEW)
+        pend, pend_site = (p.gemm(u, e['proj']), None, first_ln(i + 1)), site + 5
+    p.site = pend_site
     return p.add_ln(x, *pend)[1]                         # ln_f feeds lm_head (the 256-column-panel kernel): materialised
 
 
@@ -549,6 +611,130 @@ class _CrossAttnRowsFn(torch.autograd.Function):
         return dq, dkv, None, None
 
 
+class _DropoutFn(torch.autograd.Function):
+    """out = keep ? x / (1 - p) : 0 (lvl_dropout_apply; the embedding site); the backward is the same call on the gradient."""
+
+    @staticmethod
+    def _apply(x, drop):
+        seed, site, p = drop
+        x = x if x.is_contiguous() else x.contiguous()
+        out = torch.empty_like(x)
+        C.require_device(x)
+        C.check(C.lib().lvl_dropout_apply(C.ptr(x), C.ptr(out), x.numel(), seed, site, p, C.dtype_code(x), C.stream_ptr()),
+                'lvl_dropout_apply')
+        return out
+
+    @staticmethod
+    def forward(ctx, x, seed, site, p):
+        ctx.drop = (seed, site, p)
+        return _DropoutFn._apply(x, ctx.drop)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _DropoutFn._apply(dout, ctx.drop), None, None, None
+
+
+class _GatedAddLnDropFn(torch.autograd.Function):
+    """_GatedAddLnFn with dropout on y: s = res + (keep ? tanh(alpha) / (1 - p) : 0) * y, h = LayerNorm(s) -> (s, h).
+    lvl_gated_add_layernorm_train_drop / _bwd_drop; the mask is regenerated from ctx.drop = (seed, site, p)."""
+
+    @staticmethod
+    def forward(ctx, res, y, alpha, gamma, beta, eps, seed, site, p):
+        res = res if res.is_contiguous() else res.contiguous()
+        y = y if y.is_contiguous() else y.contiguous()
+        rows, D = res.shape
+        g, b = ops._f32(gamma), ops._f32(beta)
+        gate = _tanh_gate(alpha)
+        s, h = torch.empty_like(res), torch.empty_like(res)
+        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+        C.require_device(res, y, g, b)
+        C.check(C.lib().lvl_gated_add_layernorm_train_drop(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(b), float(eps),
+                                                           C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows, D, seed, site, p,
+                                                           C.dtype_code(res), C.stream_ptr()),
+                'lvl_gated_add_layernorm_train_drop')
+        ctx.save_for_backward(s, y if gate is not None else None, gate, g, mean, rstd)
+        ctx.meta = (None if alpha is None else alpha.dtype, gamma.dtype, beta.dtype)
+        ctx.drop = (seed, site, p)
+        return s, h
+
+    @staticmethod
+    def backward(ctx, dadd, dh):
+        s, y, gate, g, mean, rstd = ctx.saved_tensors
+        adt, gdt, bdt = ctx.meta
+        seed, site, p = ctx.drop
+        rows, D = s.shape
+        if dh is None:
+            dh = torch.zeros_like(s)
+        dh = dh if dh.is_contiguous() else dh.contiguous()
+        if dadd is not None and not dadd.is_contiguous():
+            dadd = dadd.contiguous()
+        ds, dy = torch.empty_like(s), torch.empty_like(s)
+        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
+        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+        dgate = torch.empty(1, dtype=torch.float32, device=s.device) if gate is not None else None
+        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
+        C.check(C.lib().lvl_gated_add_layernorm_bwd_drop(C.ptr(dh), C.ptr(s), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(mean),
+                                                         C.ptr(rstd), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma),
+                                                         C.ptr(dbeta), C.ptr(dgate), C.ptr(ws), rows, D, seed, site, p,
+                                                         C.dtype_code(s), C.stream_ptr()), 'lvl_gated_add_layernorm_bwd_drop')
+        dalpha = None
+        if gate is not None:
+            dalpha = (dgate * (1.0 - gate * gate)).reshape(()).to(adt)
+        return ds, dy, dalpha, dgamma.to(gdt), dbeta.to(bdt), None, None, None, None
+
+
+def _off_ptr(t, elements):
+    return C._c.c_void_p(t.data_ptr() + elements * t.element_size())
+
+
+class _AttnRowsDropFn(torch.autograd.Function):
+    """lvl_attn_rows_drop_fwd / _bwd, dropout on the attention probabilities. kv given: the cross-attention, q [rows, D] over
+    kv [rows / qrep, Tk, 2 D]. kv None: the causal self-attention on q = qkv [B L, 3 D] with qrep = L positions per caption
+    (keys and values are its own thirds; the gradient comes back as dqkv)."""
+
+    @staticmethod
+    def _layout(q, kv, qrep, heads):
+        D = heads * 64
+        if kv is None:         # (k, v, contexts, Tk, q stride, kv row stride, kv context stride, causal)
+            return _off_ptr(q, D), _off_ptr(q, 2 * D), q.shape[0] // qrep, qrep, 3 * D, 3 * D, qrep * 3 * D, 1
+        return C.ptr(kv), _off_ptr(kv, D), kv.shape[0], kv.shape[1], D, 2 * D, kv.shape[1] * 2 * D, 0
+
+    @staticmethod
+    def forward(ctx, q, kv, qrep, heads, seed, site, p):
+        keys = qrep if kv is None else kv.shape[1]
+        if q.dtype != torch.bfloat16 or keys > ATTN_DROP_MAX_KEYS:
+            raise C.HipExtensionError(f'decoder attention with attn_pdrop > 0 is built for bf16 and at most '
+                                      f'{ATTN_DROP_MAX_KEYS} keys (caption positions / image tokens per clip); got '
+                                      f'{q.dtype}, {keys}')
+        q = q if q.is_contiguous() else q.contiguous()
+        if kv is not None:
+            kv = kv if kv.is_contiguous() else kv.contiguous()
+        C.require_device(q, kv)
+        k, v, contexts, Tk, qs, kvs, kvc, causal = _AttnRowsDropFn._layout(q, kv, qrep, heads)
+        out = torch.empty(q.shape[0], heads * 64, dtype=q.dtype, device=q.device)
+        C.check(C.lib().lvl_attn_rows_drop_fwd(C.ptr(q), k, v, C.ptr(out), contexts, qrep, Tk, heads, qs, kvs, kvc, causal,
+                                               seed, site, p, C.dtype_code(q), C.stream_ptr()), 'lvl_attn_rows_drop_fwd')
+        ctx.save_for_backward(q, kv)
+        ctx.cfg = (qrep, heads, seed, site, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv = ctx.saved_tensors
+        qrep, heads, seed, site, p = ctx.cfg
+        D = heads * 64
+        dout = dout if dout.is_contiguous() else dout.contiguous()
+        k, v, contexts, Tk, qs, kvs, kvc, causal = _AttnRowsDropFn._layout(q, kv, qrep, heads)
+        dq = torch.empty_like(q)
+        dkv = torch.empty_like(kv) if kv is not None else None
+        dk, dv = (_off_ptr(dq, D), _off_ptr(dq, 2 * D)) if kv is None else (C.ptr(dkv), _off_ptr(dkv, D))
+        C.check(C.lib().lvl_attn_rows_drop_bwd(C.ptr(q), k, v, C.ptr(dout), C.ptr(dq), dk, dv, contexts, qrep, Tk, heads, qs,
+                                               kvs, kvc, causal, seed, site, p, C.dtype_code(q), C.stream_ptr()),
+                'lvl_attn_rows_drop_bwd')
+        return dq, dkv, None, None, None, None, None
+
+
 class _LmHeadFn(torch.autograd.Function):
     """logits = h W^T for the (tied) lm_head weight W [vocab, D]: the vocabulary is padded with zero rows to the GEMM's
     256-column tiles (as the inference image is), the padded bf16 image and its transpose are cast per forward from the
@@ -588,24 +774,38 @@ class _LmHeadFn(torch.autograd.Function):
 
 class _TrainOps:
     """The plan's primitives as the autograd Functions above (rows in bf16). A Conv1D / LayerNorm role is the module itself,
-    a gate the alpha parameter (_GatedAddLnFn takes and differentiates its tanh). Nothing is cached: built per forward."""
+    a gate the alpha parameter (_GatedAddLnFn takes and differentiates its tanh). Nothing is cached: built per forward.
+    `pdrop` = (resid, embd, attn) probabilities this forward applies (all 0: exactly the plan without dropout); with any
+    of them set, ONE seed is drawn here and travels in each Function's ctx."""
     dtype = torch.bfloat16
 
-    def __init__(self, model):
+    def __init__(self, model, pdrop=(0.0, 0.0, 0.0)):
         _lay_out(self, model, conv=lambda m: m, ln=lambda m: m, gate=lambda alpha: alpha)
         self.wte, self.wpe, self.head = model.transformer.wte.weight, model.transformer.wpe.weight, model.lm_head.weight
+        self.p_resid, self.p_embd, self.p_attn = (float(v) for v in pdrop)
+        self.seed = _draw_seed() if any(pdrop) else 0
+        self.site = None                              # set by the plan before every primitive that has a dropout site
 
     def embed(self, ids, L):
         x = ops.text_embed(ids, self.wte, self.wpe, self.dtype)
         if x is None:                                 # tables the gather kernel does not take (bf16 parameters, width > 2048)
             x = (F.embedding(ids, self.wte) + self.wpe[:L]).to(self.dtype)
-        return x.reshape(-1, self.D)
+        x = x.reshape(-1, self.D)
+        return _DropoutFn.apply(x, self.seed, 0, self.p_embd) if self.p_embd else x
+
+    def self_attn(self, i, qkv, L):
+        """The causal self-attention of block i on qkv [B L, 3D]: ops.causal_attention, or with attn_pdrop the rows kernel."""
+        if self.p_attn:
+            return _AttnRowsDropFn.apply(qkv, None, L, self.heads, self.seed, 1 + 6 * i + 3, self.p_attn)
+        return ops.causal_attention(qkv.reshape(-1, L, 3 * self.D), self.heads).reshape(-1, self.D)
 
     def gemm(self, x2, m, act=None):
         y = _Conv1DFn.apply(x2, m.weight, m.bias)
         return y if act is None else _ActFn.apply(y, act)
 
     def add_ln(self, res, y, alpha, ln):
+        if y is not None and self.p_resid:
+            return _GatedAddLnDropFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps, self.seed, self.site, self.p_resid)
         out = _GatedAddLnFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps)
         return out if y is not None else (res, out)
 
@@ -614,6 +814,8 @@ class _TrainOps:
         return self.gemm(h, m, act), x
 
     def cross_attn(self, q, kv, qrep):
+        if self.p_attn:
+            return _AttnRowsDropFn.apply(q, kv, qrep, self.heads, self.seed, self.site, self.p_attn)
         return _CrossAttnRowsFn.apply(q, kv, qrep, self.heads)
 
     def logits(self, h2):
@@ -837,6 +1039,8 @@ class GPT2LMHeadModel(nn.Module):
                 xkv, qrep = _image_kv(p, enc), L
 
             def self_attention(i, qkv):
+                if train:
+                    return p.self_attn(i, qkv, L)
                 return ops.causal_attention(qkv.reshape(B, L, 3 * p.D), p.heads).reshape(B * L, p.D)
             h = _run_blocks(p, p.embed(ids, L), xkv, qrep, self_attention)
             logits = p.logits(h).reshape(*shape, p.vocab)
@@ -859,12 +1063,24 @@ class GPT2LMHeadModel(nn.Module):
             raise NotImplementedError('lavila_amd.gpt2_gated trains in bf16 (bf16 parameters, or float32 masters under '
                                       'torch.autocast(\'cuda\', dtype=torch.bfloat16)); there is no float32 backward for the '
                                       'decoder: call it under torch.no_grad()')
-        drop = [k for k in ('resid_pdrop', 'embd_pdrop', 'attn_pdrop') if _cfg(self.config, k, 0.0)]
+        names = ('resid_pdrop', 'embd_pdrop', 'attn_pdrop')
+        drop = [k for k in names if _cfg(self.config, k, 0.0)]
+        pdrop = (0.0, 0.0, 0.0)
         if drop and self.training:
-            raise NotImplementedError(f'the decoder has no dropout: config.{" / ".join(drop)} must be 0.0 to train it '
-                                      '(transformers\' GPT2Config defaults them to 0.1), or call .eval()')
+            if not decoder_dropout_enabled():
+                raise NotImplementedError(f'the decoder has no dropout: config.{" / ".join(drop)} must be 0.0 to train it '
+                                          '(transformers\' GPT2Config defaults them to 0.1), or call .eval(). The dropout '
+                                          'kernels are opt-in: LAVILA_DECODER_DROPOUT=1 or gpt2_gated.DECODER_DROPOUT = True')
+            pdrop = tuple(float(_cfg(self.config, k, 0.0)) for k in names)
+            if not all(0.0 <= v < 1.0 for v in pdrop):
+                raise ValueError(f'config.{" / ".join(names)} = {pdrop} must lie in [0, 1)')
         C.require_device(self.transformer.wte.weight)
-        return _TrainOps(self)
+        return _TrainOps(self, pdrop)
+
+    def applies_dropout(self):
+        """Whether a training forward of this decoder would drop now (switch on, training mode, a non-zero probability)."""
+        return bool(self.training and decoder_dropout_enabled() and
+                    any(_cfg(self.config, k, 0.0) for k in ('resid_pdrop', 'embd_pdrop', 'attn_pdrop')))
 
     def decode_session(self, encoder_hidden_states, max_length, seqs_per_context=1, graph=True):
         """Cached decoding against `encoder_hidden_states` [contexts, NQ, D]; see DecodeSession. The last sessions are

@@ -207,6 +207,11 @@ class GraphedTrainStep:
                 raise NotImplementedError('GraphedTrainStep: dropout inside a replayed graph (RNG state is not advanced)')
             if type(m).__name__ == 'DropPath' and getattr(m, 'drop_prob', 0.) > 0 and self.model.training:
                 raise NotImplementedError('GraphedTrainStep: stochastic depth inside a replayed graph')
+            # the narrator decoder holds no nn.Dropout: its masks come from a seed that is a kernel ARGUMENT, baked into the
+            # captured graph -- every replay would repeat the masks of the captured step
+            if callable(getattr(m, 'applies_dropout', None)) and m.applies_dropout():
+                raise NotImplementedError('GraphedTrainStep: decoder dropout inside a replayed graph (the seed is a kernel '
+                                          'argument of the captured launches: every replay would repeat its masks)')
         self.device = torch.device(device)
         self.amp_dtype = amp_dtype
         self.kwargs = dict(use_checkpoint=False, norm_embed=True)

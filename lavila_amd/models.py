@@ -581,6 +581,8 @@ def _vclm_openai_timesformer(clip_name, vision_kwargs, vision_width, vision_laye
     vision_model.head = nn.Identity()
     vision_model.pre_logits = nn.Identity()
     vision_model.fc = nn.Identity()
+    # gpt2_config() holds resid / embd / attn_pdrop = 0.0, or transformers' 0.1 (what the reference's GPT2Config carries
+    # here) when the decoder's dropout is switched on (LAVILA_DECODER_DROPOUT=1, gpt2_gated.DECODER_DROPOUT)
     config = augment_gpt2_config(gpt2_config(gpt2_name), cross_attn_freq=cross_attn_freq, gated_xattn=gated_xattn)
     text_decoder = GatedGPT2LMHeadModel(config)
     if not random_init_gpt2:
