@@ -582,12 +582,23 @@ int lvl_linear_tn(const void* x, const void* w, const float* bias, void* y, void
                   float* colsum, float* ws, uint32_t* sched, int64_t M, int N, int K, int epilogue, int dtype,
                   void* stream);
 
+/* ---- Plain Linear GEMM on ragged widths ------------------------------------------------------------------------
+ * y[M,N] = x[M,K] . w[N,K]^T (+ bias) for N % 64 == 0, K % 64 == 0, M >= 1: the Conv1D GEMMs (forward and input gradient)
+ * of a GPT-2 decoder whose widths are multiples of 64 but not of 256 (gpt2_gated.py's GPT-2 XL: 1600, 3200, 4800). bf16
+ * operands and result, f32 accumulation, bias [N] f32 nullable, y row stride N. Two launches on `stream`: lvl_linear_tn's
+ * persistent kernel over the N / 256 full column tiles (the launch it issues for w[:256 * (N / 256)], with N as the output
+ * stride; `sched` as there) and an edge kernel for the 64 / 128 / 192 columns behind them (alone when N < 256). No atomics,
+ * fixed summation order: repeats are bit-identical. epilogue must be LVL_EPI_BIAS and dtype LVL_BF16 (others: LVL_ENOSYS;
+ * unknown values LVL_EINVAL); operands below 4 GiB and 16-byte aligned pointers as for lvl_linear_tn. */
+int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* y, uint32_t* sched, int64_t M, int N,
+                         int K, int epilogue, int dtype, void* stream);
+
 /* ---- Linear-layer weight gradient ------------------------------------------------------------------------
  * dW[N,K] = dY[M,N]^T X[M,K], dbias[N] (nullable) = column sums of dY: what torch.autograd computes for the weight
  * and bias of every nn.Linear on the path (qkv/proj: timesformer.py:96-99, Mlp fc1/fc2: timesformer.py:47-50) when
  * `loss.backward()` runs (main_pretrain.py:520). dy: [M,N], x: [M,K] bf16 row-major; dw: [N,K] f32; dbias: [N] f32.
- * Tiled for N, K multiples of 192/288/384 (TSF-B/L widths); other shapes return LVL_ENOSYS and the caller keeps
- * the library GEMM. Workspace: lvl_workspace_floats("linear_wgrad", N, K) floats (-1 = unsupported shape).
+ * Tiled for N, K multiples of 192/288/384 (TSF-B/L widths) or 128/256, and -- where none of those divides the shape --
+ * of 160/320 (the GPT-2 XL decoder's 1600-family); other shapes return LVL_ENOSYS and the caller keeps the library GEMM. Workspace: lvl_workspace_floats("linear_wgrad", N, K) floats (-1 = unsupported shape).
  * sched (nullable): CHUNK-COUNTER block of the launch, 1024 x uint32 (64-byte aligned), ZERO on entry, zero again when
  * the launch has drained (same reuse rule as lvl_linear_tn's block). With it every (tile, row split) unit is cut into
  * row chunks handed out by device counters: a workgroup works through its own unit and then takes unclaimed chunks of

@@ -63,6 +63,7 @@ SIGNATURES = {
     'lvl_token_xent_reduce': (_I, [_P, _P, _P, _I, _I, _P, _P]),
     'lvl_token_xent_bwd': (_I, [_P, _L, _P, _L, _P, _P, _F, _L, _I, _L, _P, _I, _P]),
     'lvl_linear_tn': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
+    'lvl_linear_tn_ragged': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     'lvl_linear_wgrad': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     'lvl_cast_transpose': (_I, [_P, _P, _P, _I, _I, _P]),
     'lvl_cast_transpose_multi': (_I, [_P, _I, _L, _P]),

@@ -68,6 +68,15 @@
 //     A compute unit that another kernel holds (an RCCL channel during the gradient all-reduce) therefore costs
 //     the launch one tile's worth of throughput, not a static range of tiles: its workgroup starts late, finds
 //     the queues drained and leaves. The last workgroup out zeroes the counters again.
+//
+// N IS A STRIDE. The kernel uses N only as the row stride of Y (and of aux / the column partials); the column tiles it
+// walks are `tiles_n`, which launch_tn computes as N / 256 rounded DOWN. Launched on an output whose width is not a
+// multiple of 256 it computes the first 256 * (N / 256) columns exactly as it would for W[:256 * (N / 256)] and never
+// reads or writes the columns behind them. lvl_linear_tn keeps refusing such an N (its epilogues 2 / 5 reduce column
+// partials over all N columns); lvl_linear_tn_ragged (bottom of this file) uses the property for N % 64 == 0: this
+// kernel for the full tiles, gemm_tn_edge.hip's small kernel for the 64 / 128 / 192 columns behind them. The kernel has
+// no column mask and gets none: it sits at 248-252 VGPRs, and its K-loop waits COUNT the epilogue's stores (NS below),
+// which a sometimes-skipped store would break.
 #include <type_traits>
 
 #include "common.h"
@@ -76,6 +85,8 @@ int lvl_debug_late_mod();
 int lvl_colsum_mid_rows();
 int lvl_launch_column_reduce(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
                              float* out2, hipStream_t st);
+int lvl_launch_tn_edge(const void* x, const void* w, const float* bias, void* y, int64_t M, int N, int K, int n_first,
+                       hipStream_t st);
 
 // the LDS-DMA fills set M0 inside inline asm and say so in the clobber list; this kernel has no other M0 user
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -956,4 +967,34 @@ extern "C" int lvl_linear_tn(const void* x, const void* w, const float* bias, vo
     default:
       return lvl_fail(LVL_EINVAL, "linear_tn: unknown epilogue %d", epilogue);
   }
+}
+
+// Plain GEMM (+ bias) for any N % 64 == 0 (the decoder widths of the GPT-2 XL narrators: 1600, 3200, 4800): the full
+// 256-column tiles by the persistent kernel above -- the launch, grid and schedule lvl_linear_tn issues for W[:N0],
+// N0 = 256 * (N / 256), with N as the output stride -- and the N - N0 columns behind them by the edge kernel
+// (gemm_tn_edge.hip) on the same stream. The two launches write disjoint columns of y.
+extern "C" int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* y, uint32_t* sched, int64_t M,
+                                    int N, int K, int epilogue, int dtype, void* stream) {
+  LVL_REQUIRE(x && w && y, "linear_tn_ragged: null pointer");
+  LVL_REQUIRE(dtype == LVL_BF16 || dtype == LVL_F32, "linear_tn_ragged: unknown dtype %d", dtype);
+  if (dtype != LVL_BF16)
+    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: bf16 only (float32 rows at these widths: lvl_linear_skinny_f32c)");
+  LVL_REQUIRE(epilogue >= LVL_EPI_BIAS && epilogue <= LVL_EPI_MUL_AUX_COLSUM, "linear_tn_ragged: unknown epilogue %d", epilogue);
+  if (epilogue != LVL_EPI_BIAS)
+    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: epilogue %d is not available on ragged widths (LVL_EPI_BIAS only)", epilogue);
+  LVL_REQUIRE(M > 0 && N > 0 && K > 0, "linear_tn_ragged: empty problem");
+  if (N % 64 != 0 || K % BK != 0)
+    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: no tiling for N=%d K=%d (N %% 64 == 0 and K %% 64 == 0 needed)", N, K);
+  if ((uint64_t)M * K * 2 >= (1ull << 32) || (uint64_t)N * K * 2 >= (1ull << 32))
+    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: operand larger than 4 GiB (32-bit DMA offsets)");
+  LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(w) && lvl_aligned16(y) && lvl_aligned16(bias),
+              "linear_tn_ragged: pointers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int N0 = N / TN * TN;
+  if (N0 > 0) {
+    const int rc = launch_tn<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
+    if (rc != LVL_OK) return rc;
+  }
+  if (N0 < N) return lvl_launch_tn_edge(x, w, bias, y, M, N, K, N0, st);
+  return LVL_OK;
 }

@@ -340,11 +340,10 @@ class _Pack:
         if self.dtype == torch.bfloat16:
             if rows <= SKINNY_MAX_ROWS and n_out % 16 == 0 and n_in % 32 == 0:
                 return self._skinny(x2, w, b, act)
-            if ops._tn_ok(rows, n_out, n_in):
-                y = ops.linear_tn_raw(x2, w, b, C.EPI_BIAS)
-            else:
+            y = ops.linear_tn_rows(x2, w, b)        # lvl_linear_tn, or lvl_linear_tn_ragged for widths in 64s (GPT-2 XL)
+            if y is None:
                 ops.warn_once(('conv1d', n_out, n_in), f'decoder Conv1D [{n_in}->{n_out}] on {rows} rows runs on the '
-                              'library GEMM (lvl_linear_tn needs out % 256 == 0 and in % 64 == 0)')
+                              'library GEMM (in % 64 == 0 and out % 256 == 0, or out % 64 == 0 with both >= 256, needed)')
                 y = F.linear(x2, w, b.to(torch.bfloat16))
         elif self.own:                                  # float32 decoder, term images: own kernels in f32-class mode
             return ops.linear_f32_rows(x2, w, b, act)
@@ -478,14 +477,16 @@ class _Conv1DFn(torch.autograd.Function):
         n_in, n_out = weight.shape
         rows = x2.shape[0]
         w_in_out, w_out_in = ops.weight_copies(weight)
-        ctx.own = ops._tn_ok(rows, n_out, n_in) and (not ctx.needs_input_grad[0] or ops._tn_ok(rows, n_in, n_out))
+        # forward and input gradient each pick lvl_linear_tn or lvl_linear_tn_ragged by their own shape (c_fc [1600 -> 6400]
+        # tiles lvl_linear_tn forward and needs the ragged entry backward); the layer is on the own kernels when both are served
+        ctx.own = ops._tn_rows_ok(rows, n_out, n_in) and (not ctx.needs_input_grad[0] or ops._tn_rows_ok(rows, n_in, n_out))
         ctx.meta = (weight.dtype, bias.dtype)
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         ctx.save_for_backward(x2, w_in_out)
         if ctx.own:
-            return ops.linear_tn_raw(x2, w_out_in, ops._f32(bias), C.EPI_BIAS)
+            return ops.linear_tn_rows(x2, w_out_in, ops._f32(bias))
         ops.warn_once(('conv1d', n_out, n_in), f'decoder Conv1D [{n_in}->{n_out}] on {rows} rows runs on the '
-                      'library GEMM (lvl_linear_tn needs out % 256 == 0 and in % 64 == 0)')
+                      'library GEMM (in % 64 == 0 and out % 256 == 0, or out % 64 == 0 with both >= 256, needed)')
         with torch.autocast('cuda', enabled=False):
             return F.linear(x2, w_out_in, bias.detach().to(torch.bfloat16))
 
@@ -497,7 +498,7 @@ class _Conv1DFn(torch.autograd.Function):
         dx = dw = db = None
         with torch.autocast('cuda', enabled=False):
             if ctx.needs_input_grad[0]:
-                dx = ops.linear_tn_raw(dy, w_in_out, None, C.EPI_BIAS) if ctx.own else dy @ w_in_out.t()
+                dx = ops.linear_tn_rows(dy, w_in_out) if ctx.own else dy @ w_in_out.t()
             if ctx.needs_input_grad[1]:
                 dw = ops._wgrad(x2, dy, wdt)                  # x^T dy: [in, out], the Conv1D layout
             if ctx.needs_input_grad[2]:
@@ -747,7 +748,7 @@ class _LmHeadFn(torch.autograd.Function):
         rows = h2.shape[0]
         w = _pad_rows(weight.detach().to(torch.bfloat16), 256)
         Vp = w.shape[0]
-        ctx.own = ops._tn_ok(rows, Vp, D) and ops._tn_ok(rows, D, Vp)
+        ctx.own = ops._tn_ok(rows, Vp, D) and ops._tn_rows_ok(rows, D, Vp)       # the input gradient has N = D: ragged at 1600
         h2 = h2 if h2.is_contiguous() else h2.contiguous()
         ctx.save_for_backward(h2, w)
         ctx.meta = (V, weight.dtype)
@@ -766,7 +767,7 @@ class _LmHeadFn(torch.autograd.Function):
         dh = dw = None
         with torch.autocast('cuda', enabled=False):
             if ctx.needs_input_grad[0]:
-                dh = ops.linear_tn_raw(dl, w.t().contiguous(), None, C.EPI_BIAS) if ctx.own else dl @ w
+                dh = ops.linear_tn_rows(dl, w.t().contiguous()) if ctx.own else dl @ w
             if ctx.needs_input_grad[1]:
                 dw = ops._wgrad(dl, h2, wdt)[:V]
         return dh, dw

