@@ -4,10 +4,12 @@
 // softmax, multinomial: at 640 captions (64 clips x 10 samples, the documented recipe) that is 3 ms per step, as much as
 // the whole decoder. Here ONE workgroup per caption keeps the row in LDS as 16-bit order-preserving keys (the decoder's
 // logits are bf16: 100 KB for GPT-2's 50257 entries) and works on it in place:
-//   1. max, sum exp, sum exp * (l - max): the entropy of the UNWARPED distribution, or the cross entropy against a
-//      target token (what generate() accumulates into the perplexity);
+//   1. max, sum exp, sum exp * (l - max): the entropy of the UNWARPED distribution (0 log 0 = 0: a -inf logit adds
+//      nothing, as in torch.special.entr), or the cross entropy against a target token (what generate() accumulates
+//      into the perplexity);
 //   2. top-k: the k-th largest KEY by a two-level radix count (2048 + 32 buckets: bf16 keys have 16 bits, so two levels
-//      are exact); entries below it are dropped (ties with the k-th value stay, as `scores < kth` does in transformers);
+//      are exact); entries below it are dropped (ties with the k-th value stay, as `scores < kth` does in transformers;
+//      +0 and -0 are one value there and share one key here);
 //   3. top-p on what is left, at temperature T: the boundary VALUE below which the ascending cumulative mass stays within
 //      (1 - top_p) of the total -- transformers' rule `cumsum(sorted ascending) <= 1 - top_p` without sorting -- by
 //      bisection over the 16 key bits, each round one pass over per-thread register copies of the weights and one block
@@ -23,9 +25,13 @@ namespace {
 constexpr int ST = 1024;            // threads per row
 constexpr int L1B = 2048, L2B = 32; // radix levels over the 16-bit key: key >> 5, key & 31
 
-__device__ __forceinline__ uint32_t key_of(uint16_t b) { return (b & 0x8000u) ? (uint16_t)~b : (uint16_t)(b | 0x8000u); }
+// 16-bit keys in the order of the values: a value with the sign bit clear keeps its bits with the top bit set, one with the
+// sign bit set takes the two's complement of its bits. -0 and +0 so share the key 0x8000: they are ONE value to every
+// comparison transformers makes (`scores < kth`, the ascending sort), hence one level of the top-k count and of the nucleus'
+// ties (the one's complement would put -0 a key below +0). No real entry has key 0, the padding's.
+__device__ __forceinline__ uint32_t key_of(uint16_t b) { return (b & 0x8000u) ? (uint16_t)(0u - b) : (uint16_t)(b | 0x8000u); }
 __device__ __forceinline__ float val_of(uint32_t k) {
-  const uint16_t b = (k & 0x8000u) ? (uint16_t)(k & 0x7fffu) : (uint16_t)~k;
+  const uint16_t b = (k & 0x8000u) ? (uint16_t)(k & 0x7fffu) : (uint16_t)(0u - k);
   return bf16_to_f32(b);
 }
 
@@ -153,6 +159,15 @@ __global__ __launch_bounds__(ST) void sample_kernel(const uint16_t* __restrict__
   }
   s0 = block_sum(s0, sc, 0);
   s1 = block_sum(s1, sc, 1);
+  if (s1 != s1) {                                   // a -inf logit: 0 * -inf. 0 log 0 = 0 (torch.special.entr): sum again without
+    s1 = 0.f;                                       // the entries of weight 0 (block-uniform branch, off the usual path)
+    for (int i = tid; i < V; i += ST) {
+      const float d = val_of(keys[i]) - lmax;
+      const float e = __expf(d);
+      s1 = e > 0.f ? fmaf(e, d, s1) : s1;
+    }
+    s1 = block_sum(s1, sc, 1);
+  }
   if (tid == 0) {
     const float logz = __logf(s0);
     float out = logz - s1 / s0, cnt = 1.f;                                // entropy = log Z - E[l - max]
@@ -300,7 +315,7 @@ __global__ __launch_bounds__(ST) void sample_kernel(const uint16_t* __restrict__
         if (want < run) break;
       }
     }
-    sc.ubcast[3] = (unsigned)pick;
+    atomicMin(&sc.ubcast[3], (unsigned)pick);      // two claims (a prefix that absorbed a weight below its ulp): the first
   }
   __syncthreads();
   if (sc.ubcast[3] == 0xffffffffu) {                                        // greedy, or uniform * zk landed on / beyond the
