@@ -5,57 +5,7 @@
 // in the environment (or lvl_debug_f32_generic) sends float32 calls to the generic kernels instead (A/B in the tests).
 #include <stdlib.h>
 
-#include "common.h"
-
-int lvl_generic_divided_fwd(const void* qkv, void* out, float* lse, int B, int F, int N, int H, int mode, int dtype,
-                            hipStream_t st, bool do_groups, bool do_cls);
-int lvl_generic_divided_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
-                            float* ws, int B, int F, int N, int H, int mode, int dtype, hipStream_t st);
-int lvl_generic_causal_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dtype, hipStream_t st);
-int lvl_generic_causal_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
-                           float* ws, int B, int L, int H, int dtype, hipStream_t st);
-bool lvl_space_mfma_supported(int F, int N, int dtype);
-int lvl_space_mfma_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
-                       hipStream_t st);
-// key-tiled streaming kernels for large space groups (attn_space_stream.hip)
-bool lvl_space_stream_wanted(int F, int N, int dtype);
-int lvl_space_stream_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
-                         hipStream_t st);
-int lvl_space_stream_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                         int B, int F, int N, int H, int dtype, hipStream_t st);
-bool lvl_time_fast_supported(int F, int N, int H);
-bool lvl_time_mfma_supported(int F, int N, int H);
-int lvl_time_mfma_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, hipStream_t st);
-int lvl_time_mfma_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                      int B, int F, int N, int H, hipStream_t st);
-// 5..16 frames: the MFMA kernels (attn_time_mfma.hip; 4.2 TB/s forward at 16 frames against 1.0 TB/s for the
-// register-tiled kernels, profiles/r02_time_attention_mfma_vs_valu.txt); up to 4 frames, or a head count that is not
-// a multiple of 4: the register-tiled kernels
-static bool time_use_mfma(int F, int N, int H) { return lvl_time_mfma_supported(F, N, H); }
-bool lvl_text_mfma_supported(int L);
-int lvl_text_mfma_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int dtype, hipStream_t st);
-bool lvl_text_mfma_bwd_supported(int L, int dtype);
-int lvl_text_mfma_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                      int B, int L, int H, int dtype, hipStream_t st);
-bool lvl_space_mfma_bwd_supported(int F, int N, int dtype);
-int lvl_space_mfma_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                       float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st);
-int lvl_space_mfma_bwd_dq_part_rows(int B, int F, int N);
-bool lvl_time_fast_bwd_supported(int F, int N, int H);
-int lvl_time_fast_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                      float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st);
-int lvl_time_fast_bwd_dq_part_rows(int B, int F, int N, int H);
-int lvl_colsum_mid_rows();
-int lvl_launch_column_reduce(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
-                             float* out2, hipStream_t st);
-int lvl_launch_column_reduce_tail(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
-                                  float* out2, float* zero_dst, const float* copy_src, float* copy_dst, int tail_n,
-                                  hipStream_t st);
-int lvl_qkv_bias_sources(const void* dqkv, const void* dout, float* dbias, float* ws, int64_t rows, int D, int dtype,
-                         bool zero_k, const float* v_src, hipStream_t st);
-int64_t lvl_qkv_bias_ws_floats(int D);
-int lvl_time_fast_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
-                      hipStream_t st);
+#include "attn_internal.h"
 
 // float32 calls take the fast kernels unless the environment (LAVILA_F32_GENERIC=1, read once) or the test hook
 // lvl_debug_f32_generic asks for the generic ones
@@ -81,6 +31,39 @@ extern "C" int lvl_debug_f32_generic(int on) {
 }
 static bool fast_dtype(int dtype) { return dtype == LVL_BF16 || (dtype == LVL_F32 && f32_fast()); }
 
+// The kernel families of the divided attention, in priority order; the shape-generic kernels are what remains when no
+// entry is eligible. Space: the streaming kernels where they are the shipped choice (or forced, lvl_debug_space_stream),
+// else the LDS-resident ones. Time, 5..16 frames and heads in fours, bf16: the MFMA kernels (4.2 TB/s forward at 16
+// frames against 1.0 TB/s register-tiled, profiles/r02_time_attention_mfma_vs_valu.txt); otherwise the register-tiled
+// kernels. part_rows: the family's dq rider (attn_internal.h), null = none.
+enum Dir { FWD, BWD };
+struct Family { int mode; AttnOk* ok[2]; AttnPartRows* part_rows; AttnFwd* fwd; AttnBwd* bwd; };      // ok[Dir]
+static const Family kFamilies[] = {
+    {LVL_ATTN_SPACE, {lvl_space_stream_wanted, lvl_space_stream_wanted}, nullptr, lvl_space_stream_fwd, lvl_space_stream_bwd},
+    {LVL_ATTN_SPACE, {lvl_space_mfma_supported, lvl_space_mfma_bwd_supported}, lvl_space_mfma_bwd_dq_part_rows,
+     lvl_space_mfma_fwd, lvl_space_mfma_bwd},
+    {LVL_ATTN_TIME, {lvl_time_mfma_supported, lvl_time_mfma_supported}, nullptr, lvl_time_mfma_fwd, lvl_time_mfma_bwd},
+    {LVL_ATTN_TIME, {lvl_time_fast_supported, lvl_time_fast_supported}, lvl_time_fast_bwd_dq_part_rows,
+     lvl_time_fast_fwd, lvl_time_fast_bwd},
+};
+
+// THE dispatch decision: the family that serves this call, or null for the generic kernels
+static const Family* select(Dir dir, int mode, int F, int N, int H, int dtype) {
+  if (!fast_dtype(dtype)) return nullptr;
+  for (const Family& f : kFamilies)
+    if (f.mode == mode && f.ok[dir](F, N, H, dtype)) return &f;
+  return nullptr;
+}
+// the causal (text) attention has one fast family, with entry points of their own (no frames, no cls row)
+static bool causal_fast(Dir dir, int L, int dtype) {
+  return fast_dtype(dtype) && (dir == FWD ? lvl_text_mfma_supported(L) : lvl_text_mfma_bwd_supported(L, dtype));
+}
+// a shape is on the fast path when neither direction lands on the generic kernels
+static int fast_path(int mode, int F, int N, int H, int dtype) {
+  if (mode == LVL_ATTN_CAUSAL) return causal_fast(FWD, N, dtype) && causal_fast(BWD, N, dtype);
+  return select(FWD, mode, F, N, H, dtype) && select(BWD, mode, F, N, H, dtype);
+}
+
 static int check_divided(const char* name, const void* qkv, const void* out, int B, int F, int N, int H, int mode,
                          int dtype) {
   LVL_REQUIRE(qkv && out, "%s: null pointer", name);
@@ -96,46 +79,23 @@ extern "C" int lvl_divided_attn_fwd(const void* qkv, void* out, float* lse, floa
   if (int rc = check_divided("divided_attn_fwd", qkv, out, B, F, N, H, mode, dtype)) return rc;
   LVL_REQUIRE(lse && ws, "divided_attn_fwd: null lse / workspace");
   if (B == 0) return LVL_OK;
-  if (fast_dtype(dtype) && mode == LVL_ATTN_SPACE && F <= 64 && lvl_space_stream_wanted(F, N, dtype))
-    return lvl_space_stream_fwd(qkv, out, lse, ws, B, F, N, H, dtype, (hipStream_t)stream);
-  if (fast_dtype(dtype) && mode == LVL_ATTN_SPACE && lvl_space_mfma_supported(F, N, dtype))
-    return lvl_space_mfma_fwd(qkv, out, lse, ws, B, F, N, H, dtype, (hipStream_t)stream);
-  if (dtype == LVL_BF16 && mode == LVL_ATTN_TIME && time_use_mfma(F, N, H))
-    return lvl_time_mfma_fwd(qkv, out, lse, ws, B, F, N, H, (hipStream_t)stream);
-  if (fast_dtype(dtype) && mode == LVL_ATTN_TIME && lvl_time_fast_supported(F, N, H))
-    return lvl_time_fast_fwd(qkv, out, lse, ws, B, F, N, H, dtype, (hipStream_t)stream);
+  if (const Family* f = select(FWD, mode, F, N, H, dtype))
+    return f->fwd(qkv, out, lse, ws, B, F, N, H, dtype, (hipStream_t)stream);
   g_generic_calls.fetch_add(1, std::memory_order_relaxed);
-  return lvl_generic_divided_fwd(qkv, out, lse, B, F, N, H, mode, dtype, (hipStream_t)stream, true, true);
+  return lvl_generic_divided_fwd(qkv, out, lse, B, F, N, H, mode, dtype, (hipStream_t)stream);
 }
 
-// which backward kernel family a call lands on, and how many rows of dq column-sum partials it can emit on the way
-// (0: no rider in that family -- the bias gradient's q third is then reduced from dqkv afterwards)
-enum { BWD_STREAM, BWD_SPACE_MFMA, BWD_TIME_MFMA, BWD_TIME_FAST, BWD_GENERIC };
-static int bwd_family(int B, int F, int N, int H, int mode, int dtype, int* part_rows) {
-  *part_rows = 0;
-  if (fast_dtype(dtype) && mode == LVL_ATTN_SPACE && F <= 64 && lvl_space_stream_wanted(F, N, dtype)) return BWD_STREAM;
-  if (fast_dtype(dtype) && mode == LVL_ATTN_SPACE && lvl_space_mfma_bwd_supported(F, N, dtype)) {
-    *part_rows = lvl_space_mfma_bwd_dq_part_rows(B, F, N);
-    return BWD_SPACE_MFMA;
-  }
-  if (dtype == LVL_BF16 && mode == LVL_ATTN_TIME && time_use_mfma(F, N, H)) return BWD_TIME_MFMA;
-  if (fast_dtype(dtype) && mode == LVL_ATTN_TIME && lvl_time_fast_bwd_supported(F, N, H)) {
-    *part_rows = lvl_time_fast_bwd_dq_part_rows(B, F, N, H);
-    return BWD_TIME_FAST;
-  }
-  return BWD_GENERIC;
+// rows of dq column-sum partials the backward of this call emits on the way (0: no rider in its family -- the bias
+// gradient's q third is then reduced from dqkv afterwards)
+static int bwd_part_rows(int B, int F, int N, int H, int mode, int dtype) {
+  const Family* f = select(BWD, mode, F, N, H, dtype);
+  return f && f->part_rows ? f->part_rows(B, F, N, H) : 0;
 }
 
 static int divided_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
                        float* dq_part, int B, int F, int N, int H, int mode, int dtype, hipStream_t st) {
-  int part_rows;
-  switch (bwd_family(B, F, N, H, mode, dtype, &part_rows)) {
-    case BWD_STREAM: return lvl_space_stream_bwd(qkv, out, dout, lse, dqkv, ws, B, F, N, H, dtype, st);
-    case BWD_SPACE_MFMA: return lvl_space_mfma_bwd(qkv, out, dout, lse, dqkv, ws, dq_part, B, F, N, H, dtype, st);
-    case BWD_TIME_MFMA: return lvl_time_mfma_bwd(qkv, out, dout, lse, dqkv, ws, B, F, N, H, st);
-    case BWD_TIME_FAST: return lvl_time_fast_bwd(qkv, out, dout, lse, dqkv, ws, dq_part, B, F, N, H, dtype, st);
-    default: break;
-  }
+  if (const Family* f = select(BWD, mode, F, N, H, dtype))
+    return f->bwd(qkv, out, dout, lse, dqkv, ws, dq_part, B, F, N, H, dtype, st);
   g_generic_calls.fetch_add(1, std::memory_order_relaxed);
   return lvl_generic_divided_bwd(qkv, out, dout, lse, dqkv, ws, B, F, N, H, mode, dtype, st);
 }
@@ -160,8 +120,7 @@ extern "C" int lvl_divided_attn_bwd(const void* qkv, const void* out, const void
 //      over the q third of dqkv.
 // ws2: lvl_divided_attn_bwd_bias_ws floats.
 extern "C" int64_t lvl_divided_attn_bwd_bias_ws(int B, int F, int N, int H, int mode, int dtype) {
-  int part_rows = 0;
-  if (B > 0 && F > 0 && N > 0 && H > 0) bwd_family(B, F, N, H, mode, dtype, &part_rows);
+  const int part_rows = (B > 0 && F > 0 && N > 0 && H > 0) ? bwd_part_rows(B, F, N, H, mode, dtype) : 0;
   const int64_t D = (int64_t)H * 64;
   const int64_t rider = ((int64_t)part_rows + lvl_colsum_mid_rows()) * D;
   const int64_t pass = lvl_qkv_bias_ws_floats((int)D);
@@ -181,8 +140,7 @@ extern "C" int lvl_divided_attn_bwd_bias(const void* qkv, const void* out, const
   if (B == 0) {
     return lvl_zero_f32(dbias, (size_t)3 * D, st);
   }
-  int part_rows;
-  bwd_family(B, F, N, H, mode, dtype, &part_rows);
+  const int part_rows = bwd_part_rows(B, F, N, H, mode, dtype);
   float* dq_part = part_rows > 0 ? ws2 : nullptr;
   if (int rc = divided_bwd(qkv, out, dout, lse, dqkv, ws, dq_part, B, F, N, H, mode, dtype, st)) return rc;
   // the zeros of the k third and a ready-made v third ride on the second stage of whichever reduction runs last
@@ -203,7 +161,7 @@ extern "C" int lvl_causal_attn_fwd(const void* qkv, void* out, float* lse, int B
   LVL_REQUIRE(B >= 0 && L > 0 && H > 0, "causal_attn_fwd: bad shape B=%d L=%d H=%d", B, L, H);
   LVL_REQUIRE(lvl_aligned16(qkv) && lvl_aligned16(out), "causal_attn_fwd: pointers must be 16-byte aligned");
   if (B == 0) return LVL_OK;
-  if (fast_dtype(dtype) && lvl_text_mfma_supported(L))
+  if (causal_fast(FWD, L, dtype))
     return lvl_text_mfma_fwd(qkv, out, lse, B, L, H, dtype, (hipStream_t)stream);
   g_generic_calls.fetch_add(1, std::memory_order_relaxed);
   return lvl_generic_causal_fwd(qkv, out, lse, B, L, H, dtype, (hipStream_t)stream);
@@ -216,7 +174,7 @@ extern "C" int lvl_causal_attn_bwd(const void* qkv, const void* out, const void*
   LVL_REQUIRE(lvl_aligned16(qkv) && lvl_aligned16(out) && lvl_aligned16(dout) && lvl_aligned16(dqkv),
               "causal_attn_bwd: pointers must be 16-byte aligned");
   if (B == 0) return LVL_OK;
-  if (fast_dtype(dtype) && lvl_text_mfma_bwd_supported(L, dtype))
+  if (causal_fast(BWD, L, dtype))
     return lvl_text_mfma_bwd(qkv, out, dout, lse, dqkv, ws, B, L, H, dtype, (hipStream_t)stream);
   g_generic_calls.fetch_add(1, std::memory_order_relaxed);
   return lvl_generic_causal_bwd(qkv, out, dout, lse, dqkv, ws, B, L, H, dtype, (hipStream_t)stream);
@@ -224,24 +182,8 @@ extern "C" int lvl_causal_attn_bwd(const void* qkv, const void* out, const void*
 
 // 1 if a bf16 call of this shape runs on the MFMA / register-tiled kernels (forward AND backward), 0 if it lands on
 // the shape-generic kernels of attn_generic.hip (correct, latency-bound). Host-side query, no device work.
-extern "C" int lvl_attention_fast_path(int mode, int F, int N, int H) {
-  if (mode == LVL_ATTN_SPACE)
-    return F <= 64 && (lvl_space_stream_wanted(F, N, LVL_BF16) ||
-                       (lvl_space_mfma_supported(F, N, LVL_BF16) && lvl_space_mfma_bwd_supported(F, N, LVL_BF16)));
-  if (mode == LVL_ATTN_TIME)
-    return lvl_time_mfma_supported(F, N, H) || (lvl_time_fast_supported(F, N, H) && lvl_time_fast_bwd_supported(F, N, H));
-  if (mode == LVL_ATTN_CAUSAL) return lvl_text_mfma_supported(N) && lvl_text_mfma_bwd_supported(N, LVL_BF16);
-  return 0;
-}
+extern "C" int lvl_attention_fast_path(int mode, int F, int N, int H) { return fast_path(mode, F, N, H, LVL_BF16); }
 
 // the same question for float32 tensors (the parity configuration): 1 = the f32-class instantiations of the fast
 // kernels (split-operand MFMA / float32 register-tiled), 0 = the shape-generic kernels
-extern "C" int lvl_attention_fast_path_f32(int mode, int F, int N, int H) {
-  if (!f32_fast()) return 0;
-  if (mode == LVL_ATTN_SPACE)
-    return F <= 64 && (lvl_space_stream_wanted(F, N, LVL_F32) ||
-                       (lvl_space_mfma_supported(F, N, LVL_F32) && lvl_space_mfma_bwd_supported(F, N, LVL_F32)));
-  if (mode == LVL_ATTN_TIME) return lvl_time_fast_supported(F, N, H) && lvl_time_fast_bwd_supported(F, N, H);
-  if (mode == LVL_ATTN_CAUSAL) return lvl_text_mfma_supported(N) && lvl_text_mfma_bwd_supported(N, LVL_F32);
-  return 0;
-}
+extern "C" int lvl_attention_fast_path_f32(int mode, int F, int N, int H) { return fast_path(mode, F, N, H, LVL_F32); }

@@ -7,7 +7,7 @@
 //     (q replicated in registers) -> online softmax across chunks (no score buffer, any key count)
 //   * value phase: lane d holds output channel d; p_j is broadcast with v_readlane
 // No atomics, no cross-wave communication: results are deterministic.
-#include "common.h"
+#include "attn_internal.h"
 
 namespace {
 
@@ -293,17 +293,13 @@ int run_bwd(const void* qkv, const void* out, const void* dout, const float* lse
 
 // entry points used by the dispatcher in attention.hip
 int lvl_generic_divided_fwd(const void* qkv, void* out, float* lse, int B, int F, int N, int H, int mode, int dtype,
-                            hipStream_t st, bool do_groups, bool do_cls) {
+                            hipStream_t st) {
   int rc = LVL_OK;
-  if (do_groups) {
-    const AttnDesc d = group_desc(F, N, H, mode);
-    LVL_DISPATCH_DTYPE(dtype, rc = run_fwd<T>(qkv, out, lse, d, B, st));
-    if (rc) return rc;
-  }
-  if (do_cls) {
-    const AttnDesc c = cls_row_desc(F, N, H);
-    LVL_DISPATCH_DTYPE(dtype, rc = run_fwd<T>(qkv, out, lse, c, B, st));
-  }
+  const AttnDesc d = group_desc(F, N, H, mode);
+  LVL_DISPATCH_DTYPE(dtype, rc = run_fwd<T>(qkv, out, lse, d, B, st));
+  if (rc) return rc;
+  const AttnDesc c = cls_row_desc(F, N, H);
+  LVL_DISPATCH_DTYPE(dtype, rc = run_fwd<T>(qkv, out, lse, c, B, st));
   return rc;
 }
 

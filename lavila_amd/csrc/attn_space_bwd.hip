@@ -20,6 +20,7 @@
 //               atomics into a workspace finalised by a tiny kernel.
 // PRECISION POLICY (template P, attn_mfma_common.h): PrecBf16 = the benched kernels; PrecSplit = the same kernel text on
 // float32 tensors, operands as hi/lo bf16 images, 3 MFMAs per product (f32-class: what the parity configuration runs).
+#include "attn_internal.h"
 #include "attn_mfma_common.h"
 
 // The fused kernel's score arithmetic runs on v_pk_fma / v_pk_mul_f32 pairs; the scalar form measured 0.7 % SLOWER in
@@ -385,7 +386,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 1 : (P::kSplit ? 2 : 4))) void 
     // ---- the cls KEY (row 0 of tile 0) collects gradient from every frame: this frame's share goes to slot f of the
     // partial slab (one writer per slot; cls_grad_finalize_kernel adds the slots up in order: no atomics, deterministic)
     if (kt == 0 && g == 0) {
-      float* kv0 = atom_ws + (((size_t)b * H + h) * F + f) * 192 + 64;
+      float* kv0 = lvl_cls_slab(atom_ws, b, h, H, F, f) + 64;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         kv0[dt * 16 + c] = adk[dt][0] * 0.125f;
@@ -401,7 +402,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 1 : (P::kSplit ? 2 : 4))) void 
   if constexpr (TEXT) return;
   // ---- d(cls query): the per-tile sums were accumulated in LDS; this frame's share goes to slot f --------------
   __syncthreads();
-  if (tid < 64) atom_ws[(((size_t)b * H + h) * F + f) * 192 + tid] = dqc[tid] * 0.125f;
+  if (tid < 64) lvl_cls_slab(atom_ws, b, h, H, F, f)[tid] = dqc[tid] * 0.125f;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -483,7 +484,7 @@ __global__ __launch_bounds__(256, (P::kSplit ? 1 : 2)) void space_bwd_fused_kern
   const io_t* obase = out + (size_t)b * T * D + h * 64;
   const io_t* dobase = dout + (size_t)b * T * D + h * 64;
   const float* lrow = lse + ((size_t)b * H + h) * T;
-  float* cls_ws = atom_ws + (((size_t)b * H + h) * F + f) * 192;  // this frame's slot: d cls q | d cls k | d cls v
+  float* cls_ws = lvl_cls_slab(atom_ws, b, h, H, F, f);  // this frame's slot: d cls q | d cls k | d cls v
   const int c = lane & 15, g = lane >> 4;
   const FragOff fo = frag_offsets(lane);
   // token of query row qr: patch rows, then the cls token; padding rows alias a valid token (never stored)
@@ -808,19 +809,19 @@ int dispatch_fused(const void* qkv, const void* out, const void* dout, const flo
 
 // dqkv[b, token 0, :] = (d cls q | d cls k | d cls v) from the f32 atomic workspace
 template <typename P>
-__global__ __launch_bounds__(192) void cls_grad_finalize_kernel(const float* __restrict__ atom_ws,
+__global__ __launch_bounds__(kClsSlab) void cls_grad_finalize_kernel(const float* __restrict__ atom_ws,
                                                                 typename P::io_t* __restrict__ dqkv, int T, int H,
                                                                 int nslots) {
-  // The cls token's d(q | k | v) of one (b, h): the sum of `nslots` partial records [192] f32, one per contributing
+  // The cls token's d(q | k | v) of one (b, h): the sum of `nslots` partial records [kClsSlab] f32, one per contributing
   // workgroup (space kernels: one per frame; time kernels: one per location chunk), added up in slot order. Round 6: the
   // contributors used f32 atomicAdd on ONE record -- the order of four to twenty-five additions then depended on timing, and
   // through the cls query of the time attention a last-bit difference flipped a bf16 rounding of dqkv about one step in six
   // at the TSF-B geometry: the "second outcome" of the step (profiles/r06_second_outcome.txt).
-  const int h = blockIdx.x % H, b = blockIdx.x / H, t = threadIdx.x;      // t in [0,192): part = t/64
+  const int h = blockIdx.x % H, b = blockIdx.x / H, t = threadIdx.x;      // t in [0, kClsSlab): part = t/64
   const int D = H * 64;
-  const float* rec = atom_ws + ((size_t)b * H + h) * nslots * 192 + t;
+  const float* rec = lvl_cls_slab(atom_ws, b, h, H, nslots, 0) + t;
   float acc = 0.f;
-  for (int s = 0; s < nslots; ++s) acc += rec[(size_t)s * 192];
+  for (int s = 0; s < nslots; ++s) acc += rec[(size_t)s * kClsSlab];
   dqkv[(size_t)b * T * 3 * D + (t >> 6) * D + h * 64 + (t & 63)] = P::from_f32(acc);
 }
 
@@ -884,34 +885,36 @@ int dispatch_dq(int nkeys, const void* qkv, const void* out, const void* dout, c
 
 }  // namespace
 
-void lvl_launch_cls_grad_finalize(const float* atom_ws, void* dqkv, int B, int T, int H, int nslots, int dtype,
-                                  hipStream_t st) {
+int lvl_launch_cls_grad_finalize(const float* atom_ws, void* dqkv, int B, int T, int H, int nslots, int dtype,
+                                 hipStream_t st) {
   if (dtype == LVL_F32)
-    hipLaunchKernelGGL(cls_grad_finalize_kernel<PrecSplit>, dim3((unsigned)(B * H)), dim3(192), 0, st, atom_ws,
+    hipLaunchKernelGGL(cls_grad_finalize_kernel<PrecSplit>, dim3((unsigned)(B * H)), dim3(kClsSlab), 0, st, atom_ws,
                        (float*)dqkv, T, H, nslots);
   else
-    hipLaunchKernelGGL(cls_grad_finalize_kernel<PrecBf16>, dim3((unsigned)(B * H)), dim3(192), 0, st, atom_ws,
+    hipLaunchKernelGGL(cls_grad_finalize_kernel<PrecBf16>, dim3((unsigned)(B * H)), dim3(kClsSlab), 0, st, atom_ws,
                        (uint16_t*)dqkv, T, H, nslots);
+  LVL_CHECK_LAUNCH("cls_grad_finalize");
+  return LVL_OK;
 }
 
 // float32 (f32-class, PrecSplit): the fused kernel only (up to 288 keys; its four images fit the LDS)
-bool lvl_space_mfma_bwd_supported(int F, int N, int dtype) {
-  if (N < 1 || F > 64) return false;
+bool lvl_space_mfma_bwd_supported(int F, int N, int H, int dtype) {
+  if (N < 1 || F > kClsMaxParts) return false;
   if (N + 1 <= kFusedPairs * 32) return true;                                      // fused kernel
   if (dtype == LVL_F32) return false;
   return N + 1 <= kBigTiles * 16 && dkv_geometry(N, 4).total <= 160 * 1024;      // large groups: 4-wave kernels
 }
 
 // rows of the dq column-sum slab the fused kernel writes (0: this shape runs on kernels without the rider)
-int lvl_space_mfma_bwd_dq_part_rows(int B, int F, int N) { return N + 1 <= kFusedPairs * 32 ? B * F : 0; }
+int lvl_space_mfma_bwd_dq_part_rows(int B, int F, int N, int H) { return N + 1 <= kFusedPairs * 32 ? B * F : 0; }
 
-// ws layout: delta [B*H*T] f32, then the cls token's partial records [B*H][F][192] f32 (d cls q | d cls k | d cls v per frame)
+// ws: the backward layout of attn_internal.h, one slab per frame
 // dq_part (nullable): [B*F, H*64] f32 partial column sums of dQ, written when lvl_space_mfma_bwd_dq_part_rows > 0
 int lvl_space_mfma_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
                        float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st) {
+  LVL_REQUIRE_CLS_PARTS("space_mfma_bwd", F);
   const int T = 1 + F * N;
-  float* delta = ws;
-  float* atom_ws = ws + (size_t)B * H * T;            // every slot is written whole by its frame's workgroup: no zeroing
+  const auto [delta, atom_ws] = lvl_cls_bwd_split(ws, B, H, T);
   if (N + 1 <= kFusedPairs * 32) {
     if (int rc = dtype == LVL_F32 ? dispatch_fused<PrecSplit>(qkv, out, dout, lse, dqkv, atom_ws, dq_part, B, F, N, H, st)
                                   : dispatch_fused<PrecBf16>(qkv, out, dout, lse, dqkv, atom_ws, dq_part, B, F, N, H, st))
@@ -921,9 +924,7 @@ int lvl_space_mfma_bwd(const void* qkv, const void* out, const void* dout, const
     if (int rc = dispatch_dq<PrecBf16, false>(N + 1, qkv, out, dout, lse, dqkv, delta, B, F, N, H, st)) return rc;
     if (int rc = launch_dkv<PrecBf16, false>(qkv, out, dout, lse, delta, dqkv, atom_ws, B, F, N, H, st)) return rc;
   }
-  lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, F, dtype, st);
-  LVL_CHECK_LAUNCH("cls_grad_finalize");
-  return LVL_OK;
+  return lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, F, dtype, st);
 }
 
 bool lvl_text_mfma_bwd_supported(int L, int dtype) {

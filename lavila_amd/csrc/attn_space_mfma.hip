@@ -30,12 +30,12 @@
 // Roofline: algorithmic HBM bytes per (b,f,h) = 4 * N * 64 * 2 (q,k,v in, o out); MFMA work is ~1/3 of
 // the HBM time at 8 TB/s on TSF-B, so the kernel is built to stream: 2
 // workgroups (16 waves) per CU (<= 80 KB LDS each) overlap one group's staging with the other's MFMA phase.
+#include "attn_internal.h"
 #include "attn_mfma_common.h"
 
 namespace {
 
 using namespace attn_mfma;
-constexpr int CLS_REC = 66;       // cls partial record: m, l, acc[64]
 constexpr int kBigTiles = 37;     // large-group variant: up to 592 keys (TSF-L/14 at 336: 577)
 
 template <int NKT, int NW, int IMAGES = 1> struct SpaceLds {
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 1 : ((NKT <= 13 && !P::kSplit) 
     // o[dt][r] = O[query g*4+r][d = dt*16 + c]
     if (cls_tile) {
       // record of the CLS query over this frame's keys: (max, sum, un-normalised acc[64]) = column/row 0
-      float* rec = cls_ws + (((size_t)b * H + h) * F + f) * CLS_REC;
+      float* rec = lvl_cls_rec(cls_ws, b, h, H, F, f);
       if (g == 0) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) rec[2 + dt * 16 + c] = o[dt][0];
@@ -261,14 +261,14 @@ __global__ __launch_bounds__(64) void cls_combine_kernel(const float* __restrict
                                                          typename P::io_t* __restrict__ out,
                                                          float* __restrict__ lse, int nparts, int T, int H) {
   const int h = blockIdx.x % H, b = blockIdx.x / H, d = threadIdx.x;
-  const float* rec = cls_ws + ((size_t)b * H + h) * nparts * CLS_REC;
+  const float* rec = lvl_cls_rec(cls_ws, b, h, H, nparts, 0);
   float M = -INFINITY;
-  for (int p = 0; p < nparts; ++p) M = fmaxf(M, rec[p * CLS_REC]);
+  for (int p = 0; p < nparts; ++p) M = fmaxf(M, rec[p * kClsRec]);
   float Lsum = 0.f, acc = 0.f;
   for (int p = 0; p < nparts; ++p) {
-    const float w = __expf(rec[p * CLS_REC] - M);
-    Lsum = fmaf(rec[p * CLS_REC + 1], w, Lsum);
-    acc = fmaf(rec[p * CLS_REC + 2 + d], w, acc);
+    const float w = __expf(rec[p * kClsRec] - M);
+    Lsum = fmaf(rec[p * kClsRec + 1], w, Lsum);
+    acc = fmaf(rec[p * kClsRec + 2 + d], w, acc);
   }
   out[(size_t)b * T * H * 64 + h * 64 + d] = P::from_f32(acc / Lsum);
   if (d == 0) lse[((size_t)b * H + h) * T] = M + __logf(Lsum);
@@ -285,10 +285,7 @@ int launch_space_fwd(const void* qkv, void* out, float* lse, float* ws, int B, i
                      L::total, st, (const io_t*)qkv, (io_t*)out, lse, ws, F, N, H);
   LVL_CHECK_LAUNCH("space_fwd_mfma");
   if (TEXT) return LVL_OK;
-  hipLaunchKernelGGL(cls_combine_kernel<P>, dim3((unsigned)(B * H)), dim3(64), 0, st, ws, (io_t*)out, lse, F,
-                     1 + F * N, H);
-  LVL_CHECK_LAUNCH("cls_combine");
-  return LVL_OK;
+  return lvl_launch_cls_combine(ws, out, lse, B, H, F, 1 + F * N, P::kSplit ? LVL_F32 : LVL_BF16, st);
 }
 
 template <typename P>
@@ -315,23 +312,26 @@ int dispatch_text_fwd(const void* qkv, void* out, float* lse, int B, int L, int 
 
 }  // namespace
 
-void lvl_launch_cls_combine(const float* ws, void* out, float* lse, int B, int H, int nparts, int T, int dtype,
-                            hipStream_t st) {
+int lvl_launch_cls_combine(const float* ws, void* out, float* lse, int B, int H, int nparts, int T, int dtype,
+                           hipStream_t st) {
   if (dtype == LVL_F32)
     hipLaunchKernelGGL(cls_combine_kernel<PrecSplit>, dim3((unsigned)(B * H)), dim3(64), 0, st, ws, (float*)out, lse,
                        nparts, T, H);
   else
     hipLaunchKernelGGL(cls_combine_kernel<PrecBf16>, dim3((unsigned)(B * H)), dim3(64), 0, st, ws, (uint16_t*)out, lse,
                        nparts, T, H);
+  LVL_CHECK_LAUNCH("cls_combine");
+  return LVL_OK;
 }
 
 // bf16: groups of up to 592 keys; float32 (f32-class, PrecSplit: four LDS images): up to 272 keys
-bool lvl_space_mfma_supported(int F, int N, int dtype) {
-  return N + 1 <= (dtype == LVL_F32 ? 17 : kBigTiles) * 16 && N >= 1 && F <= 64;
+bool lvl_space_mfma_supported(int F, int N, int H, int dtype) {
+  return N + 1 <= (dtype == LVL_F32 ? 17 : kBigTiles) * 16 && N >= 1 && F <= kClsMaxParts;
 }
 
 int lvl_space_mfma_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
                        hipStream_t st) {
+  LVL_REQUIRE_CLS_PARTS("space_mfma_fwd", F);
   const int nkeys = N + 1;
   if (dtype == LVL_F32) {
     const int rc = dispatch_space_fwd_small<PrecSplit>(nkeys, qkv, out, lse, ws, B, F, N, H, st);

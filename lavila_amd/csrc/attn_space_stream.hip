@@ -19,6 +19,7 @@
 //            dK / dV go to the atomic slab (it collects gradient from every frame).
 // Same precision policies as the resident kernels (attn_mfma_common.h): PrecBf16, and PrecSplit for float32 tensors
 // (f32-class: hi/lo images, 3 MFMAs per product), which also takes the 577-key float32 groups off the generic kernels.
+#include "attn_internal.h"
 #include "attn_mfma_common.h"
 
 namespace {
@@ -26,7 +27,6 @@ namespace {
 using namespace attn_mfma;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kExp2 = 0.125f * kLog2e;          // exp(s * scale) = exp2(s * kExp2)
-constexpr int CLS_REC = 66;                       // cls partial record: m, l, acc[64]
 constexpr int KC = 64;                            // streamed rows per chunk (4 MFMA tiles)
 
 template <int IMAGES> struct StreamLds {
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, (P::kSplit ? 1 : OCC)) void space_stream_fwd_k
     if (!live[t]) continue;
     if (cls_t[t]) {
       // record of the cls query over this frame's keys: (max, sum, un-normalised acc[64]) = query column 0
-      float* rec = cls_ws + (((size_t)b * H + h) * F + f) * CLS_REC;
+      float* rec = lvl_cls_rec(cls_ws, b, h, H, F, f);
       if (c == 0) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256, (P::kSplit ? 1 : 3)) void space_stream_dq_kern
   const io_t* dobase = dout + (size_t)b * T * D + h * 64;
   const float* lrow = lse + ((size_t)b * H + h) * T;
   float* drow = delta + ((size_t)b * H + h) * T;
-  float* cls_slab = atom_ws + (((size_t)b * H + h) * F + f) * 192;        // d cls q | d cls k | d cls v
+  float* cls_slab = lvl_cls_slab(atom_ws, b, h, H, F, f);
   const int c = lane & 15, g = lane >> 4;
   const int nqt = (N + 15) / 16, ntiles = nqt + 1;
   const FragOff fo = frag_offsets(lane);
@@ -633,7 +633,7 @@ __global__ __launch_bounds__(256, (P::kSplit ? 1 : 2)) void space_stream_dkv_ker
   const io_t* dobase = dout + (size_t)b * T * D + h * 64;
   const float* lrow = lse + ((size_t)b * H + h) * T;
   const float* drow = delta + ((size_t)b * H + h) * T;
-  float* cls_slab = atom_ws + (((size_t)b * H + h) * F + f) * 192;
+  float* cls_slab = lvl_cls_slab(atom_ws, b, h, H, F, f);
   const int c = lane & 15, g = lane >> 4;
   const int nkt = (nkeys + 15) / 16;
   const FragOff fo = frag_offsets(lane);
@@ -966,11 +966,6 @@ int launch_stream_bwd(const void* qkv, const void* out, const void* dout, const 
 
 }  // namespace
 
-void lvl_launch_cls_combine(const float* ws, void* out, float* lse, int B, int H, int nparts, int T, int dtype,
-                            hipStream_t st);
-void lvl_launch_cls_grad_finalize(const float* atom_ws, void* dqkv, int B, int T, int H, int nslots, int dtype,
-                                  hipStream_t st);
-
 // Test / measurement hook: 1 = the streaming kernels for EVERY space group (parity tests at small shapes, A/B against the
 // resident kernels), -1 = never, 0 = the shipped choice (lvl_space_stream_wanted).
 extern "C" int lvl_debug_space_stream(int mode) {
@@ -1001,7 +996,8 @@ extern "C" int lvl_set_fp8_qk(int on) {
   return LVL_OK;
 }
 
-bool lvl_space_stream_wanted(int F, int N, int dtype) {
+bool lvl_space_stream_wanted(int F, int N, int H, int dtype) {
+  if (F > kClsMaxParts) return false;           // one cls partial per frame
   const int mode = g_stream_mode.load();
   if (mode != 0) return mode > 0;
   return N + 1 > 288 || (dtype == LVL_F32 && N + 1 > 272);
@@ -1009,27 +1005,24 @@ bool lvl_space_stream_wanted(int F, int N, int dtype) {
 
 int lvl_space_stream_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
                          hipStream_t st) {
+  LVL_REQUIRE_CLS_PARTS("space_stream_fwd", F);
   const int rc = dtype == LVL_F32 ? launch_stream_fwd<PrecSplit>(qkv, out, lse, ws, B, F, N, H, st)
                  : fp8_qk()       ? launch_stream_fwd<PrecFp8QK>(qkv, out, lse, ws, B, F, N, H, st)
                                   : launch_stream_fwd<PrecBf16>(qkv, out, lse, ws, B, F, N, H, st);
   if (rc != LVL_OK) return rc;
-  lvl_launch_cls_combine(ws, out, lse, B, H, F, 1 + F * N, dtype, st);
-  LVL_CHECK_LAUNCH("cls_combine");
-  return LVL_OK;
+  return lvl_launch_cls_combine(ws, out, lse, B, H, F, 1 + F * N, dtype, st);
 }
 
-// ws layout: delta [B*H*T] f32, then atomics [B*H*192] f32 (d cls q | d cls k | d cls v)
+// ws: the backward layout of attn_internal.h, one slab per frame; no rider (dq_part unused)
 int lvl_space_stream_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                         int B, int F, int N, int H, int dtype, hipStream_t st) {
+                         float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st) {
+  LVL_REQUIRE_CLS_PARTS("space_stream_bwd", F);
   const int T = 1 + F * N;
-  float* delta = ws;
-  float* atom_ws = ws + (size_t)B * H * T;            // partial records [B*H][F][192]: every slot has its writer, no zeroing
+  const auto [delta, atom_ws] = lvl_cls_bwd_split(ws, B, H, T);
   const int rc = dtype == LVL_F32
                      ? launch_stream_bwd<PrecSplit>(qkv, out, dout, lse, dqkv, delta, atom_ws, B, F, N, H, st)
                  : fp8_qk() ? launch_stream_bwd<PrecFp8QK>(qkv, out, dout, lse, dqkv, delta, atom_ws, B, F, N, H, st)
                             : launch_stream_bwd<PrecBf16>(qkv, out, dout, lse, dqkv, delta, atom_ws, B, F, N, H, st);
   if (rc != LVL_OK) return rc;
-  lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, F, dtype, st);
-  LVL_CHECK_LAUNCH("cls_grad_finalize");
-  return LVL_OK;
+  return lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, F, dtype, st);
 }

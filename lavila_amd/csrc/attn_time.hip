@@ -14,11 +14,10 @@
 // gradient from every location -- go through LDS + f32 atomics into a workspace (cls_grad_finalize_kernel).
 #include <stdlib.h>
 
-#include "common.h"
+#include "attn_internal.h"
 
 namespace {
 
-constexpr int CLS_REC = 66;
 constexpr float kLog2e = 1.4426950408889634f;
 
 // E = element type in HBM: uint16_t (bf16 bits, the benched path) or float (the parity configuration: the same kernels,
@@ -214,7 +213,7 @@ __global__ __launch_bounds__((DPL == 2 ? 512 : 256), (DPL == 2 || sizeof(E) == 4
 #pragma unroll
       for (int i = 0; i < DPL; ++i) acc[i] = fmaf(r[2 + i], w, acc[i]);
     }
-    float* rec = cls_ws + (((size_t)b * H + h) * NC + chunk) * CLS_REC;
+    float* rec = lvl_cls_rec(cls_ws, b, h, H, NC, chunk);
     if (dl == 0) { rec[0] = M * (1.0f / kLog2e); rec[1] = Ls; }      // record max in natural-log units
 #pragma unroll
     for (int i = 0; i < DPL; ++i) rec[2 + dl * DPL + i] = acc[i];
@@ -409,7 +408,7 @@ __global__ __launch_bounds__((DPL == 2 ? 512 : 256), time_bwd_waves(sizeof(E), F
     }
     // this chunk's record of the cls token's d(q | k | v): slot `chunk` of the (b, h) partial slab, one writer, plain
     // stores; cls_grad_finalize_kernel adds the NC slots up in order (round 6: deterministic, no f32 atomics)
-    float* dst = atom_ws + (((size_t)b * H + h) * NC + chunk) * 192 + dl * DPL;
+    float* dst = lvl_cls_slab(atom_ws, b, h, H, NC, chunk) + dl * DPL;
 #pragma unroll
     for (int i = 0; i < DPL; ++i) {
       dst[i] = acc[i];
@@ -440,7 +439,7 @@ TimeGeom time_geometry(int N, int H, int dpl) {
   g.block = per_n * g.NPB;
   g.ok = g.block <= (dpl == 2 ? 512 : 256);
   int nch = g.NPB * 8;                       // >= 8 locations per thread group: amortise the cls/LDS epilogue
-  while ((N + nch - 1) / nch > 64) nch *= 2;  // at most 64 partial records per (b,h)
+  while ((N + nch - 1) / nch > kClsMaxParts) nch *= 2;
   g.NCH = nch;
   g.NC = (N + nch - 1) / nch;
   return g;
@@ -448,12 +447,7 @@ TimeGeom time_geometry(int N, int H, int dpl) {
 
 }  // namespace
 
-void lvl_launch_cls_combine(const float* ws, void* out, float* lse, int B, int H, int nparts, int T, int dtype,
-                            hipStream_t st);
-void lvl_launch_cls_grad_finalize(const float* atom_ws, void* dqkv, int B, int T, int H, int nslots, int dtype,
-                                  hipStream_t st);
-
-bool lvl_time_fast_supported(int F, int N, int H) {
+bool lvl_time_fast_supported(int F, int N, int H, int dtype) {
   if (!(F == 1 || F == 2 || F == 3 || F == 4 || F == 8 || F == 16)) return false;
   return time_geometry(N, H, time_dpl(F)).ok;
 }
@@ -463,6 +457,7 @@ int lvl_time_fast_fwd(const void* qkv, void* out, float* lse, float* ws, int B, 
   const int dpl = time_dpl(F);
   const TimeGeom g = time_geometry(N, H, dpl);
   if (!g.ok) return lvl_fail(LVL_ENOSYS, "time_fast_fwd: unsupported head count %d", H);
+  LVL_REQUIRE_CLS_PARTS("time_fast_fwd", g.NC);
   const size_t shmem = (size_t)g.NPB * H * (64 / dpl) * (2 + dpl) * sizeof(float);
   const dim3 grid((unsigned)(B * g.NC)), block(g.block);
 #define TIME_FWD(FF, DD)                                                                                          \
@@ -485,9 +480,7 @@ int lvl_time_fast_fwd(const void* qkv, void* out, float* lse, float* ws, int B, 
   }
 #undef TIME_FWD
   LVL_CHECK_LAUNCH("time_fwd");
-  lvl_launch_cls_combine(ws, out, lse, B, H, g.NC, 1 + F * N, dtype, st);
-  LVL_CHECK_LAUNCH("cls_combine");
-  return LVL_OK;
+  return lvl_launch_cls_combine(ws, out, lse, B, H, g.NC, 1 + F * N, dtype, st);
 }
 
 // -1 (default): measured choice per shape -- 2 at F = 4 (the benched TSF-B shape: 0.485 ms per backward + bias gradient
@@ -506,26 +499,22 @@ extern "C" int lvl_debug_time_bwd_rider(int mode) {
   return LVL_OK;
 }
 
-bool lvl_time_fast_bwd_supported(int F, int N, int H) {
-  if (!(F == 1 || F == 2 || F == 3 || F == 4 || F == 8 || F == 16)) return false;
-  return time_geometry(N, H, time_dpl(F)).ok;
-}
-
 // rows of the dq column-sum slab (one per workgroup); 0 = this family runs without the rider
 int lvl_time_fast_bwd_dq_part_rows(int B, int F, int N, int H) {
   const TimeGeom g = time_geometry(N, H, time_dpl(F));
   return (g.ok && time_rider_mode(F) != 0) ? B * g.NC : 0;
 }
 
-// ws layout: delta [B*H*T] f32 (unused here), then the cls token's partial records [B*H][NC][192] f32
+// ws: the backward layout of attn_internal.h, one slab per location chunk
 // dq_part (nullable): [lvl_time_fast_bwd_dq_part_rows, H*64] f32 partial column sums of dq (bias-gradient rider)
 int lvl_time_fast_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
                       float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st) {
   const int dpl = time_dpl(F);
   const TimeGeom g = time_geometry(N, H, dpl);
   if (!g.ok) return lvl_fail(LVL_ENOSYS, "time_fast_bwd: unsupported head count %d", H);
+  LVL_REQUIRE_CLS_PARTS("time_fast_bwd", g.NC);
   const int T = 1 + F * N;
-  float* atom_ws = ws + (size_t)B * H * T;            // every (b, h, chunk) slot is written whole by its workgroup: no zeroing
+  float* atom_ws = lvl_cls_bwd_split(ws, B, H, T).slabs;
   const int rider = dq_part ? time_rider_mode(F) : 0;
   const size_t shmem = (size_t)g.NPB * H * (64 / dpl) * (rider ? 4 : 3) * dpl * sizeof(float);
   const dim3 grid((unsigned)(B * g.NC)), block(g.block);
@@ -558,7 +547,5 @@ int lvl_time_fast_bwd(const void* qkv, const void* out, const void* dout, const 
 #undef TIME_BWD
 #undef TIME_BWD_R
   LVL_CHECK_LAUNCH("time_bwd");
-  lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, g.NC, dtype, st);
-  LVL_CHECK_LAUNCH("cls_grad_finalize");
-  return LVL_OK;
+  return lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, g.NC, dtype, st);
 }

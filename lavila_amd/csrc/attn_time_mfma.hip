@@ -19,12 +19,12 @@
 //     added to the f32 workspace once per wave.
 // A workgroup is 4 waves = 4 consecutive heads of the same location range (their head rows are adjacent in memory).
 // HBM-bound: 4 rows in + 1 row out per token forward, 5 in + 3 out backward; the MFMA work is noise.
+#include "attn_internal.h"
 #include "attn_mfma_common.h"
 
 namespace {
 
 using namespace attn_mfma;
-constexpr int CLS_REC = 66;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kExp2 = 0.125f * kLog2e;          // exp(s * scale) = exp2(s * kExp2)
 constexpr int NWV = 4;                            // waves (= heads) per workgroup
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(NWV * 64) void time_mfma_fwd_kernel(const uint16_t*
     if (g == 0 && live) lse[((size_t)b * H + h) * T + 1 + c * N + n] = m * 0.125f + __logf(l);
   }
   // partial record of the CLS query over this wave's locations
-  float* rec = cls_ws + (((size_t)b * H + h) * NC + chunk) * CLS_REC;
+  float* rec = lvl_cls_rec(cls_ws, b, h, H, NC, chunk);
   if (g == 0) {
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) rec[2 + dt * 16 + c] = ca[dt][0];
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(NWV * 64) void time_mfma_bwd_kernel(const uint16_t*
   // the cls token's gradients: row 0 of the accumulated tiles (lanes g == 0) -> this chunk's slot of the (b, h) partial
   // slab, one writer per slot; cls_grad_finalize_kernel adds the NC slots up in order (round 6: no f32 atomics)
   if (g == 0) {
-    float* dst = atom_ws + (((size_t)b * H + h) * NC + chunk) * 192;
+    float* dst = lvl_cls_slab(atom_ws, b, h, H, NC, chunk);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       dst[dt * 16 + c] = aq[dt][0] * 0.125f;
@@ -407,42 +407,39 @@ __global__ __launch_bounds__(NWV * 64) void time_mfma_bwd_kernel(const uint16_t*
 struct Geo { int NCH, NC; };
 inline Geo geometry(int N) {
   int nch = 16;                                // locations per wave: amortises the cls prologue / epilogue
-  while ((N + nch - 1) / nch > 64) nch *= 2;   // at most 64 partial records per (b, h)
+  while ((N + nch - 1) / nch > kClsMaxParts) nch *= 2;
   return Geo{nch, (N + nch - 1) / nch};
 }
 
 }  // namespace
 
-void lvl_launch_cls_combine(const float* ws, void* out, float* lse, int B, int H, int nparts, int T, int dtype,
-                            hipStream_t st);
-void lvl_launch_cls_grad_finalize(const float* atom_ws, void* dqkv, int B, int T, int H, int nslots, int dtype,
-                                  hipStream_t st);
+// bf16 only: there is no f32-class instantiation of these kernels
+bool lvl_time_mfma_supported(int F, int N, int H, int dtype) {
+  return dtype == LVL_BF16 && F >= 5 && F <= 16 && N >= 1 && H % NWV == 0;
+}
 
-bool lvl_time_mfma_supported(int F, int N, int H) { return F >= 5 && F <= 16 && N >= 1 && H % NWV == 0; }
-
-int lvl_time_mfma_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, hipStream_t st) {
+int lvl_time_mfma_fwd(const void* qkv, void* out, float* lse, float* ws, int B, int F, int N, int H, int dtype,
+                      hipStream_t st) {
   const Geo g = geometry(N);
+  LVL_REQUIRE_CLS_PARTS("time_mfma_fwd", g.NC);
   hipLaunchKernelGGL(time_mfma_fwd_kernel, dim3((unsigned)(B * g.NC * (H / NWV))), dim3(NWV * 64), 0, st,
                      (const uint16_t*)qkv, (uint16_t*)out, lse, ws, F, N, H, g.NCH, g.NC);
   LVL_CHECK_LAUNCH("time_mfma_fwd");
-  lvl_launch_cls_combine(ws, out, lse, B, H, g.NC, 1 + F * N, LVL_BF16, st);
-  LVL_CHECK_LAUNCH("cls_combine");
-  return LVL_OK;
+  return lvl_launch_cls_combine(ws, out, lse, B, H, g.NC, 1 + F * N, LVL_BF16, st);
 }
 
-// ws layout: delta [B*H*T] f32 (unused here), then the cls token's partial records [B*H][NC][192] f32
+// ws: the backward layout of attn_internal.h, one slab per location chunk; no rider (dq_part unused)
 int lvl_time_mfma_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* ws,
-                      int B, int F, int N, int H, hipStream_t st) {
+                      float* dq_part, int B, int F, int N, int H, int dtype, hipStream_t st) {
   const Geo g = geometry(N);
+  LVL_REQUIRE_CLS_PARTS("time_mfma_bwd", g.NC);
   const int T = 1 + F * N;
-  float* atom_ws = ws + (size_t)B * H * T;            // every (b, h, chunk) slot is written whole by its wave: no zeroing
+  float* atom_ws = lvl_cls_bwd_split(ws, B, H, T).slabs;
   if (int rc = lvl_allow_lds<time_mfma_bwd_kernel>()) return rc;
   hipLaunchKernelGGL(time_mfma_bwd_kernel, dim3((unsigned)(B * g.NC * (H / NWV))), dim3(NWV * 64),
                      NWV * (4 * IMG + 16 * OS) * sizeof(uint16_t), st,
                      (const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, (uint16_t*)dqkv, atom_ws, F,
                      N, H, g.NCH, g.NC);
   LVL_CHECK_LAUNCH("time_mfma_bwd");
-  lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, g.NC, LVL_BF16, st);
-  LVL_CHECK_LAUNCH("cls_grad_finalize");
-  return LVL_OK;
+  return lvl_launch_cls_grad_finalize(atom_ws, dqkv, B, T, H, g.NC, LVL_BF16, st);
 }

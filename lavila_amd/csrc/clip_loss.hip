@@ -7,7 +7,7 @@
 // output aside); the row statistics (log-sum-exp, diagonal, expectation, argmax) come out of one
 // streaming pass, and backward recomputes the logits from the gathered embeddings + gathered LSEs,
 // so no gradient collective is needed.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -124,10 +124,6 @@ __global__ __launch_bounds__(256) void clip_bwd_kernel(const T* __restrict__ img
 }
 
 }  // namespace
-
-bool lvl_clip_mfma_supported(int E);
-int lvl_clip_fwd_mfma(const void* img_all, const void* txt_all, const float* scale, int B, int G, int E, int row0,
-                      float* stats, int32_t* argmax, float* logits, int dtype, hipStream_t st);
 
 extern "C" int lvl_clip_loss_fwd(const void* img_all, const void* txt_all, const float* scale, int B, int G, int E, int row0,
                                  float* stats, int32_t* argmax, float* logits, int dtype, void* stream) {

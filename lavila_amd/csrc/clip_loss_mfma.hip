@@ -9,6 +9,7 @@
 // (the 1e-3 parity bar holds with two orders of margin) at bf16 matrix-core speed. The contraction is tiny
 // (2*B*G*E flop per direction); what matters is that no pass over a [B, G] tensor is ever made.
 #include "attn_mfma_common.h"
+#include "internal.h"
 
 namespace {
 

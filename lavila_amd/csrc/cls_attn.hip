@@ -6,7 +6,7 @@
 // qkv weight writes them. One workgroup per (b, h): 32 key slots x 8 lanes (8 channels each, one 128-byte row per slot),
 // one pass over K and V with a flash-style running (max, sum, acc) per slot, merged through LDS. HBM-bound: the kernel
 // reads kv once (forward) and reads kv + writes dkv once (backward); f32 arithmetic for both element types.
-#include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -242,9 +242,6 @@ extern "C" int lvl_cls_attn_fwd(const void* q, const void* kv, void* out, float*
   LVL_CHECK_LAUNCH("cls_attn_fwd");
   return LVL_OK;
 }
-
-int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
-                               hipStream_t st);          // cross_attn_mfma.hip
 
 extern "C" int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, int qrep, int Tk, int H,
                                        int dtype, void* stream) {

@@ -1,7 +1,7 @@
 // Library identification, error text and workspace sizing (host-only code).
 #include <stdarg.h>
 
-#include "common.h"
+#include "attn_internal.h"
 
 thread_local char lvl_err_buf[512] = "";
 
@@ -12,15 +12,6 @@ int lvl_fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
-
-int lvl_ln_bwd_parts();
-int lvl_gelu_bwd_row_blocks();
-int lvl_qkv_bias_row_blocks();
-int lvl_colsum_mid_rows();
-int lvl_gate_bwd_parts();
-int lvl_dp_dy_parts();
-int64_t lvl_wgrad_workspace_floats(int64_t N, int64_t K);
-int64_t lvl_linear_tn_workspace_floats(int64_t M, int64_t N);
 
 // Compute units the persistent kernels (lvl_linear_tn, lvl_linear_wgrad) size their grids for; 0 = all of the device.
 static std::atomic<int> g_cu_limit{0};
@@ -89,11 +80,10 @@ extern "C" int64_t lvl_workspace_floats(const char* op, int64_t rows, int64_t co
   if (!strcmp(op, "droppath_add_layernorm_bwd"))
     return (int64_t)(lvl_ln_bwd_parts() + lvl_colsum_mid_rows()) * 3 * cols + (int64_t)(lvl_dp_dy_parts() + lvl_colsum_mid_rows()) * cols;
   if (!strcmp(op, "bias_quickgelu_bwd")) return (int64_t)(lvl_gelu_bwd_row_blocks() + lvl_colsum_mid_rows()) * cols;
-  if (!strcmp(op, "divided_attn_fwd")) return rows * 64 * 66;   // <= 64 CLS-row partial records per (b,h)
-  // delta [B*H, T] + the cls token's partial gradient records: <= 64 slots of [192] per (b, h) (one per frame / per
-  // location chunk, added up in order by cls_grad_finalize_kernel)
-  if (!strcmp(op, "divided_attn_bwd")) return rows * cols + rows * 192 * 64;
-  if (!strcmp(op, "causal_attn_bwd")) return rows * cols;    // delta [B*H, L]
+  // rows = B*H, cols = T: the CLS-row workspace contract of attn_internal.h
+  if (!strcmp(op, "divided_attn_fwd")) return lvl_cls_fwd_ws_floats(rows);
+  if (!strcmp(op, "divided_attn_bwd")) return lvl_cls_bwd_ws_floats(rows, cols, true);
+  if (!strcmp(op, "causal_attn_bwd")) return lvl_cls_bwd_ws_floats(rows, cols, false);    // delta [B*H, L]
   if (!strcmp(op, "qkv_bias_grad")) return (int64_t)(lvl_qkv_bias_row_blocks() + lvl_colsum_mid_rows()) * 2 * cols;   // cols = D
   if (!strcmp(op, "linear_wgrad")) return lvl_wgrad_workspace_floats(rows, cols);   // rows = N (out), cols = K (in); -1: no tiling
   if (!strcmp(op, "linear_tn")) return lvl_linear_tn_workspace_floats(rows, cols);   // rows = M, cols = N

@@ -18,6 +18,7 @@
 //         fragment (j = k*16 + g*4 + r) share one Philox call, generated where the fragment is packed; nothing is stored.
 #include "attn_mfma_common.h"
 #include "dropout.h"
+#include "internal.h"
 
 using namespace attn_mfma;
 

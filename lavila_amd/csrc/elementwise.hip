@@ -1,9 +1,6 @@
 // bias+QuickGELU (fwd/bwd), patch gather (patchify) and token assembly, gfx950.
 // All HBM-bound single-pass kernels: 16 B per lane, consecutive lanes on consecutive vectors.
-#include "common.h"
-
-int lvl_launch_column_reduce(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
-                             float* out2, hipStream_t st);
+#include "internal.h"
 
 namespace {
 
@@ -588,15 +585,10 @@ extern "C" int lvl_vec_mat_f32(const float* v, const float* W, float* out, int N
 }
 
 int lvl_qkv_bias_row_blocks() { return kBiasGradRowBlocks; }
-int lvl_colsum_mid_rows();
 int64_t lvl_qkv_bias_ws_floats(int D) { return (int64_t)(kBiasGradRowBlocks + lvl_colsum_mid_rows()) * 2 * D; }
 
 // Column sums of the q third of dqkv (-> dbias[0, D)) and / or of dout (-> dbias[2D, 3D)); a null source is skipped and its
 // third of dbias left untouched. ws: lvl_qkv_bias_ws_floats.
-int lvl_launch_column_reduce_tail(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
-                                  float* out2, float* zero_dst, const float* copy_src, float* copy_dst, int tail_n,
-                                  hipStream_t st);
-
 // zero_k: also write the exact zeros of the k third (dbias[D, 2D)); v_src: a ready-made v third to copy into dbias[2D, 3D)
 // (only meaningful when dout is null) -- both ride on the reduction's second stage.
 int lvl_qkv_bias_sources(const void* dqkv, const void* dout, float* dbias, float* ws, int64_t rows, int D, int dtype,

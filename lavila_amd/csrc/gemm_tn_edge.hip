@@ -26,7 +26,7 @@
 //   * rows at or behind M (last row tile): the LOADS re-read row M-1 (clamped row index, as the main kernel's xclamp
 //     does), the STORES are skipped. W rows and bias entries are always inside [n_first, N): N % 64 == 0.
 // Resources (gfx950, hipcc -O3): see DESIGN.md, "Ragged widths"; no scratch.
-#include "common.h"
+#include "internal.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 ge_bf16x8;
 typedef __attribute__((ext_vector_type(16))) float ge_f32x16;

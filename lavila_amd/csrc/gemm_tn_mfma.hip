@@ -79,14 +79,7 @@
 // which a sometimes-skipped store would break.
 #include <type_traits>
 
-#include "common.h"
-
-int lvl_debug_late_mod();
-int lvl_colsum_mid_rows();
-int lvl_launch_column_reduce(const float* part, int nparts, int width, int seg, float* mid, float* out0, float* out1,
-                             float* out2, hipStream_t st);
-int lvl_launch_tn_edge(const void* x, const void* w, const float* bias, void* y, int64_t M, int N, int K, int n_first,
-                       hipStream_t st);
+#include "internal.h"
 
 // the LDS-DMA fills set M0 inside inline asm and say so in the clobber list; this kernel has no other M0 user
 #pragma clang diagnostic ignored "-Winline-asm"

@@ -8,7 +8,7 @@
 // Algorithmic bytes per row (E = element size): fwd cols*E*(n_in + n_out), bwd cols*E*(1 + n_in + 1).
 #include <stdlib.h>
 
-#include "common.h"
+#include "internal.h"
 
 // The general and the exact-width kernels must agree to the bit (activation checkpointing recomputes a forward that may take
 // the other instantiation): no implicit contraction in this file, every fused multiply-add is written as one, and each

@@ -2,9 +2,7 @@
 // wgrad_mfma.hip (the 6x6 and 8x4 wave tiles of the towers and the base decoder; the design notes are in its header) and
 // wgrad_160.hip (the 5x5 and 8x5 wave tiles of the 1600-family widths).
 #pragma once
-#include "common.h"
-
-int lvl_debug_late_mod();
+#include "internal.h"
 
 // the LDS-DMA fills set M0 inside inline asm and say so in the clobber list; this kernel has no other M0 user
 #pragma clang diagnostic ignored "-Winline-asm"

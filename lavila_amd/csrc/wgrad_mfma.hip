@@ -38,10 +38,6 @@
 // otherwise). Bit-reproducible runs: LAVILA_DYNAMIC_TILES=0 (static plan; the default on a single GPU).
 #include "wgrad_kernel.h"
 
-// the 160-family instantiations (wgrad_160.hip); cfg counts from kFirstCfg160
-int lvl_launch_wgrad_160(int cfg, int tiles_k, int ntiles, int S, const void* dy, const void* x, float* part, float* bpart,
-                         int64_t M, int N, int K, unsigned* sched, hipStream_t st);
-
 namespace {
 
 // dw[e] = sum_s part[s][e] (+ the < 32 tail rows m >= M_main, which the tiled kernel skips), db[n] likewise
