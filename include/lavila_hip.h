@@ -524,6 +524,24 @@ int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* v, const vo
                            int64_t kv_ctx_stride, int causal, uint64_t seed, uint32_t site, float p, int dtype,
                            void* stream);
 
+/* ---- packed caption rows: the narrator's teacher-forced pass on the rows that carry a label -------------------------
+ * A batch of B captions of up to L positions keeps len_b = cu[b + 1] - cu[b] leading rows each; cu [B + 1] int32 (device),
+ * cu[0] = 0, R = cu[B] packed rows.
+ *   lvl_rows_pack:   dst[cu[b] + i, 0:D] = src[b, i, 0:D] for i < len_b. src element (b, i, c) at b * src_batch_stride +
+ *                    i * src_row_stride + c; dst [R, D] contiguous.
+ *   lvl_rows_unpack: dst[b, i, 0:D] = i < len_b ? src[cu[b] + i, 0:D] : 0 for EVERY b < B, i < L (every addressed element is
+ *                    written on every call; nothing outside columns [0, D) of a row, nothing behind row B L - 1). src [R, D]
+ *                    contiguous, dst strided like lvl_rows_pack's src; its batches must not overlap.
+ * Each is the other's adjoint: the backward of one is the other on the gradient. dtype LVL_BF16 or LVL_F32; rows move as
+ * 16-byte words, bit for bit: D % 8 == 0, strides multiples of 8 elements, src / dst 16-byte aligned, B L <= 2^31 - 1.
+ * The host validates the lengths (it holds them); for memory safety the kernel clamps len_b into [0, L] and cu[b] into
+ * [0, b L], so no access leaves the first B L packed rows or the rectangle whatever `cu` holds. Plain vector loads and
+ * stores, no atomics, no workspace; the grid is capped at 4096 workgroups of 256 threads that stride over the rows. */
+int lvl_rows_pack(const void* src, int64_t src_batch_stride, int64_t src_row_stride, const int32_t* cu, int B, int L, int D,
+                  void* dst, int dtype, void* stream);
+int lvl_rows_unpack(const void* src, const int32_t* cu, int B, int L, int D, void* dst, int64_t dst_batch_stride,
+                    int64_t dst_row_stride, int dtype, void* stream);
+
 /* lvl_sample_next_token: everything VCLM_HF.generate does with one step's logits (narrator.py:122-137 and the warpers
  * of :368-389 = transformers' Temperature / TopK / TopP logits warpers with min_tokens_to_keep = 1), one workgroup per
  * caption, the row resident in LDS as 16-bit keys -- no sort, no [rows, vocab] temporaries:

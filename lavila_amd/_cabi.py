@@ -104,6 +104,8 @@ SIGNATURES = {
     'lvl_gated_add_layernorm_bwd_drop': (_I, [_P] * 14 + [_I, _I, _U64, _U32, _F, _I, _P]),
     'lvl_attn_rows_drop_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
     'lvl_attn_rows_drop_bwd': (_I, [_P] * 7 + [_I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_rows_pack': (_I, [_P, _L, _L, _P, _I, _I, _I, _P, _I, _P]),
+    'lvl_rows_unpack': (_I, [_P, _P, _I, _I, _I, _P, _L, _L, _I, _P]),
 }
 
 _lib = None

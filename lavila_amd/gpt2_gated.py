@@ -47,6 +47,13 @@ per training forward comes from torch's CPU generator (torch.manual_seed reprodu
 `fixed_dropout_seed(seed)` pins it. The distribution is the reference's, the random stream is not. A
 probability of 0 takes exactly the path without dropout; inference, decoding, .eval() and no_grad never drop.
 
+Packed rows: `forward(..., row_lengths=[B] lengths)` runs the plan on the first len_b positions of every sequence only, as
+R = sum len_b packed rows (PackedRows over lvl_rows_pack / lvl_rows_unpack, csrc/pack_rows.hip): the embedding is packed, every
+row primitive and the lm_head see R rows, each attention runs its kernels on the zero-filled rectangle [B, longest] between an
+unpack and a pack, and `.logits` keeps its shape with exact zeros at and behind len_b. Both primitive sets take it through the
+one plan; without the keyword nothing of it is reached. What makes it exact for a causal decoder whose dropped positions carry
+ignored labels: DESIGN.md section 4; lavila_amd.narrator.PACK_CAPTIONS switches it on for VCLM_HF.forward.
+
 What the reference's vendored HF class offers beyond this (attention / head masks, token types, past_key_values as
 arguments, pruning, model parallelism, the other heads) raises NotImplementedError.
 """
@@ -280,6 +287,61 @@ def _lay_out(p, model, conv, ln, gate):
     p.ln_f = ln(tr.ln_f)
 
 
+class PackedRows:
+    """The row layout of a forward with `row_lengths`: caption b keeps its first len_b of L positions, the plan's rows are the
+    R = sum len_b kept ones in caption order (ops.pack_rows / ops.unpack_rows over `cu`, the [B + 1] int32 offsets on the
+    device). The attentions run on the rectangle [B, longest] with zeros behind a caption's rows (`around`); the plan hands
+    this object to `cross_attn` where an unpacked forward hands the positions per caption."""
+
+    def __init__(self, lengths, L, device):
+        self.lengths, self.B, self.L = lengths, len(lengths), L
+        self.longest, self.rows = max(lengths), sum(lengths)
+        cu = [0]
+        for n in lengths:
+            cu.append(cu[-1] + n)
+        self.cu = torch.tensor(cu, dtype=torch.int32).to(device)
+
+    def pack(self, x):
+        """[B, positions, W] -> [R, W]."""
+        return ops.pack_rows(x, self.cu, self.rows)
+
+    def unpack(self, y, positions):
+        """[R, W] -> [B, positions, W] with zeros behind every caption's rows (positions >= the longest caption)."""
+        return ops.unpack_rows(y, self.cu, self.B, positions)
+
+    def around(self, attention, y):
+        """attention([B * longest, W] rows of the zero-filled rectangle) -> [B * longest, D], on the packed rows y."""
+        out = attention(self.unpack(y, self.longest).reshape(self.B * self.longest, -1))
+        return self.pack(out.reshape(self.B, self.longest, -1))
+
+
+def _row_lengths_on_host(row_lengths, B, L):
+    """What can be said about `row_lengths` without a read-back: -> (the lengths as a list, or None for a device tensor whose
+    values travel with the forward's one read-back; that tensor as int64 [B], or None)."""
+    if torch.is_tensor(row_lengths):
+        if row_lengths.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f'row_lengths must hold integers, got {row_lengths.dtype}')
+        if row_lengths.dim() != 1 or row_lengths.shape[0] != B:
+            raise ValueError(f'row_lengths must have shape [{B}] (one length per sequence), got {tuple(row_lengths.shape)}')
+        if row_lengths.is_cuda:
+            return None, row_lengths.to(torch.int64)
+        row_lengths = row_lengths.tolist()
+    elif not isinstance(row_lengths, (list, tuple)):
+        raise ValueError(f'row_lengths must be a [B] integer tensor or a list, got {type(row_lengths).__name__}')
+    if len(row_lengths) != B:
+        raise ValueError(f'row_lengths must hold one length per sequence ({B}), got {len(row_lengths)}')
+    if not all(isinstance(n, int) and not isinstance(n, bool) for n in row_lengths):
+        raise ValueError('row_lengths must hold integers')
+    return _checked_row_lengths(row_lengths, L), None
+
+
+def _checked_row_lengths(lengths, L):
+    bad = [n for n in lengths if not 1 <= n <= L]
+    if bad:
+        raise ValueError(f'row_lengths must lie in [1, {L}] (the sequence length), got {bad[0]}')
+    return [int(n) for n in lengths]
+
+
 def cross_attn_rows_raw(q, kv, qrep, heads):
     """lvl_cross_attn_rows_fwd: rows q [rows, D] over the image keys | values kv [rows / qrep, Tk, 2 D] -> [rows, D]."""
     out = torch.empty_like(q)
@@ -351,29 +413,38 @@ class _Pack:
             y = torch.addmm(b, x2, w)
         return y if act is None else self.act(y, act)
 
-    def logits(self, h2):
-        """lm_head (no bias, gpt2_gated.py:1010,1139): [rows, D] -> [rows, vocab] (a view of the padded product)."""
+    def logits(self, h2, rows=None):
+        """lm_head (no bias, gpt2_gated.py:1010,1139): [rows, D] -> [rows, vocab] (a view of the padded product); of packed
+        rows (`rows`: their PackedRows) -> [B, L, vocab], the padded product unpacked with zero rows behind every caption."""
+        full = self._padded_logits(h2)
+        if rows is None:
+            return full[:, :self.vocab]
+        if full.shape[1] % 8:                           # the library GEMM against an unpadded head (LAVILA_F32_MFMA=0)
+            full = F.pad(full, (0, -full.shape[1] % 8))
+        return rows.unpack(full, rows.L)[:, :, :self.vocab]
+
+    def _padded_logits(self, h2):
         if self.dtype == torch.bfloat16:
             # 50432 x 768 (profiles/r03_skinny_variants.json, in-graph): up to 128 rows lvl_linear_skinny's LDS-staged tiles
             # (17 us; the 256-column-panel kernel 32), beyond that the panel kernel (72 us at 640 rows; tiles 87-120)
             if h2.shape[0] > 128 and ops._tn_ok(h2.shape[0], self.head.shape[0], self.D) and self.head.shape[0] >= 8192:
-                return ops.linear_tn_raw(h2, self.head, None, C.EPI_BIAS)[:, :self.vocab]
+                return ops.linear_tn_raw(h2, self.head, None, C.EPI_BIAS)
             if h2.shape[0] <= SKINNY_MAX_ROWS and self.D % 32 == 0:
-                return self._skinny(h2, self.head, None, None)[:, :self.vocab]
+                return self._skinny(h2, self.head, None, None)
             if ops._tn_ok(h2.shape[0], self.head.shape[0], self.D):
-                return ops.linear_tn_raw(h2, self.head, None, C.EPI_BIAS)[:, :self.vocab]
+                return ops.linear_tn_raw(h2, self.head, None, C.EPI_BIAS)
         elif self.head3 is not None:                    # float32: f32-class mode of the own kernels
-            return ops.linear_f32_rows(h2, self.head3)[:, :self.vocab]
-        return F.linear(h2, self.head)[:, :self.vocab]
+            return ops.linear_f32_rows(h2, self.head3)
+        return F.linear(h2, self.head)
 
-    def embed(self, ids, L, pos_dev=None):
+    def embed(self, ids, L, pos_dev=None, rows=None):
         ids = ids.reshape(-1).contiguous()
         C.require_device(ids)
         out = torch.empty(ids.shape[0], self.D, dtype=self.dtype, device=ids.device)
         C.check(C.lib().lvl_gpt2_embed(C.ptr(ids), C.ptr(self.wte), C.ptr(self.wpe), C.ptr(pos_dev), C.ptr(out),
                                        ids.shape[0], L, self.D, self.vocab, self.positions, C.dtype_code(out),
                                        C.stream_ptr()), 'lvl_gpt2_embed')
-        return out
+        return out if rows is None else rows.pack(out.reshape(-1, L, self.D))
 
     def add_ln(self, res, y, gate, ln):
         """res <- res + gate * y (in place) -> (res, LayerNorm(res))."""
@@ -388,6 +459,8 @@ class _Pack:
         return u
 
     def cross_attn(self, q, kv, qrep):
+        if isinstance(qrep, PackedRows):
+            return qrep.around(lambda rect: cross_attn_rows_raw(rect, kv, qrep.longest, self.heads), q)
         return cross_attn_rows_raw(q, kv, qrep, self.heads)
 
     def gemm_ln(self, x, pend, entry, act=None, fuse=True):
@@ -426,7 +499,8 @@ def _image_kv(p, enc):
 
 def _run_blocks(p, x, xkv, qrep, self_attention, fuse_ln=True):
     """The block stack on rows x [rows, D] -> LayerNorm_f of the final residual. xkv: per block image keys / values
-    or None (no encoder states: plain GPT-2, gpt2_gated.py:432); `self_attention(i, qkv)` -> [rows, D]. Every residual
+    or None (no encoder states: plain GPT-2, gpt2_gated.py:432); qrep: the rows per clip, or the PackedRows of a forward on
+    packed caption rows (handed to p.cross_attn as it is); `self_attention(i, qkv)` -> [rows, D]. Every residual
     add + LayerNorm is PENDING as (y, gate, ln) until the Conv1D that reads it (p.gemm_ln -> (product, new residual)).
     Before every primitive that has a dropout site the plan sets `p.site`: of the pending add's y, or of the attention
     probabilities -- 1 + 6 i + k in the reference's execution order (k: 0 cross-attention probabilities, 1 cross c_proj,
@@ -740,10 +814,11 @@ class _LmHeadFn(torch.autograd.Function):
     """logits = h W^T for the (tied) lm_head weight W [vocab, D]: the vocabulary is padded with zero rows to the GEMM's
     256-column tiles (as the inference image is), the padded bf16 image and its transpose are cast per forward from the
     current parameter (nothing cached, nothing stale) and the padded columns are dropped again. dW [vocab, D] comes back as
-    a gradient of the weight: tied, autograd adds it to the embedding's."""
+    a gradient of the weight: tied, autograd adds it to the embedding's. `padded`: the whole padded product is the result
+    (what a forward on packed rows unpacks; its gradient arrives in that shape too)."""
 
     @staticmethod
-    def forward(ctx, h2, weight):
+    def forward(ctx, h2, weight, padded=False):
         V, D = weight.shape
         rows = h2.shape[0]
         w = _pad_rows(weight.detach().to(torch.bfloat16), 256)
@@ -751,26 +826,31 @@ class _LmHeadFn(torch.autograd.Function):
         ctx.own = ops._tn_ok(rows, Vp, D) and ops._tn_rows_ok(rows, D, Vp)       # the input gradient has N = D: ragged at 1600
         h2 = h2 if h2.is_contiguous() else h2.contiguous()
         ctx.save_for_backward(h2, w)
-        ctx.meta = (V, weight.dtype)
+        ctx.meta = (V, weight.dtype, padded)
         if ctx.own:
-            return ops.linear_tn_raw(h2, w, None, C.EPI_BIAS)[:, :V]
-        ops.warn_once(('lm_head', V, D), f'decoder lm_head [{D}->{V}] on {rows} rows runs on the library GEMM')
-        with torch.autocast('cuda', enabled=False):
-            return F.linear(h2, w)[:, :V]
+            full = ops.linear_tn_raw(h2, w, None, C.EPI_BIAS)
+        else:
+            ops.warn_once(('lm_head', V, D), f'decoder lm_head [{D}->{V}] on {rows} rows runs on the library GEMM')
+            with torch.autocast('cuda', enabled=False):
+                full = F.linear(h2, w)
+        return full if padded else full[:, :V]
 
     @staticmethod
     def backward(ctx, dlogits):
         h2, w = ctx.saved_tensors
-        V, wdt = ctx.meta
-        dl = torch.zeros(h2.shape[0], w.shape[0], dtype=torch.bfloat16, device=h2.device)
-        dl[:, :V] = dlogits
+        V, wdt, padded = ctx.meta
+        if padded:
+            dl = dlogits.to(torch.bfloat16).contiguous()
+        else:
+            dl = torch.zeros(h2.shape[0], w.shape[0], dtype=torch.bfloat16, device=h2.device)
+            dl[:, :V] = dlogits
         dh = dw = None
         with torch.autocast('cuda', enabled=False):
             if ctx.needs_input_grad[0]:
                 dh = ops.linear_tn_rows(dl, w.t().contiguous()) if ctx.own else dl @ w
             if ctx.needs_input_grad[1]:
                 dw = ops._wgrad(dl, h2, wdt)[:V]
-        return dh, dw
+        return dh, dw, None
 
 
 class _TrainOps:
@@ -787,11 +867,12 @@ class _TrainOps:
         self.seed = _draw_seed() if any(pdrop) else 0
         self.site = None                              # set by the plan before every primitive that has a dropout site
 
-    def embed(self, ids, L):
+    def embed(self, ids, L, rows=None):
         x = ops.text_embed(ids, self.wte, self.wpe, self.dtype)
         if x is None:                                 # tables the gather kernel does not take (bf16 parameters, width > 2048)
             x = (F.embedding(ids, self.wte) + self.wpe[:L]).to(self.dtype)
-        x = x.reshape(-1, self.D)
+        # packed rows: the embedding dropout site then indexes the PACKED rows (element = packed row * D + column)
+        x = x.reshape(-1, self.D) if rows is None else rows.pack(x.reshape(-1, L, self.D))
         return _DropoutFn.apply(x, self.seed, 0, self.p_embd) if self.p_embd else x
 
     def self_attn(self, i, qkv, L):
@@ -815,12 +896,16 @@ class _TrainOps:
         return self.gemm(h, m, act), x
 
     def cross_attn(self, q, kv, qrep):
+        if isinstance(qrep, PackedRows):              # the rectangle's (ctx, h, i, j) index serves the dropout site
+            return qrep.around(lambda rect: self.cross_attn(rect, kv, qrep.longest), q)
         if self.p_attn:
             return _AttnRowsDropFn.apply(q, kv, qrep, self.heads, self.seed, self.site, self.p_attn)
         return _CrossAttnRowsFn.apply(q, kv, qrep, self.heads)
 
-    def logits(self, h2):
-        return _LmHeadFn.apply(h2, self.head)
+    def logits(self, h2, rows=None):
+        if rows is None:
+            return _LmHeadFn.apply(h2, self.head)
+        return rows.unpack(_LmHeadFn.apply(h2, self.head, True), rows.L)[:, :, :self.vocab]
 
 
 class DecodeSession:
@@ -1008,7 +1093,11 @@ class GPT2LMHeadModel(nn.Module):
 
     def forward(self, input_ids=None, past_key_values=None, attention_mask=None, token_type_ids=None, position_ids=None,
                 head_mask=None, inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None, labels=None,
-                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+                use_cache=None, output_attentions=None, output_hidden_states=None, return_dict=None, row_lengths=None):
+        """`row_lengths` ([B] integers on the device or the host, or a list; 1 <= len_b <= L): only the first len_b positions
+        of sequence b run through the decoder, as packed rows (PackedRows); `.logits` keeps its shape, with exact zeros at
+        and behind position len_b. Exact for what a causal decoder computes at the kept positions; it is not
+        `attention_mask`, which stays refused."""
         unsupported = dict(past_key_values=past_key_values, attention_mask=attention_mask, token_type_ids=token_type_ids,
                            position_ids=position_ids, head_mask=head_mask, inputs_embeds=inputs_embeds,
                            encoder_attention_mask=encoder_attention_mask)
@@ -1018,17 +1107,26 @@ class GPT2LMHeadModel(nn.Module):
                                       'not on the narrator path (cached decoding: decode_session())')
         if input_ids is None:
             raise ValueError('You have to specify input_ids')
-        train = self._trains(encoder_hidden_states)
-        p = self._train_ops() if train else self._pack()
         shape = tuple(input_ids.shape)
         L = shape[-1]
+        lengths = lengths_dev = None
+        if row_lengths is not None:
+            lengths, lengths_dev = _row_lengths_on_host(row_lengths, input_ids.numel() // max(L, 1), L)
+        train = self._trains(encoder_hidden_states)
+        p = self._train_ops() if train else self._pack()
         if L > p.positions:
             raise ValueError(f'sequence of {L} tokens exceeds the decoder\'s {p.positions} positions')
         ids = input_ids.reshape(-1, L).contiguous()
         B = ids.shape[0]
-        lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())      # ONE read-back; the gather kernels clamp
+        if lengths_dev is None:
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(ids)).tolist())  # ONE read-back; the gather kernels clamp
+        else:                                                                    # ... in which device lengths travel along
+            C.require_device(ids, lengths_dev)
+            lo, hi, *lengths = torch.cat([torch.stack(torch.aminmax(ids)), lengths_dev]).tolist()
+            lengths = _checked_row_lengths(lengths, L)
         if lo < 0 or hi >= p.vocab:
             raise IndexError(f'input_ids out of range [0, {p.vocab}): min {lo}, max {hi}')
+        rows = None if lengths is None else PackedRows(lengths, L, ids.device)
         enc = encoder_hidden_states
         if enc is not None:
             enc = ops.lowp(enc)
@@ -1039,12 +1137,18 @@ class GPT2LMHeadModel(nn.Module):
             if enc is not None and any(e['cross'] for e in p.blocks):
                 xkv, qrep = _image_kv(p, enc), L
 
-            def self_attention(i, qkv):
+            def self_attention(i, qkv, L=L):
                 if train:
                     return p.self_attn(i, qkv, L)
                 return ops.causal_attention(qkv.reshape(B, L, 3 * p.D), p.heads).reshape(B * L, p.D)
-            h = _run_blocks(p, p.embed(ids, L), xkv, qrep, self_attention)
-            logits = p.logits(h).reshape(*shape, p.vocab)
+            if rows is None:
+                h = _run_blocks(p, p.embed(ids, L), xkv, qrep, self_attention)
+                logits = p.logits(h).reshape(*shape, p.vocab)
+            else:       # the plan on the kept rows; each attention on the zero-filled rectangle [B, longest caption]
+                def packed_self_attention(i, qkv):
+                    return rows.around(lambda rect: self_attention(i, rect, rows.longest), qkv)
+                h = _run_blocks(p, p.embed(ids, L, rows=rows), xkv, rows if xkv is not None else None, packed_self_attention)
+                logits = p.logits(h, rows).reshape(*shape, p.vocab)
             loss = None
             if labels is not None:                              # gpt2_gated.py:1142-1148
                 loss = F.cross_entropy(logits[..., :-1, :].reshape(-1, p.vocab).float(), labels[..., 1:].reshape(-1))

@@ -54,6 +54,7 @@ import torch
 import torch.distributed as dist
 
 from . import models as _models
+from . import narrator as _narrator
 from . import ops
 
 _active = threading.local()
@@ -194,6 +195,11 @@ class GraphedTrainStep:
                                       'aborts the process). Hand over the bare module: with a process group initialised '
                                       'the step keeps the collectives between its graph segments and averages the '
                                       'gradients itself')
+        bare = net.module if hasattr(net, 'module') else net
+        if isinstance(bare, _narrator.VCLM_HF) and _narrator.pack_captions_enabled():
+            raise NotImplementedError('GraphedTrainStep: a VCLM_HF that packs its caption rows cannot be replayed (the row '
+                                      'count of every step depends on its captions): unset LAVILA_PACK_CAPTIONS / '
+                                      'narrator.PACK_CAPTIONS for the graphed step, or run the eager loop')
         if not torch.cuda.is_available():
             raise RuntimeError('GraphedTrainStep needs a HIP device (hipGraph capture)')
         for grp in optimizer.param_groups:

@@ -30,6 +30,28 @@ from . import ops
 from .timesformer import SpaceTimeTransformer, _like_caller
 
 
+# Packed caption rows in VCLM_HF.forward: None = follow LAVILA_PACK_CAPTIONS in the environment ('1' = on), True / False = set
+# here. Read per call (pack_captions_enabled), never cached. On, the teacher-forced decoder pass runs only on the positions up to
+# every caption's last non-pad label (gpt2_gated.GPT2LMHeadModel.forward(row_lengths=...)): the positions behind it carry pad
+# labels, which CaptionLoss ignores, and the causal mask keeps them from every position in front -- same loss, same gradients.
+PACK_CAPTIONS = None
+
+
+def pack_captions_enabled():
+    if PACK_CAPTIONS is not None:
+        return bool(PACK_CAPTIONS)
+    return os.environ.get('LAVILA_PACK_CAPTIONS', '0') == '1'
+
+
+def caption_row_lengths(labels, pad_id):
+    """labels [B, L] -> [B] int64: len_b = max(1, 1 + the last index i with labels[b, i] != pad_id), the decoder positions of
+    caption b whose label, or a later one, counts in CaptionLoss. Pad-id tokens INSIDE a caption stay (GPT-2's id 0 is also
+    the token "!", and its row feeds the later positions); a caption of pad labels only keeps one row."""
+    L = labels.shape[1]
+    index = torch.arange(1, L + 1, device=labels.device)
+    return ((labels != pad_id) * index).amax(dim=1).clamp_(min=1)
+
+
 class LayerNorm(nn.Module):
     """coca.py:25-34: LayerNorm without a learned bias (`gamma` parameter, `beta` buffer of zeros), eps 1e-5."""
 
@@ -152,6 +174,8 @@ def sample_next_token(logits, top_k, top_p, temperature, target=None, pad_id=-10
 class VCLM_HF(nn.Module):
     """narrator.py:31-147: same constructor; encode_image, forward and generate run on the HIP path (`text_decoder`:
     a lavila_amd.gpt2_gated.GPT2LMHeadModel), and so do beam_sample / group_beam_search (round 4)."""
+    # the id captions are padded with (MyGPT2Tokenizer.pad_token_id, tokenizer.py:211-236): what packed captions trim behind
+    caption_pad_id = 0
 
     def __init__(self, vision_width: int, vision_model: nn.Module, text_width: int, text_decoder: nn.Module,
                  num_img_queries=256, dim_head=64, heads=8, **kwargs):
@@ -189,9 +213,11 @@ class VCLM_HF(nn.Module):
         else:
             self.text_decoder.gradient_checkpointing_disable()
         text, labels = text[:, :-1], text[:, 1:]
+        # packed captions: the lengths stay on the device and travel in the decoder's one read-back
+        packed = dict(row_lengths=caption_row_lengths(labels, self.caption_pad_id)) if pack_captions_enabled() else {}
         with ops.model_forward():                 # tower, pooler and decoder share one weight-copy generation per step
             image_tokens = self.encode_image(image, use_checkpoint=use_checkpoint)
-            logits = self.text_decoder(text.contiguous(), encoder_hidden_states=image_tokens).logits
+            logits = self.text_decoder(text.contiguous(), encoder_hidden_states=image_tokens, **packed).logits
         return {'text_tokens_logits': logits.permute(0, 2, 1), 'labels': labels}
 
     @staticmethod

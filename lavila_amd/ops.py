@@ -1384,6 +1384,86 @@ def text_embed(text, table, pos, out_dtype):
 
 
 # --------------------------------------------------------------------------------------------------
+# packed caption rows (csrc/pack_rows.hip): [B, L, D] <-> the len_b leading rows of every caption, [R, D]
+# --------------------------------------------------------------------------------------------------
+def _row_view(t, what):
+    """A [B, L, D] bf16 / f32 device view the row kernels address in place: unit column stride, D and both row strides
+    multiples of 8 elements, 16-byte aligned base."""
+    if not t.is_cuda:
+        C.require_device(t)                           # raises: there is no CPU fallback
+    if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] % 8 or t.stride(0) % 8 or t.stride(1) % 8 or t.stride(1) < t.shape[2]:
+        raise C.HipExtensionError(f'{what}: a [B, L, D] view with unit column stride, D and the row strides multiples of 8 '
+                                  f'is needed; got {tuple(t.shape)} with strides {tuple(t.stride())}')
+    return t
+
+
+def _row_offsets(cu, B):
+    C.require_device(cu)
+    if cu.dtype != torch.int32 or cu.numel() != B + 1:
+        raise C.HipExtensionError(f'row offsets must be {B + 1} int32 values, got {tuple(cu.shape)} {cu.dtype}')
+    return cu
+
+
+def rows_pack_raw(src, cu, rows: int):
+    """lvl_rows_pack: src [B, L, D] (a strided view is read in place), cu [B + 1] int32 on the device with cu[B] == rows (the
+    caller holds the lengths) -> [rows, D]: caption b's first cu[b + 1] - cu[b] rows at cu[b]."""
+    B, L, D = _row_view(src, 'rows_pack').shape
+    out = torch.empty(int(rows), D, dtype=src.dtype, device=src.device)
+    C.check(C.lib().lvl_rows_pack(C.ptr(src), src.stride(0), src.stride(1), C.ptr(_row_offsets(cu, B)), B, L, D, C.ptr(out),
+                                  C.dtype_code(src), C.stream_ptr()), 'lvl_rows_pack')
+    return out
+
+
+def rows_unpack_raw(src, cu, B: int, L: int, out=None):
+    """lvl_rows_unpack: src [R, D] contiguous -> out [B, L, D] (fresh, or a strided view written in place): caption b's
+    rows followed by zeros; every element of out[:, :, :D] is written."""
+    C.require_device(src)
+    D = src.shape[1]
+    if out is None:
+        out = torch.empty(B, L, D, dtype=src.dtype, device=src.device)
+    if tuple(_row_view(out, 'rows_unpack').shape) != (B, L, D) or out.dtype != src.dtype:
+        raise C.HipExtensionError(f'rows_unpack: destination {tuple(out.shape)} {out.dtype} for [{B}, {L}, {D}] {src.dtype}')
+    C.check(C.lib().lvl_rows_unpack(C.ptr(src), C.ptr(_row_offsets(cu, B)), B, L, D, C.ptr(out), out.stride(0), out.stride(1),
+                                    C.dtype_code(src), C.stream_ptr()), 'lvl_rows_unpack')
+    return out
+
+
+class _PackRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cu, rows):
+        ctx.cu, ctx.shape = cu, x.shape[:2]           # an index tensor (no gradient, not an output): a plain attribute
+        return rows_pack_raw(x, cu, rows)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return rows_unpack_raw(dy.contiguous(), ctx.cu, *ctx.shape), None, None
+
+
+class _UnpackRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, cu, B, L):
+        ctx.cu, ctx.rows = cu, y.shape[0]
+        return rows_unpack_raw(y.contiguous(), cu, B, L)
+
+    @staticmethod
+    def backward(ctx, dx):
+        if dx.stride(2) != 1 or dx.stride(1) % 8 or dx.stride(0) % 8:
+            dx = dx.contiguous()
+        return rows_pack_raw(dx, ctx.cu, ctx.rows), None, None, None
+
+
+def pack_rows(x, cu, rows: int):
+    """[B, L, D] -> [rows, D]: the leading cu[b + 1] - cu[b] rows of every caption, in caption order; the backward is
+    unpack_rows on the gradient (zeros for the rows left behind)."""
+    return _PackRowsFn.apply(x, cu, rows)
+
+
+def unpack_rows(y, cu, B: int, L: int):
+    """[R, D] -> [B, L, D], zeros behind every caption's rows; the backward is pack_rows on the gradient."""
+    return _UnpackRowsFn.apply(y, cu, B, L)
+
+
+# --------------------------------------------------------------------------------------------------
 # attention cores
 # --------------------------------------------------------------------------------------------------
 def set_fp8_qk(on: bool):
