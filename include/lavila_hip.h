@@ -626,6 +626,17 @@ int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* 
  * dst_term_stride = rows_padded * cols): dy3 [3M,N] = (h; h; l), x3 [3M,K] = (h; l; h); dw is float32 either way. */
 int lvl_linear_wgrad(const void* dy, const void* x, float* dw, float* dbias, float* ws, uint32_t* sched, int64_t M,
                      int N, int K, int dtype, void* stream);
+/* What lvl_linear_wgrad would launch for (M, N, K) under the current lvl_set_compute_units limit (host-side query, no
+ * device work; without a device the plan is the one of 256 compute units). out[9] = {cfg, tiles_k, ntiles, S, base, rem,
+ * L, nch0, nch1}: tile configuration (index into the kernel's table of workgroup shapes), tiles along K, output tiles,
+ * row splits (ntiles * S workgroups); the M / 32 full row blocks are dealt to the splits as `base` each, the first `rem`
+ * splits one more; with `sched` a unit is claimed in chunks of L row blocks, nch0 / nch1 of them for a unit of base /
+ * base + 1 blocks. M = 0: the plan the workspace is sized for (the largest S), row fields zero. LVL_ENOSYS where
+ * lvl_linear_wgrad has no tiling. */
+int lvl_linear_wgrad_plan(int64_t M, int N, int K, int* out);
+/* The (split, tile) pair = split * ntiles + tile that workgroup `bid` of a launch of `pairs` = ntiles * S workgroups
+ * computes under configuration `cfg` (the kernel's own block decode); negative for arguments out of range. */
+int lvl_linear_wgrad_pair_of_block(int cfg, int pairs, int bid);
 
 /* ---- bias gradient of the qkv Linear that feeds an attention core ------------------------------------------------
  * dbias[3D] = column sums over all rows of the dqkv an attention backward produced (what autograd computes for

@@ -65,6 +65,8 @@ SIGNATURES = {
     'lvl_linear_tn': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     'lvl_linear_tn_ragged': (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
     'lvl_linear_wgrad': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'lvl_linear_wgrad_plan': (_I, [_L, _I, _I, _c.POINTER(_I)]),
+    'lvl_linear_wgrad_pair_of_block': (_I, [_I, _I, _I]),
     'lvl_cast_transpose': (_I, [_P, _P, _P, _I, _I, _P]),
     'lvl_cast_transpose_multi': (_I, [_P, _I, _L, _P]),
     'lvl_split_bf16x3': (_I, [_P, _P, _L, _I, _L, _L, _L, _I, _P]),

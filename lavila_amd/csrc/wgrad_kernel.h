@@ -30,6 +30,21 @@ __device__ __forceinline__ wg_f32x4 mfma16(uint4 a, uint4 b, wg_f32x4 c) {
 // (L even), nch0 / nch1 of them for a unit of base / base + 1 blocks.
 struct RowPlan { int base, rem, L, nch0, nch1, late_mod; };
 
+// XCD-aware decode of a block id into one of the P = ntiles * S split-major (split, tile) pairs: consecutive block ids
+// alternate XCDs, so XCD x = bid % 8 is given a contiguous range of the pairs: the workgroups that stream the same rows
+// sit behind the same L2. One definition for the kernel and for lvl_linear_wgrad_pair_of_block (the tests' view of it).
+template <bool ANY_PAIRS>
+__host__ __device__ __forceinline__ int pair_of_block(int P, int bid) {
+  if constexpr (!ANY_PAIRS) {
+    return (bid & 7) * (P >> 3) + (bid >> 3);      // XCD x owns [x*P/8, (x+1)*P/8); make_plan: P is a multiple of 8
+  } else {
+    // the 160-family: 4800 x 1600 is 150 tiles at S = 1, so its plans take ANY number of pairs. XCD x owns q (+ 1 for
+    // the first r XCDs) consecutive pairs, P = 8 q + r -- as many as there are block ids congruent to x: a bijection
+    const int x8 = bid & 7, q = P >> 3, r = P & 7;
+    return (x8 < r ? x8 * (q + 1) : r * (q + 1) + (x8 - r) * q) + (bid >> 3);
+  }
+}
+
 template <int WN, int WK, int TA, int TB>
 struct Geo {
   static constexpr int NW = WN * WK, NT = 64 * NW;
@@ -55,19 +70,8 @@ __global__ __launch_bounds__(64 * WN * WK) void wgrad_kernel(const uint16_t* __r
   extern __shared__ __attribute__((aligned(16))) uint16_t smem[];     // [NSTAGE][A image | B image | dump]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wn = wave % WN, wk = wave / WN;
-  // XCD-aware decode: consecutive block ids alternate XCDs, so XCD x = bid % 8 is given the contiguous range
-  // [x*P/8, (x+1)*P/8) of the split-major (split, tile) pairs, P = ntiles*S: the workgroups that stream the same
-  // rows sit behind the same L2
   const int bid = blockIdx.x;
-  int pair;
-  if constexpr (TA != 5 && TB != 5) {
-    pair = (bid & 7) * ((ntiles * S) >> 3) + (bid >> 3);      // make_plan: ntiles * S is a multiple of 8
-  } else {
-    // the 160-family: 4800 x 1600 is 150 tiles at S = 1, so its plans take ANY number of pairs. XCD x owns q (+ 1 for
-    // the first r XCDs) consecutive pairs, P = 8 q + r -- as many as there are block ids congruent to x: a bijection
-    const int P = ntiles * S, x8 = bid & 7, q = P >> 3, r = P & 7;
-    pair = (x8 < r ? x8 * (q + 1) : r * (q + 1) + (x8 - r) * q) + (bid >> 3);
-  }
+  const int pair = pair_of_block<TA == 5 || TB == 5>(ntiles * S, bid);
   const int split = pair / ntiles, tile = pair % ntiles;
   const int n0 = (tile / tiles_k) * G::TN, k0 = (tile % tiles_k) * G::TK;
   const int64_t steps_total = M / MS;      // full row blocks; the < 32 tail rows are added by wgrad_reduce_kernel

@@ -146,6 +146,25 @@ int64_t lvl_wgrad_workspace_floats(int64_t N, int64_t K) {
   return (int64_t)p.S * N * K + (int64_t)p.S * N;
 }
 
+// Host-only view of what a launch would run: the make_plan / row_plan results of lvl_linear_wgrad itself (no device code)
+extern "C" int lvl_linear_wgrad_plan(int64_t M, int N, int K, int* out) {
+  LVL_REQUIRE(out != nullptr, "linear_wgrad_plan: null pointer");
+  LVL_REQUIRE(M >= 0 && N > 0 && K > 0, "linear_wgrad_plan: M >= 0 and N, K > 0 needed");
+  const Plan p = make_plan(N, K, M);
+  if (!p.ok) return lvl_fail(LVL_ENOSYS, "linear_wgrad: no tiling for N=%d K=%d (multiples of 192/288/384, 128/256 or 160/320 needed)", N, K);
+  RowPlan rp{};
+  if (M > 0) rp = row_plan(M, p.S);
+  const int v[9] = {p.cfg, p.tiles_k, p.ntiles, p.S, rp.base, rp.rem, rp.L, rp.nch0, rp.nch1};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return LVL_OK;
+}
+
+extern "C" int lvl_linear_wgrad_pair_of_block(int cfg, int pairs, int bid) {
+  LVL_REQUIRE(cfg >= 0 && cfg < kNumCfg, "linear_wgrad_pair_of_block: unknown configuration %d", cfg);
+  LVL_REQUIRE(pairs > 0 && bid >= 0 && bid < pairs, "linear_wgrad_pair_of_block: block %d of %d", bid, pairs);
+  return (kCfg[cfg][2] == 5 || kCfg[cfg][3] == 5) ? pair_of_block<true>(pairs, bid) : pair_of_block<false>(pairs, bid);
+}
+
 extern "C" int lvl_linear_wgrad(const void* dy, const void* x, float* dw, float* dbias, float* ws, uint32_t* sched,
                                 int64_t M, int N, int K, int dtype, void* stream) {
   LVL_REQUIRE(dy && x && dw && ws, "linear_wgrad: null pointer");

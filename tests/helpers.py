@@ -1,4 +1,6 @@
-"""Shared test helpers: build the lavila_amd model for a golden config, oracle-side slab maths."""
+"""Shared test helpers: build the lavila_amd model for a golden config, oracle-side slab maths, the launch harness of the
+persistent GEMMs' GPU tests (CU limit / late workgroups, guard rows, one guarded lvl_linear_wgrad launch)."""
+import contextlib
 import os
 import sys
 
@@ -73,6 +75,65 @@ def check_fixture_gradients(fx, grads, rtol, norm_rtol, tag=''):
         got = grads[k].detach().float().norm().item()
         assert abs(got - n) <= norm_rtol * n + 1e-6, (tag, k, got, n)
     return worst
+
+
+@contextlib.contextmanager
+def launch_config(libs, cus, late):
+    """compute-unit limit and late-workgroup modulus on every library given; both reset in any case"""
+    try:
+        for lib in libs:
+            assert lib.lvl_set_compute_units(cus) == 0
+            assert lib.lvl_debug_late_workgroups(late) == 0
+        yield
+    finally:
+        for lib in libs:
+            assert lib.lvl_set_compute_units(0) == 0
+            assert lib.lvl_debug_late_workgroups(0) == 0
+
+
+def sched_block(sched, words=16):
+    """the counter block of a launch: None for the static schedule, else `words` zero words"""
+    return None if sched == 'static' else torch.zeros(words, dtype=torch.int32, device='cuda')
+
+
+def guarded_in(t, extra=256):
+    """t [M, C] as the first M rows of a larger buffer whose other rows are NaN / +Inf / -Inf"""
+    M = t.shape[0]
+    buf = torch.empty((M + extra,) + tuple(t.shape[1:]), dtype=t.dtype, device='cuda')
+    buf[M::3] = float('nan')
+    buf[M + 1::3] = float('inf')
+    buf[M + 2::3] = float('-inf')
+    buf[:M] = t
+    return buf[:M]
+
+
+WS_SENTINEL = 0x7FA5A5A5      # bit pattern (a NaN payload nobody writes) of the floats behind a guarded workspace
+
+
+def wgrad_launch(lib, dy, x, want_db, sched, guard, blk=None, ws_guard=0):
+    """one lvl_linear_wgrad launch -> (dw, db). dw, db and the workspace are pre-filled with NaN (every element the
+    result depends on must be written); guard: rows >= M of dy and x are NaN / Inf. sched 'static': no counter block;
+    otherwise `blk` (a block a launch has used before) or a fresh zero block, which must be all zero again afterwards.
+    ws_guard: that many sentinel floats behind lvl_workspace_floats must come back untouched."""
+    from lavila_amd import _cabi as C
+    M, N = dy.shape
+    K = x.shape[1]
+    if guard:
+        dy, x = guarded_in(dy), guarded_in(x)
+    n_ws = int(lib.lvl_workspace_floats(b'linear_wgrad', N, K))
+    ws = torch.full((n_ws + ws_guard,), float('nan'), device='cuda')
+    ws[n_ws:].view(torch.int32).fill_(WS_SENTINEL)
+    dw = torch.full((N, K), float('nan'), device='cuda')
+    db = torch.full((N,), float('nan'), device='cuda') if want_db else None
+    if blk is None:
+        blk = sched_block(sched, 1024)
+    C.check(lib.lvl_linear_wgrad(C.ptr(dy), C.ptr(x), C.ptr(dw), C.ptr(db), C.ptr(ws), C.ptr(blk), M, N, K, C.LVL_BF16,
+                                 C.stream_ptr()), 'lvl_linear_wgrad')
+    if blk is not None:
+        torch.cuda.synchronize()
+        assert int(blk.abs().sum()) == 0, blk.tolist()
+    assert bool((ws[n_ws:].view(torch.int32) == WS_SENTINEL).all()), 'lvl_linear_wgrad wrote behind its workspace'
+    return dw, db
 
 
 def oracle_slab_forward(img_all, txt_all, scale, B, row0):

@@ -11,7 +11,6 @@
     exactly on small integers; outputs bit-equal across CU counts and schedules (a tile's arithmetic does not depend on
     who computes it); rows >= M of the outputs never written, rows >= M of the inputs never read.
 """
-import contextlib
 import ctypes
 import os
 import shutil
@@ -19,6 +18,11 @@ import subprocess
 
 import pytest
 import torch
+
+from helpers import guarded_in as _guarded_in
+from helpers import launch_config as _launch_config
+from helpers import sched_block as _sched_block
+from helpers import wgrad_launch as _wgrad
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -51,35 +55,6 @@ def _qg(u):
 def _qg_grad(u):
     s = torch.sigmoid(1.702 * u)
     return s * (1 + 1.702 * u * (1 - s))
-
-
-@contextlib.contextmanager
-def _launch_config(libs, cus, late):
-    """compute-unit limit and late-workgroup modulus on every library given; both reset in any case"""
-    try:
-        for lib in libs:
-            assert lib.lvl_set_compute_units(cus) == 0
-            assert lib.lvl_debug_late_workgroups(late) == 0
-        yield
-    finally:
-        for lib in libs:
-            assert lib.lvl_set_compute_units(0) == 0
-            assert lib.lvl_debug_late_workgroups(0) == 0
-
-
-def _sched_block(sched, words=16):
-    return None if sched == 'static' else torch.zeros(words, dtype=torch.int32, device=DEV)
-
-
-def _guarded_in(t, extra=256):
-    """t [M, C] as the first M rows of a larger buffer whose other rows are NaN / +Inf / -Inf"""
-    M = t.shape[0]
-    buf = torch.empty((M + extra,) + tuple(t.shape[1:]), dtype=t.dtype, device=DEV)
-    buf[M::3] = float('nan')
-    buf[M + 1::3] = float('inf')
-    buf[M + 2::3] = float('-inf')
-    buf[:M] = t
-    return buf[:M]
 
 
 def _guarded_out(M, N, dtype):
@@ -411,26 +386,8 @@ def test_counted_waits_of_the_few_cu_shape(audit_lib, epi):
 
 
 # --------------------------------------------------------------------------------------------------------------------
-# lvl_linear_wgrad on the same remainders
+# lvl_linear_wgrad on the same remainders (the launch harness: helpers.wgrad_launch)
 # --------------------------------------------------------------------------------------------------------------------
-def _wgrad(lib, dy, x, want_db, sched, guard):
-    from lavila_amd import _cabi as C
-    M, N = dy.shape
-    K = x.shape[1]
-    if guard:
-        dy, x = _guarded_in(dy), _guarded_in(x)
-    ws = torch.full((int(lib.lvl_workspace_floats(b'linear_wgrad', N, K)),), float('nan'), device=DEV)
-    dw = torch.full((N, K), float('nan'), device=DEV)
-    db = torch.full((N,), float('nan'), device=DEV) if want_db else None
-    blk = _sched_block(sched, 1024)
-    C.check(lib.lvl_linear_wgrad(C.ptr(dy), C.ptr(x), C.ptr(dw), C.ptr(db), C.ptr(ws), C.ptr(blk), M, N, K, C.LVL_BF16,
-                                 C.stream_ptr()), 'lvl_linear_wgrad')
-    if blk is not None:
-        torch.cuda.synchronize()
-        assert int(blk.abs().sum()) == 0, blk.tolist()
-    return dw, db
-
-
 def test_linear_wgrad_tail_rows_on_every_schedule():
     """lvl_linear_wgrad (dW = dy^T x, with and without dbias) at every remainder of the matrix, 8 / 16 / all CUs x
     static / dynamic / late: rows >= M of dy and x are NaN/Inf and never read; exact on small integers under every
