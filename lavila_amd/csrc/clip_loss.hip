@@ -184,15 +184,16 @@ __global__ __launch_bounds__(256) void ssl_fwd_kernel(const T* __restrict__ img_
   const T* Bm = dir == 0 ? txt_all : img_all;
   for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = Elem<T>::load(A + (int64_t)gi * E + e);
   __syncthreads();
-  const int ind_i = ind[gi];
+  const int ind_i = ind[gi] != 0;                                   // any non-zero indicator counts as 1
   const float sc0 = scales[ind_i], sc1 = scales[ind_i + 1];          // partner indicator 0 / 1
 
   float m = -INFINITY, l = 0.f, ex[3] = {0.f, 0.f, 0.f}, best = -INFINITY, diag_z = 0.f, diag_l = 0.f;
   int bi = 0x7fffffff;
   for (int j = threadIdx.x; j < G; j += blockDim.x) {
     const float zr = dot_row(Bm + (int64_t)j * E, a_s, E);
-    const int bucket = ind_i + ind[j];
-    const float z = zr * (ind[j] ? sc1 : sc0);
+    const int ind_j = ind[j] != 0;
+    const int bucket = ind_i + ind_j;
+    const float z = zr * (ind_j ? sc1 : sc0);
     if (logits) logits[((int64_t)dir * B + i) * G + j] = z;
     if (j == gi) { diag_z = zr; diag_l = z; }
     if (z > best) { best = z; bi = j; }
@@ -259,12 +260,12 @@ __global__ __launch_bounds__(256) void ssl_bwd_kernel(const T* __restrict__ img_
   const T* Bm = dir == 0 ? txt_all : img_all;
   for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = Elem<T>::load(A + (int64_t)gi * E + e);
   __syncthreads();
-  const int ind_i = ind[gi];
+  const int ind_i = ind[gi] != 0;                                   // any non-zero indicator counts as 1
   const float sc0 = scales[ind_i], sc1 = scales[ind_i + 1];
   const float L_own = lse_all[(int64_t)dir * G + gi];
   const float* L_other = lse_all + (int64_t)(1 - dir) * G;
   for (int j = threadIdx.x; j < G; j += blockDim.x) {
-    const float s = ind[j] ? sc1 : sc0;
+    const float s = ind[j] != 0 ? sc1 : sc0;
     const float z = dot_row(Bm + (int64_t)j * E, a_s, E) * s;
     c[j] = s * (__expf(z - L_own) + __expf(z - L_other[j]) - (j == gi ? 2.f : 0.f));
   }

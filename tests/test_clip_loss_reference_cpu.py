@@ -1,7 +1,9 @@
 """CPU: the float64 slab reference of the contrastive head (tests/clip_loss_reference.py) against the float32 oracle
-restatements and float64 autograd, and every input condition tests/test_gpu_clip_loss_exact.py relies on -- exactness of
-the logits in any summation order, the planted ties and their relation to the kernels' work split, the branch each shape
-reaches -- computed from the shapes, plus the measurement the GPU tolerance of lse / expect is derived from."""
+restatements and float64 autograd, and every input condition tests/test_gpu_clip_loss_exact.py and
+tests/test_gpu_clip_loss_bwd_exact.py rely on -- exactness of the logits in any summation order (also of the lo-bearing
+cases, fragment by fragment), the planted ties and their relation to the kernels' work split, the branch each shape
+reaches, the grouped lse_all against the plain one -- computed from the shapes, plus the measurements the GPU tolerances
+of lse / expect and of both backwards are derived from."""
 import os
 
 import numpy as np
@@ -248,3 +250,176 @@ def test_backward_refuses_a_row_beyond_the_LDS_limit_on_the_host(name):
         msg = lib.lvl_last_error().decode()
         assert rc != 0 and 'too large for the LDS-resident row' in msg and f'G={G}' in msg, (rc, msg)
         assert (grads == 0x7FA5A5A5).all()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# what tests/test_gpu_clip_loss_bwd_exact.py and the lo-bearing forward cases rely on
+# ----------------------------------------------------------------------------------------------------------------------
+def _lse_args(c):
+    ssl = c['kind'] == 'ssl'
+    return (c['img'], c['txt'], None if ssl else c['scale'], c['ind'] if ssl else None, c['scales3'] if ssl else None)
+
+
+def test_grouped_lse_equals_the_chunked_one():
+    """lse_all computes each distinct (row, indicator) once, weighted by its count: equal to every row against every
+    column at G <= 1025 (weights instead of repeated terms reorder a float64 sum: 1e-12 on values of size <= 100), on the
+    sparse exact cases, where the grouping bites, and on random rows, where every row is its own group"""
+    cases = [R.exact_case(*s) for s in R.BWD_SPECS]
+    cases += [R.random_bwd_case(kind, *sh, cls, False) for kind in ('clip', 'ssl') for sh in R.RANDOM_BWD_SHAPES
+              for cls in R.RANDOM_SCALES]
+    grouped = 0
+    for c in cases:
+        assert c['G'] <= 1025
+        want = R.lse_all_chunked(*_lse_args(c))
+        for chunk in (512, 7):
+            np.testing.assert_allclose(R.lse_all(*_lse_args(c), chunk=chunk), want, atol=1e-12, rtol=0)
+        key = np.concatenate([c['txt'], c['ind'][:, None]], 1) if c['kind'] == 'ssl' else c['txt']
+        grouped += len(np.unique(key, axis=0)) < c['G'] // 2
+    assert grouped >= 3, grouped                              # the E = 8 shapes: at most 112 (SSL: 224) distinct rows
+    for s in R.LARGE_SPECS:                                   # E = 8, two non-zeros: at most 4 * C(8,2) rows, planted ones aside
+        c = R.exact_case(*s)
+        assert len(np.unique(c['txt'], axis=0)) <= 112 + 2 * len(c['ties']) and len(c['ties']) >= 2
+
+
+def test_backward_shapes_reach_the_branches_they_are_listed_for():
+    clip = [s[1:5] for s in R.BWD_SPECS if s[0] == 'clip']
+    ssl = [s[1:5] for s in R.BWD_SPECS if s[0] == 'ssl']
+    assert sorted(clip) == sorted(R.MFMA_SHAPES + R.VALU_SHAPES) and sorted(ssl) == sorted(R.VALU_SHAPES)
+    for shapes in (clip, ssl):
+        br = {s: R.bwd_branches(*s) for s in shapes}
+        for tag in ('e_second_pass', 'idle_column_threads', 'stride', 'ends_at_G'):
+            assert any(b[tag] for b in br.values()), tag
+        assert any(b['e_second_pass'] and b['stride'] for b in br.values())
+        assert {s[2] for s in shapes} >= {264, 768} and max(s[1] for s in shapes) == 1025
+        assert not any(b['lds_opt_in'] for b in br.values())
+    assert 512 in {s[2] for s in clip} and 256 in {s[2] for s in clip}      # E == 256: exactly one pass, no idle thread
+    lg = [R.bwd_branches(*s) for s in R.LARGE_SHAPES]
+    assert [(s[2] + s[1]) * 4 for s in R.LARGE_SHAPES] == [65536, 65540, R.LDS_LIMIT_BYTES]
+    assert [b['lds_opt_in'] for b in lg] == [False, True, True] and [b['lds_limit'] for b in lg] == [False, False, True]
+    assert any(b['ends_at_G'] for b in lg) and any(s[3] == 0 for s in R.LARGE_SHAPES)
+    assert all(s[0] in (2, 3) and s[2] == 8 for s in R.LARGE_SHAPES)
+    assert {s[0] for s in R.LARGE_SPECS} == {'clip', 'ssl'}
+    assert R.RANDOM_BWD_SHAPES == ((32, 256, 256, 64), (5, 300, 768, 7), (7, 1025, 24, 500))
+    assert R.RANDOM_SCALES == {'random14': 14.285714, 'random100': 100.0, 'paired100': 100.0}
+
+
+def _bwd_classes():
+    """class -> [(case, rows_only)]: every case whose device tolerance is MARGIN x the class's recorded number"""
+    ex = [R.exact_case(*s) for s in R.BWD_SPECS + R.SINGLE_RANK_SPECS]
+    ex += [R.one_value_pair(*s, v)[1] for s in R.VALU_SHAPES for v in (0, 1)]               # held to the clip class
+    out = {'clip': [(c, False) for c in ex if c['kind'] == 'clip'], 'rows_only': [(c, True) for c in ex if c['kind'] == 'clip'],
+           'ssl': [(c, False) for c in ex if c['kind'] == 'ssl'], 'large': [(R.exact_case(*s), False) for s in R.LARGE_SPECS]}
+    for cls in R.RANDOM_SCALES:
+        out[cls] = []
+        for sh in R.RANDOM_BWD_SHAPES:
+            for bf16 in (False, True):
+                out[cls] += [(R.random_bwd_case('clip', *sh, cls, bf16), False), (R.random_bwd_case('clip', *sh, cls, bf16), True),
+                             (R.random_bwd_case('ssl', *sh, cls, bf16), False)]
+    return out
+
+
+def test_backward_float32_restatement_error_is_within_the_recorded_one():
+    """The numbers the device tolerances of both backwards are 8 x of, per class, measured here from backward_f32 alone
+    over the un-cancelled magnitude. Only `measured <= recorded` depends on this host's float32 exp; `recorded` is held
+    under a ceiling fixed from the class's G (clip_loss_reference.bwd_ceiling states the reason)."""
+    classes = _bwd_classes()
+    assert set(classes) == set(R.BWD_F32_ERR) == set(R.BWD_CLASS_G)
+    for cls, cases in classes.items():
+        measured = max(R.backward_f32_error(c, ro) for c, ro in cases)
+        print(f'backward float32 restatement, {cls}: {measured:.3e} (recorded {R.BWD_F32_ERR[cls]:.1e}, '
+              f'ceiling {R.bwd_ceiling(cls):.1e})')
+        assert max(c['G'] for c, _ in cases) == R.BWD_CLASS_G[cls]
+        assert measured <= R.BWD_F32_ERR[cls] <= R.bwd_ceiling(cls), cls
+        assert R.bwd_tol(cls, R.BWD_CLASS_G[cls]) == 8 * R.BWD_F32_ERR[cls]
+    eps = float(np.finfo(np.float32).eps)
+    assert R.bwd_ceiling('clip') == eps * 1025 and R.bwd_ceiling('large') == eps * 38392
+    assert R.bwd_ceiling('random100') == eps * (1025 + 0.5 * 768 * 100.0)
+
+
+def test_uncancelled_magnitude_is_the_sum_of_the_terms_before_the_diagonal_subtraction():
+    for c, rows_only in ((R.exact_case('clip', 5, 300, 8, 295, 1), False), (R.exact_case('clip', 5, 300, 8, 295, 1), True),
+                         (R.exact_case('ssl', 3, 63, 24, 11, 3), False), (R.random_bwd_case('ssl', 5, 300, 768, 7, 'random100', False), False)):
+        B, G, row0, ssl = c['B'], c['G'], c['row0'], c['kind'] == 'ssl'
+        lse = R.case_lse32(c).astype(np.float64)
+        coef = R.bwd_coef(c, rows_only)
+        g, u = R.case_backward(c, lse, coef, R.UPSTREAM, rows_only)
+        k = coef * float(np.float64(R.UPSTREAM[0]))
+        a, b = c['img'].astype(np.float64), c['txt'].astype(np.float64)
+        ind = c['ind'].astype(np.int64)
+        for d, (own, other) in enumerate(((a, b), (b, a))):
+            for i in range(B):
+                gi = row0 + i
+                s = c['scales3'].astype(np.float64)[ind[gi] + ind] if ssl else np.full(G, float(c['scale'][0]))
+                z = s * (other @ own[gi])
+                t = np.exp(z - lse[d, gi]) + (0 if rows_only else np.exp(z - lse[1 - d]))
+                t[gi] += 1.0 if rows_only else 2.0
+                np.testing.assert_allclose(u[d, i], k * ((s * t) @ np.abs(other)), rtol=1e-12, atol=0)
+        if ssl:
+            o = R.ssl_slab_backward(c['img'], c['txt'], c['ind'], lse, c['scales3'], R.UPSTREAM, coef, B, row0, True)
+        else:
+            o = R.slab_backward(c['img'], c['txt'], lse, c['scale'], R.UPSTREAM, coef, B, row0, rows_only, True)
+        for grad, mag, umag in ((o[0], o[2], o[4]), (o[1], o[3], o[5])):
+            assert (np.abs(grad) <= mag * (1 + 1e-12)).all() and (mag <= umag * (1 + 1e-12)).all()
+    # sparse rows: some gradient column takes its WHOLE un-cancelled magnitude from the diagonal term, while |c_ii| is
+    # far below 2 there -- a tolerance over sum |c| |b| would hold the kernel to ulps of a cancelled value
+    c = R.exact_case('clip', 5, 300, 8, 295, 1)
+    lse = R.case_lse32(c)
+    o = R.slab_backward(c['img'], c['txt'], lse, c['scale'], R.UPSTREAM, R.bwd_coef(c), c['B'], c['row0'], False, True)
+    assert (o[4] > 1.5 * o[2]).any()
+
+
+def test_peaked_random_cases_have_the_diagonal_cancellation():
+    """scale 100, 'paired100': in every case some local row holds softmax mass > 0.99 on its diagonal, so
+    c_ii = (p + p') - 2 cancels. The loose pairs of random_case ('random100') peak off the diagonal: stated, not hidden."""
+    loose = 0.0
+    for kind in ('clip', 'ssl'):
+        for sh in R.RANDOM_BWD_SHAPES:
+            for bf16 in (False, True):
+                assert R.diag_mass(R.random_bwd_case(kind, *sh, 'paired100', bf16)).max() > 0.99
+                c = R.random_bwd_case(kind, *sh, 'random100', bf16)
+                f = R.case_forward(c)
+                loose = max(loose, R.diag_mass(c).max())
+                if sh[2] != 768:
+                    assert np.exp(f['max'] - f['lse']).max() > 0.99       # peaked all the same, on another column
+    print(f'largest diagonal mass of the loose pairs at scale 100: {loose:.4f}')
+    assert loose < 0.99
+
+
+@pytest.mark.parametrize('which', ['img', 'txt'])
+@pytest.mark.parametrize('shape', R.MFMA_SHAPES, ids=lambda s: '-'.join(map(str, s)))
+def test_lo_bearing_cases_hold_their_conditions(shape, which):
+    """lo_case asserts the fragments, the other matrix and the 2^24 bound from the inputs. Here: the float32 logits are
+    bit-identical in several summation orders -- also when every operand is split into its bfloat16 hi and lo fragments
+    and the three products the kernel forms are accumulated separately -- and equal float64; the logits are the base
+    case's times 513 / 512, the argmax and the tie sets are the base case's; dropping either mixed product moves every
+    non-zero logit of one direction."""
+    n = R.MFMA_SHAPES.index(shape)
+    c, base = R.lo_case(which, *shape, n), R.exact_case('clip', *shape, n)
+    f, fb = R.case_forward(c), R.case_forward(base)
+    B, G, E, row0 = shape
+    assert np.array_equal(f['logits'], fb['logits'] * (1 + 2.0 ** -9)) and np.array_equal(f['argmax'], fb['argmax'])
+    assert c['ties'] == base['ties'] and len(c['ties']) >= (0 if G == 1 else 1)
+    for lab, oth, _, _ in c['ties']:
+        for d in range(2):
+            z = f['logits'][d][lab - row0]
+            assert sorted(np.flatnonzero(z == z.max())) == sorted((lab, oth))
+    rows = slice(row0, row0 + B)
+    rng = np.random.default_rng(n)
+    orders = [np.arange(E), np.arange(E)[::-1], rng.permutation(E)]
+    scale = c['scale'][0]
+    for d in range(2):
+        own, other = (c['img'], c['txt'])[d][rows], (c['txt'], c['img'])[d]
+        for o in orders:
+            assert np.array_equal(_f32_logits_in_order(own, other, scale, o).astype(np.float64), f['logits'][d])
+        a = np.float32(scale) * own
+        ah, al, bh, bl = R.round_bf16(a), R.bf16_lo(a), R.round_bf16(other), R.bf16_lo(other)
+        assert np.array_equal(ah + al, a) and np.array_equal(bh + bl, other) and not (al != 0).any() * (bl != 0).any()
+        three = (_f32_logits_in_order(al, bh, 1.0, orders[2]) + _f32_logits_in_order(ah, bl, 1.0, orders[1])
+                 + _f32_logits_in_order(ah, bh, 1.0, orders[0]))
+        assert three.dtype == np.float32 and np.array_equal(three.astype(np.float64), f['logits'][d])
+        a_lo_side = (which == 'img') == (d == 0)                  # this direction's lo fragments sit in A (the own rows)
+        assert (al != 0).any() == a_lo_side and (bl != 0).any() == (not a_lo_side)
+        dropped = _f32_logits_in_order(ah, bh, 1.0, orders[0]).astype(np.float64)      # without the mixed product
+        nz = f['logits'][d] != 0
+        assert (nz.any() or G == 1) and (dropped[nz] != f['logits'][d][nz]).all()     # (one sparse pair may not overlap)
+        assert np.array_equal(dropped, fb['logits'][d])           # off by 2^-9 relative, everywhere

@@ -1,33 +1,40 @@
-"""GPU (-m gpu): lvl_clip_loss_fwd -- the matrix-core kernel for E in 64/128/256/512 and the VALU kernel for every other
-width -- through the C ABI against the float64 slab reference (tests/clip_loss_reference.py), on inputs whose logits are
-EXACT in float32 (so the logits slab, the diagonal, the maximum and the argmax under "first maximum kept" must be equal
-to the reference bit for bit), with the row maximum tied at planted column pairs in every relation to the kernels' work
-split (same 16-column tile / tiles jt and jt+4 of one wave / different waves / the last partial tile; columns j and j+256
-of one thread / two lanes / two waves), the label once the lower and once the higher tied index. Every output is a view
-into a larger buffer filled with a NaN bit pattern (the same pattern as an int32 sentinel for argmax), 32 guard rows
-before and after; the inputs lie between NaN rows. Every test asserts the guards untouched.
+"""GPU (-m gpu): the two contrastive forwards through the C ABI against the float64 slab reference
+(tests/clip_loss_reference.py): lvl_clip_loss_fwd -- the matrix-core kernel for E in 64/128/256/512 and the VALU kernel for
+every other width -- and lvl_ssl_clip_loss_fwd (per-pair temperature, three bucket expectations, its own 9-word merge),
+on inputs whose logits are EXACT in float32 (so the logits slab, the diagonal, the maximum and the argmax under "first
+maximum kept" must be equal to the reference bit for bit), with the row maximum tied at planted column pairs in every
+relation to the kernels' work split (same 16-column tile / tiles jt and jt+4 of one wave / different waves / the last
+partial tile; columns j and j+256 of one thread / two lanes / two waves), the label once the lower and once the higher tied
+index; the SSL ties exist only after the per-pair scale has been applied. The matrix-core kernel additionally runs
+lo-bearing inputs: one matrix times 1 + 2^-9, so that every non-zero entry has a bfloat16 lo fragment and a dropped
+a.lo x b.hi or a.hi x b.lo product moves every logit of one direction by 2^-9 relative. Degenerate indicators hold the SSL
+kernel to lvl_clip_loss_fwd bit for bit; indicators other than 0 / 1 count as 1.
+
+Every output is a view into a larger buffer filled with a NaN bit pattern (the same pattern as an int32 sentinel for
+argmax), 32 guard rows before and after; the inputs lie between NaN rows. Every launch asserts the guards untouched.
 
 Tolerance of lse and expect (not chosen by running a kernel). tests/test_clip_loss_reference_cpu.py measures, on the CPU,
 how far a float32 restatement of the kernels' streaming m / l / ex recurrence and its merges lies from float64 over these
-cases, each row's error taken over max(1, max |logit|) of the row: 3.33e-7, recorded as 3.6e-7. A kernel is allowed 8 x the
-recorded number (__expf / __logf are the fast variants; their argument reduction adds an error that grows with |x|):
-2.9e-6 per unit of row scale, where the older slab test allows 1e-4 at scale ~ 14.
+cases (clip and SSL), each row's error taken over max(1, max |logit|) of the row (the SSL bucket expectations: over
+max(1, max |dot|)): 3.33e-7, recorded as 3.6e-7. A kernel is allowed 8 x the recorded number (__expf / __logf are the
+fast variants; their argument reduction adds an error that grows with |x|): 2.9e-6 per unit of row scale, where the older
+slab test allows 1e-4 at scale ~ 14.
 
-This file covers lvl_clip_loss_fwd only. The launcher names every device tensor until its launch has completed: a
-temporary would hand its block back to the allocator, and the next allocation could overwrite it before the kernel runs.
+The launchers (tests/clip_loss_launch.py) name every device tensor until the launch has completed -- a temporary would hand
+its block back to the allocator, and the next allocation could overwrite it before the kernel runs -- and read the
+indicators and scales back from the device, bit for bit, before they launch. Both backwards:
+tests/test_gpu_clip_loss_bwd_exact.py.
 """
 import numpy as np
 import pytest
 import torch
 
+import clip_loss_launch as K
 import clip_loss_reference as R
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
-GUARD = 32                      # rows; more than the 15 a 16-row workgroup could overrun by
-SENT32 = 0x7FA5A5A5             # a NaN payload nobody computes; the int32 sentinel of the argmax guards
-DTYPES = (torch.float32, torch.bfloat16)
+DTYPES = K.DTYPES
 _id = lambda s: '-'.join(map(str, s))            # noqa: E731
 
 # what each (B, G, row0) of the matrix-core sweep is there for (asserted from the shape in _assert_reaches)
@@ -62,59 +69,7 @@ def _assert_reaches(c):
         assert got[tag], (key, tag)
 
 
-def _lib():
-    from lavila_amd import _cabi as C
-    return C, C.lib()
-
-
-def _guarded(rows, width, dtype=torch.float32):
-    """(buffer, view of its rows GUARD .. GUARD + rows): every word of the buffer starts as the sentinel"""
-    buf = torch.empty(rows + 2 * GUARD, width, dtype=dtype, device=DEV)
-    buf.view(torch.int32).fill_(SENT32)
-    return buf, buf[GUARD:GUARD + rows]
-
-
-def _untouched(buf, rows):
-    w = buf.view(torch.int32)
-    return bool((w[:GUARD] == SENT32).all()) and bool((w[GUARD + rows:] == SENT32).all())
-
-
-def _guarded_in(x, dt):
-    """x [G,E] (numpy float32) in dtype dt between NaN rows"""
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    buf = torch.full((t.shape[0] + 2 * GUARD, t.shape[1]), float('nan'), dtype=dt, device=DEV)
-    buf[GUARD:GUARD + t.shape[0]] = t.to(DEV, dt)
-    assert torch.equal(buf[GUARD:GUARD + t.shape[0]].float().cpu(), t)            # the dtype holds the values exactly
-    return buf[GUARD:GUARD + t.shape[0]]
-
-
-def _dev(x, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV, dtype)
-
-
-def _forward(c, dt, want_logits=True):
-    """one lvl_clip_loss_fwd launch into guarded outputs -> stats [2,B,4], argmax [2,B], logits [2,B,G] (CPU, float64 /
-    int)"""
-    C, lib = _lib()
-    B, G, E, row0 = c['B'], c['G'], c['E'], c['row0']
-    assert c['kind'] == 'clip'
-    W = 4
-    img, txt = _guarded_in(c['img'], dt), _guarded_in(c['txt'], dt)
-    sbuf, stats = _guarded(2 * B, W)
-    abuf, argmax = _guarded(2 * B, 1, torch.int32)
-    lbuf, logits = _guarded(2 * B, G) if want_logits else (None, None)
-    # every device tensor keeps a name until the launch has completed: a temporary would hand its block back to the
-    # allocator, and the next temporary could overwrite it before the kernel reads it
-    scale = _dev(c['scale'])
-    rc = lib.lvl_clip_loss_fwd(C.ptr(img), C.ptr(txt), C.ptr(scale), B, G, E, row0, C.ptr(stats), C.ptr(argmax),
-                               C.ptr(logits), C.dtype_code(img), C.stream_ptr())
-    C.check(rc, 'forward')
-    torch.cuda.synchronize()
-    assert _untouched(sbuf, 2 * B), 'stats written outside [2,B,W]'
-    assert _untouched(abuf, 2 * B), 'argmax written outside [2,B]'
-    assert lbuf is None or _untouched(lbuf, 2 * B), 'logits written outside [2,B,G]'
-    return (stats.double().cpu().numpy().reshape(2, B, W), argmax.cpu().numpy().reshape(2, B),
-            logits.double().cpu().numpy().reshape(2, B, G) if want_logits else None)
+_forward = K.clip_forward
 
 
 def _check_forward_exact(c, dt):
@@ -146,3 +101,94 @@ def test_forward_exact_logits_and_first_index_argmax(spec, dt):
     """logits, diag, max and argmax equal to float64; lse and expect within 8 x the float32 restatement's error; guards
     untouched; the same statistics with and without the logits output"""
     _check_forward_exact(R.exact_case(*spec), dt)
+
+
+@pytest.mark.parametrize('which', ['img', 'txt'])
+@pytest.mark.parametrize('shape', R.MFMA_SHAPES, ids=_id)
+def test_forward_exact_with_lo_fragments(shape, which):
+    """float32 inputs whose one matrix carries non-zero bfloat16 lo fragments (conditions: clip_loss_reference.lo_case
+    and the CPU file): the same bit-exact assertions. Direction 0 needs a.lo x b.hi for 'img' and a.hi x b.lo for 'txt',
+    direction 1 the other one; without it every non-zero logit of that direction is off by 2^-9 relative."""
+    c = R.lo_case(which, *shape, R.MFMA_SHAPES.index(shape))
+    assert c['layout'] == 'mfma' and c['lo'] == which
+    _check_forward_exact(c, torch.float32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# lvl_ssl_clip_loss_fwd
+# ----------------------------------------------------------------------------------------------------------------------
+def _check_ssl_stats(c, f, stats, argmax, logits, tag):
+    B, G = c['B'], c['G']
+    assert np.array_equal(logits, f['logits']), tag                     # every scaled logit, bit for bit
+    assert np.array_equal(argmax, f['argmax']), (tag, argmax, f['argmax'])
+    assert np.array_equal(stats[..., 1], f['diag']) and np.array_equal(stats[..., 5], f['diag_dot']), tag
+    assert np.array_equal(stats[..., 6], f['max']) and (stats[..., 7] == 0).all(), tag
+    tol = R.fwd_tol(G) * R.row_scale(f['logits'])                       # [2,B]
+    err = np.abs(stats[..., 0] - f['lse'])
+    print(f'{tag[:6]}: lse err/tol {(err / tol).max():.3f}')
+    assert (err <= tol).all(), tag
+    tol_e = R.fwd_tol(G) * np.maximum(1.0, np.abs(f['dots']).max(-1))   # [2,B]: the expectations are of the unscaled dot
+    err = np.abs(stats[..., 2:5] - f['expect'])
+    print(f'{tag[:6]}: bucket expectations err/tol {(err / tol_e[..., None]).max():.3f}')
+    assert (err <= tol_e[..., None]).all(), tag
+
+
+@pytest.mark.parametrize('dt', DTYPES, ids=('f32', 'bf16'))
+@pytest.mark.parametrize('spec', R.SSL_SPECS, ids=_id)
+def test_ssl_forward_exact_logits_and_first_index_argmax(spec, dt):
+    """logits, diagonal logit, diagonal dot, max and argmax equal to float64, stats[7] == 0; every planted tie -- it exists
+    only after the per-pair scale -- resolves to the lower index; lse and the three bucket expectations within 8 x the
+    float32 restatement's error; guards untouched; the same statistics with and without the logits output"""
+    c = R.exact_case(*spec)
+    _assert_reaches(c)
+    f = R.case_forward(c)
+    stats, argmax, logits = K.ssl_forward(c, dt)
+    tag = (c['kind'], c['B'], c['G'], c['E'], c['row0'], str(dt), c['ties'])
+    _check_ssl_stats(c, f, stats, argmax, logits, tag)
+    assert len(c['ties']) >= (0 if c['G'] == 1 else 1)
+    for lab, oth, _, pos in c['ties']:
+        assert c['ind'][lab] != c['ind'][oth]
+        assert (f['dots'][:, lab - c['row0'], lab] != f['dots'][:, lab - c['row0'], oth]).all()      # no tie before the scale
+        assert (argmax[:, lab - c['row0']] == min(lab, oth)).all(), tag
+    s2, a2, _ = K.ssl_forward(c, dt, want_logits=False)
+    assert np.array_equal(s2, stats) and np.array_equal(a2, argmax), tag
+
+
+@pytest.mark.parametrize('dt', DTYPES, ids=('f32', 'bf16'))
+@pytest.mark.parametrize('spec', R.SSL_SPECS, ids=_id)
+def test_ssl_forward_with_one_indicator_value_is_the_clip_forward(spec, dt):
+    """scales3 = (16, 32, 64): all-zero indicators against lvl_clip_loss_fwd at scale 16, all-one at scale 64, at widths
+    where both run the same VALU recurrence (a power-of-two scale commutes with every rounding of the dot product):
+    logits, lse, diagonal, maximum and argmax bit-identical; E_k * scale against expect within fwd_tol only (the two
+    products are rounded at different points); the other two buckets are exactly 0."""
+    c = R.exact_case(*spec)
+    assert not R.uses_mfma(c['E']) and [float(v) for v in c['scales3']] == [16.0, 32.0, 64.0]
+    for value, bucket, scale in ((0, 0, 16.0), (1, 2, 64.0)):
+        ind = np.full(c['G'], value, dtype=np.int32)
+        st, am, lg = K.ssl_forward(c, dt, ind=ind)
+        clip = R.one_value_case(c, value)
+        assert float(clip['scale'][0]) == scale
+        st_c, am_c, lg_c = K.clip_forward(clip, dt)
+        tag = (spec, str(dt), value)
+        assert np.array_equal(lg, lg_c) and np.array_equal(am, am_c), tag
+        assert np.array_equal(st[..., 0], st_c[..., 0]) and np.array_equal(st[..., 1], st_c[..., 1]), tag
+        assert np.array_equal(st[..., 6], st_c[..., 3]) and np.array_equal(st[..., 5] * scale, st_c[..., 1]), tag
+        others = [k for k in range(3) if k != bucket]
+        assert (st[..., 2:5][..., others] == 0).all() and (st[..., 7] == 0).all(), tag
+        f = R.case_forward(clip)
+        assert np.array_equal(lg, f['logits']), tag
+        tol = R.fwd_tol(c['G']) * R.row_scale(f['logits'])
+        assert (np.abs(st[..., 2 + bucket] * scale - f['expect']) <= tol).all(), tag
+        assert (np.abs(st_c[..., 2] - f['expect']) <= tol).all(), tag
+
+
+@pytest.mark.parametrize('dt', DTYPES, ids=('f32', 'bf16'))
+@pytest.mark.parametrize('spec', R.SSL_SPECS[1:6:2], ids=_id)
+def test_ssl_forward_reads_any_nonzero_indicator_as_one(spec, dt):
+    """indicators drawn from {0, 1, 2, -1, 7}: every output bit-identical to the launch on their 0 / 1 images"""
+    c = R.exact_case(*spec)
+    wild = K.wild_indicators(c['ind'], seed=spec[-1])
+    got = K.ssl_forward(c, dt, ind=wild)
+    want = K.ssl_forward(c, dt)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b), (spec, str(dt))
