@@ -35,7 +35,7 @@ enum { LVL_ATTN_SPACE = 0, LVL_ATTN_TIME = 1, LVL_ATTN_CAUSAL = 2 /* lvl_attenti
 enum { LVL_EPI_BIAS = 0, LVL_EPI_BIAS_QUICKGELU = 1, LVL_EPI_QUICKGELU_BWD = 2, LVL_EPI_BIAS_RESIDUAL = 3,
        LVL_EPI_BIAS_QUICKGELU_DERIV = 4, LVL_EPI_MUL_AUX_COLSUM = 5 };
 /* activations of the narrator decoder's MLPs (lvl_act_inplace) */
-enum { LVL_ACT_GELU_NEW = 0, LVL_ACT_SQRELU = 1 };
+enum { LVL_ACT_GELU_NEW = 0, LVL_ACT_SQRELU = 1, LVL_ACT_GELU_ERF = 2 };
 
 /* library identification / diagnostics (host pointers) */
 const char* lvl_version(void);
@@ -462,7 +462,9 @@ int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, 
  *   d alpha = dgate * (1 - tanh^2 alpha). Without a gate the gradient of y is ds itself and dy / dgate are not written.
  *   ws: lvl_workspace_floats("gated_add_layernorm_bwd", rows, D). rows > 0.
  * lvl_act_fwd: a = act(u), out of place (u is kept for the backward); lvl_act_bwd: du = da * act'(u) with the forward's
- *   tanh expression for gelu_new and 2 relu(u) for relu^2 (exact zeros where u <= 0). n % 8 == 0.
+ *   tanh expression for gelu_new and 2 relu(u) for relu^2 (exact zeros where u <= 0). n % 8 == 0. All three entry points
+ *   also take LVL_ACT_GELU_ERF, the exact GELU of DistilBERT's FFN (transformers' activation "gelu"):
+ *   a = 0.5 u (1 + erf(u / sqrt 2)), du = da (Phi(u) + u phi(u)). The skinny GEMMs' fused activations do not.
  * lvl_cross_attn_rows_bwd: from q, kv and dout [rows, H*64] (softmax recomputed): dq [rows, H*64] and
  *   dkv [rows/qrep, Tk, 2*H*64], the latter accumulated in f32 over the qrep rows of a context inside one workgroup and
  *   rounded once. Every element of dq and dkv is written. bf16 and 1 <= Tk <= 256 only, else LVL_ENOSYS; any qrep >= 1.
@@ -524,6 +526,32 @@ int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* v, const vo
                            int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
                            int64_t kv_ctx_stride, int causal, uint64_t seed, uint32_t site, float p, int dtype,
                            void* stream);
+
+/* Key-masked bidirectional attention: the self-attention of a padded text batch (DistilBERT's MultiHeadSelfAttention
+ * under an attention_mask), head dim 64, scale 1/8. Operands as lvl_attn_rows_drop_fwd / _bwd: q: contexts * qrep rows
+ * q_stride elements apart; k, v: per context Tk rows kv_stride apart, contexts kv_ctx_stride apart (three tensors, or the
+ * thirds of a packed qkv); out, dout: [rows, H*64] contiguous; dq is laid out as q, dk / dv as k / v. qrep = 1 with
+ * q_stride = L * D is the row-0 form (only the first position of every sample asks).
+ * keymask: [contexts, Tk] bytes, contexts mask_ctx_stride bytes apart, non-zero = visible; NULL = all visible (the bits
+ *   of an all-ones mask).
+ * P = softmax over the visible keys of the context, the row maximum taken over visible keys only; a hidden key has
+ *   probability exactly 0 and dS exactly 0: its k / v rows do not reach any result and its dk / dv rows are exact zeros.
+ *   A context with NO visible key gets the uniform distribution over its Tk keys (what transformers' finite fill gives):
+ *   out = mean_j v_j, dv_j = sum_i dout_i / Tk, dq = dk = 0; always finite.
+ * bf16 with 1 <= Tk <= 256: the MFMA rows attention of lvl_attn_rows_drop_fwd / _bwd with a key-mask flag (one workgroup per
+ *   (context, head), exact single-pass softmax, P rounded to bf16 for P V; hidden rows of k / v are staged but enter every
+ *   product with a factor of exactly 0, so they must be finite). float32, and bf16 with Tk > 256 (DistilBERT allows 512
+ *   positions): shape-generic kernels in f32 arithmetic, one wave per (query row, head) with an online softmax over 64-key
+ *   chunks, hidden rows never read; their backward recomputes the softmax and keeps (lse, delta) per (row, head) in ws.
+ *   ws: lvl_workspace_floats("keymask_attn_bwd", contexts * qrep * H, Tk) floats, required by every call of _bwd. Every
+ *   addressed element of out / dq / dk / dv is written on every call. No atomics, bit-reproducible. Tk <= 0, strides that are
+ *   not multiples of 8, pointers off 16 bytes and unknown dtypes return LVL_EINVAL without a launch. */
+int lvl_keymask_attn_fwd(const void* q, const void* k, const void* v, const uint8_t* keymask, void* out, int contexts,
+                         int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
+                         int64_t mask_ctx_stride, int dtype, void* stream);
+int lvl_keymask_attn_bwd(const void* q, const void* k, const void* v, const uint8_t* keymask, const void* dout, void* dq,
+                         void* dk, void* dv, float* ws, int contexts, int qrep, int Tk, int H, int64_t q_stride,
+                         int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, int dtype, void* stream);
 
 /* ---- packed caption rows: the narrator's teacher-forced pass on the rows that carry a label -------------------------
  * A batch of B captions of up to L positions keeps len_b = cu[b + 1] - cu[b] leading rows each; cu [B + 1] int32 (device),

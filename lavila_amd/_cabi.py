@@ -16,7 +16,7 @@ LVL_F32, LVL_BF16 = 0, 1
 ATTN_SPACE, ATTN_TIME = 0, 1
 EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_QUICKGELU_BWD, EPI_BIAS_RESIDUAL, EPI_BIAS_QUICKGELU_DERIV, EPI_MUL_AUX_COLSUM = 0, 1, 2, 3, 4, 5
 LN_PLAIN, LN_GENERAL = 1, 2          # flags of lvl_layernorm_*_mixed
-ACT_GELU_NEW, ACT_SQRELU = 0, 1
+ACT_GELU_NEW, ACT_SQRELU, ACT_GELU_ERF = 0, 1, 2
 
 _c = ctypes
 _P, _I, _L, _F = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float
@@ -106,6 +106,8 @@ SIGNATURES = {
     'lvl_gated_add_layernorm_bwd_drop': (_I, [_P] * 14 + [_I, _I, _U64, _U32, _F, _I, _P]),
     'lvl_attn_rows_drop_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
     'lvl_attn_rows_drop_bwd': (_I, [_P] * 7 + [_I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_keymask_attn_fwd': (_I, [_P] * 5 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _P]),
+    'lvl_keymask_attn_bwd': (_I, [_P] * 9 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _P]),
     'lvl_rows_pack': (_I, [_P, _L, _L, _P, _I, _I, _I, _P, _I, _P]),
     'lvl_rows_unpack': (_I, [_P, _P, _I, _I, _I, _P, _L, _L, _I, _P]),
 }

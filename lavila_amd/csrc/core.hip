@@ -84,6 +84,7 @@ extern "C" int64_t lvl_workspace_floats(const char* op, int64_t rows, int64_t co
   if (!strcmp(op, "divided_attn_fwd")) return lvl_cls_fwd_ws_floats(rows);
   if (!strcmp(op, "divided_attn_bwd")) return lvl_cls_bwd_ws_floats(rows, cols, true);
   if (!strcmp(op, "causal_attn_bwd")) return lvl_cls_bwd_ws_floats(rows, cols, false);    // delta [B*H, L]
+  if (!strcmp(op, "keymask_attn_bwd")) return rows > 0 ? rows * 2 : 0;   // rows = contexts*qrep*H: (lse, delta) each
   if (!strcmp(op, "qkv_bias_grad")) return (int64_t)(lvl_qkv_bias_row_blocks() + lvl_colsum_mid_rows()) * 2 * cols;   // cols = D
   if (!strcmp(op, "linear_wgrad")) return lvl_wgrad_workspace_floats(rows, cols);   // rows = N (out), cols = K (in); -1: no tiling
   if (!strcmp(op, "linear_tn")) return lvl_linear_tn_workspace_floats(rows, cols);   // rows = M, cols = N

@@ -22,6 +22,8 @@
 //   dV += Pd^T . dO with Pd = keep ? P / (1 - p) : 0 (the P^T image holds Pd);  dQ, dK from dS as before.
 #include "attn_mfma_common.h"
 #include "dropout.h"
+#include "internal.h"
+#include "keymask.h"
 
 using namespace attn_mfma;
 
@@ -38,7 +40,9 @@ struct AttnDrop {
 };
 
 // q / dq rows `qs` elements apart, keys / values / dk / dv rows `kvs` apart and contexts `kvctx` apart; dout [rows, D]
-template <bool DROP, bool CAUSAL>
+// KEYMASK (lvl_keymask_attn_bwd): the forward's key mask; hidden keys have P = dS = 0, so their dk / dv rows are sums of
+// exact zeros; a context with no visible key has the uniform P and dS = 0
+template <bool DROP, bool CAUSAL, bool KEYMASK = false>
 __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint16_t* __restrict__ q, size_t qs,
                                                                       const uint16_t* __restrict__ kp,
                                                                       const uint16_t* __restrict__ vp, size_t kvs,
@@ -46,7 +50,9 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
                                                                       uint16_t* __restrict__ dq,
                                                                       uint16_t* __restrict__ dk,
                                                                       uint16_t* __restrict__ dv, int Tk, int H,
-                                                                      int qrep, AttnDrop drop) {
+                                                                      int qrep, AttnDrop drop,
+                                                                      const uint8_t* __restrict__ mask = nullptr,
+                                                                      size_t mctx = 0) {
   extern __shared__ __align__(16) uint16_t xb_smem[];
   uint16_t* Ks = xb_smem;
   uint16_t* Vs = Ks + NKT * 16 * RS;
@@ -75,6 +81,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     }
   const int nrounds = (qrep + QR - 1) / QR;
   const int qcol = wave * 16 + c;             // this lane's query as a column of the P^T / dS^T images
+  const KeyVis kv = key_visibility<KEYMASK>(mask, (size_t)ctx * mctx, Tk, g);
 #pragma unroll 1
   for (int rd = 0; rd < nrounds; ++rd) {
     // ---- phase A -------------------------------------------------------------------------------------------------
@@ -109,13 +116,16 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k * 16 + g * 4 + r;
-        acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
+        if constexpr (KEYMASK)
+          acc[k][r] = ((kv.bits >> (4 * k + r)) & 1ull) ? (kv.uniform ? 0.f : acc[k][r]) : -INFINITY;
+        else
+          acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
         m = fmaxf(m, acc[k][r]);
       }
     }
     m = fmaxf(m, __shfl_xor(m, 16, 64));
     m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float mk = m * kExp2;                    // key 0 always exists: m is finite
+    const float mk = m * kExp2;                    // key 0 always exists (KEYMASK: a visible key): m is finite
     float l = 0.f;
 #pragma unroll
     for (int k = 0; k < NKT; ++k) {
@@ -156,6 +166,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         dp[k][r] = acc[k][r] * (dp[k][r] - delta);            // dS; masked keys: P = 0
+        if constexpr (KEYMASK) dp[k][r] = kv.uniform ? 0.f : dp[k][r];      // the uniform row does not depend on the scores
         const int key = k * 16 + g * 4 + r;
         const int off = key * RS + ((((qcol >> 3) ^ (key & 7)) << 3) | (qcol & 7));
         if constexpr (DROP)
@@ -227,6 +238,20 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
 }
 
 }  // namespace
+
+// called by lvl_keymask_attn_bwd (keymask_attn.hip) for bf16, Tk <= 256
+int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
+                                     void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride,
+                                     int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st) {
+  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<false, false, true>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<false, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
+                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
+                     (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, Tk, H, qrep,
+                     AttnDrop{}, mask, (size_t)mask_ctx_stride);
+  LVL_CHECK_LAUNCH("keymask_attn_bwd (mfma)");
+  return LVL_OK;
+}
 
 extern "C" int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows,
                                        int qrep, int Tk, int H, int dtype, void* stream) {

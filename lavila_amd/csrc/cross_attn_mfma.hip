@@ -19,6 +19,7 @@
 #include "attn_mfma_common.h"
 #include "dropout.h"
 #include "internal.h"
+#include "keymask.h"
 
 using namespace attn_mfma;
 
@@ -34,12 +35,16 @@ struct AttnDrop {
 };
 
 // q rows at q + row * qs, keys at kp + ctx * kvctx + j * kvs (+ head), values at vp alike; out [rows, D]
-template <bool DROP, bool CAUSAL>
+// KEYMASK (lvl_keymask_attn_fwd): keys of a context are hidden by mask[ctx * mctx + key] == 0 (mask NULL: none); a context
+// with no visible key gets the uniform distribution over its Tk keys
+template <bool DROP, bool CAUSAL, bool KEYMASK = false>
 __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t* __restrict__ q, size_t qs,
                                                                   const uint16_t* __restrict__ kp,
                                                                   const uint16_t* __restrict__ vp, size_t kvs,
                                                                   size_t kvctx, uint16_t* __restrict__ out, int Tk, int H,
-                                                                  int qrep, AttnDrop drop) {
+                                                                  int qrep, AttnDrop drop,
+                                                                  const uint8_t* __restrict__ mask = nullptr,
+                                                                  size_t mctx = 0) {
   extern __shared__ __align__(16) uint16_t xa_smem[];
   uint16_t* Ks = xa_smem;
   uint16_t* Vs = Ks + NKT * 16 * RS;
@@ -55,6 +60,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
   const FragOff fo = frag_offsets(lane);
   uint16_t* ot = Ot + wave * 16 * OS;
   const int ntiles = (qrep + 15) >> 4;
+  const KeyVis kv = key_visibility<KEYMASK>(mask, (size_t)ctx * mctx, Tk, g);
 #pragma unroll 1
   for (int qt = wave; qt < ntiles; qt += XW) {
     const int qrow = qt * 16 + c;
@@ -73,13 +79,16 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k * 16 + g * 4 + r;
-        acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
+        if constexpr (KEYMASK)
+          acc[k][r] = ((kv.bits >> (4 * k + r)) & 1ull) ? (kv.uniform ? 0.f : acc[k][r]) : -INFINITY;
+        else
+          acc[k][r] = (key < Tk && (!CAUSAL || key <= qrow)) ? acc[k][r] : -INFINITY;
         m = fmaxf(m, acc[k][r]);
       }
     }
     m = fmaxf(m, __shfl_xor(m, 16, 64));
     m = fmaxf(m, __shfl_xor(m, 32, 64));
-    const float mk = m * kExp2;                    // key 0 always exists: m is finite
+    const float mk = m * kExp2;                    // key 0 always exists (KEYMASK: a visible key, see key_visibility): m is finite
     float l = 0.f;
 #pragma unroll
     for (int k = 0; k < NKT; ++k) {
@@ -150,6 +159,19 @@ int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int con
                      (const uint16_t*)q, D, (const uint16_t*)kv, (const uint16_t*)kv + D, 2 * D, (size_t)Tk * 2 * D,
                      (uint16_t*)out, Tk, H, qrep, AttnDrop{});
   LVL_CHECK_LAUNCH("cross_attn_rows_fwd (mfma)");
+  return LVL_OK;
+}
+
+// called by lvl_keymask_attn_fwd (keymask_attn.hip) for bf16, Tk <= 256
+int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
+                                     int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                                     int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st) {
+  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<false, false, true>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_mfma_kernel<false, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
+                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
+                     (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, AttnDrop{}, mask, (size_t)mask_ctx_stride);
+  LVL_CHECK_LAUNCH("keymask_attn_fwd (mfma)");
   return LVL_OK;
 }
 

@@ -36,3 +36,11 @@ int lvl_clip_fwd_mfma(const void* img_all, const void* txt_all, const float* sca
 // cross_attn_mfma.hip
 int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
                                hipStream_t st);
+// cross_attn_mfma.hip / cross_attn_bwd_mfma.hip: the key-masked instantiations behind lvl_keymask_attn_fwd / _bwd (bf16,
+// Tk <= 256; keymask_attn.hip holds the entry points and the shape-generic kernels)
+int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
+                                     int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                                     int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st);
+int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
+                                     void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride,
+                                     int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st);

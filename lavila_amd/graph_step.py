@@ -200,6 +200,10 @@ class GraphedTrainStep:
             raise NotImplementedError('GraphedTrainStep: a VCLM_HF that packs its caption rows cannot be replayed (the row '
                                       'count of every step depends on its captions): unset LAVILA_PACK_CAPTIONS / '
                                       'narrator.PACK_CAPTIONS for the graphed step, or run the eager loop')
+        if isinstance(bare, _models.CLIP_HF):
+            raise NotImplementedError('GraphedTrainStep: CLIP_HF is not capturable (the step is called with (video, tokens): '
+                                      'it carries no attention mask, and the DistilBERT tower trims each batch to its longest '
+                                      'caption from a host read); run it with the eager loop')
         if not torch.cuda.is_available():
             raise RuntimeError('GraphedTrainStep needs a HIP device (hipGraph capture)')
         for grp in optimizer.param_groups:

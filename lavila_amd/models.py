@@ -18,6 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import loss, ops
+from .distilbert import DistilBertModel, distilbert_config
 from .gpt2_gated import GPT2LMHeadModel as GatedGPT2LMHeadModel
 from .gpt2_gated import augment_gpt2_config, gpt2_config
 from .narrator import VCLM_HF
@@ -384,6 +385,97 @@ class CLIP(nn.Module):
                 'logit_scale': self.logit_scale.exp()}
 
 
+class CLIP_HF(nn.Module):
+    """models.py:176-290: the dual encoder with a Hugging Face text model behind `textual`. Built: projection='default',
+    text_use_cls_token=True, text_is_regressive=False on lavila_amd.distilbert.DistilBertModel -- what the
+    CLIP_OPENAI_TIMESFORMER_*_DISTILBERT_BASE constructors make. Everything else raises NotImplementedError at
+    construction. The two towers run on one stream (CLIP's text side stream is not used here)."""
+
+    def __init__(self,
+                 embed_dim: int,
+                 # vision
+                 vision_width: int,
+                 vision_model: nn.Module,
+                 # text
+                 text_width: int,
+                 text_model: nn.Module,
+                 text_use_cls_token: bool,
+                 text_is_regressive: bool,
+                 tempearture_init=0.07,      # [sic] models.py:187
+                 **kwargs,
+                 ):
+        super().__init__()
+        self.projection = kwargs['projection'] if 'projection' in kwargs else 'default'
+        if self.projection != 'default':
+            raise NotImplementedError(f'CLIP_HF: projection={self.projection!r} is not built (the \'frozen_in_time\' '
+                                      'projection heads of the CLIP_HF_EGOVLP_* models); only \'default\'')
+        if text_is_regressive:
+            raise NotImplementedError('CLIP_HF: regressive (GPT-style, EOT-row) text models are not built; only '
+                                      'text_is_regressive=False')
+        if not text_use_cls_token:
+            raise NotImplementedError('CLIP_HF: text_use_cls_token=False reads pooler_output, which DistilBERT does not '
+                                      'have; only text_use_cls_token=True')
+        if not isinstance(text_model, DistilBertModel):
+            raise NotImplementedError(f'CLIP_HF: text_model must be lavila_amd.distilbert.DistilBertModel (got '
+                                      f'{type(text_model).__module__}.{type(text_model).__name__}): no other Hugging Face '
+                                      'text tower runs on the HIP kernels')
+        self.vision_width = vision_width
+        self.visual = vision_model
+        self.text_width = text_width
+        self.textual = text_model
+        self.text_use_cls_token = text_use_cls_token
+        self.text_is_regressive = text_is_regressive
+        self.image_projection = nn.Parameter(torch.empty(vision_width, embed_dim))
+        self.text_projection = nn.Parameter(torch.empty(text_width, embed_dim))
+        print("=> initialize initial temperature with {}".format(tempearture_init))
+        self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / tempearture_init))
+        self.initialize_parameters()
+
+    def initialize_parameters(self):
+        nn.init.normal_(self.image_projection, std=self.vision_width ** -0.5)
+        nn.init.normal_(self.text_projection, std=self.text_width ** -0.5)
+
+    def build_attention_mask(self):
+        """models.py:227-233, as the reference has it: it reads self.context_length, which CLIP_HF never sets."""
+        mask = torch.empty(self.context_length, self.context_length)
+        mask.fill_(float("-inf"))
+        mask.triu_(1)
+        return mask
+
+    def encode_image(self, image, use_checkpoint=False, apply_project=True):
+        with ops.model_forward(), _amp_region():
+            x = _features(self.visual, image, use_checkpoint)
+            if not apply_project:
+                return _half_out(x, image, self.image_projection)
+            if x.dtype != self.image_projection.dtype and not torch.is_autocast_enabled():
+                x = x.to(self.image_projection.dtype)
+            return _half_out(ops.project(x, self.image_projection), image, self.image_projection)
+
+    def encode_text(self, text, attention_mask=None, use_checkpoint=False):
+        """models.py:249-279. attention_mask: [B, L] of any real or bool dtype, non-zero = visible; None = all visible.
+        use_checkpoint is accepted and ignored for DistilBERT, as in the reference. Only row 0 of the last layer is read
+        (text_use_cls_token): the tower runs on the columns up to the last visible position of the batch (one host read of
+        a scalar; not under LAVILA_TEXT_TRIM=0 or stream capture) and its last layer on row 0 only."""
+        ops.checkpoint_mode(use_checkpoint)
+        with ops.model_forward(), _amp_region():
+            x = self.textual.first_rows(text, attention_mask)
+            if x.dtype != self.text_projection.dtype and not torch.is_autocast_enabled():
+                x = x.to(self.text_projection.dtype)
+            return _half_out(ops.project(x, self.text_projection), self.text_projection)
+
+    def forward(self, image, text, mask=None, use_checkpoint=False, norm_embed=False):
+        ops.checkpoint_mode(use_checkpoint)           # anything else raises here, before a kernel is enqueued
+        with ops.model_forward():
+            image_embed = self.encode_image(image, use_checkpoint=use_checkpoint)
+            text_embed = self.encode_text(text, attention_mask=mask, use_checkpoint=use_checkpoint)
+            if norm_embed:
+                image_embed = F.normalize(image_embed.float(), dim=-1)
+                text_embed = F.normalize(text_embed.float(), dim=-1)
+            return {'image_embed': image_embed,
+                    'text_embed': text_embed,
+                    'logit_scale': self.logit_scale.exp()}
+
+
 def get_loss(model, args, tokenizer=None):
     if model.startswith('CLIP'):
         return loss.CLIPLoss(use_vissl=args.contrastive_use_vissl, cache_labels=True, rank=args.rank,
@@ -441,9 +533,11 @@ def _load_clip_weights(model, vision_model, clip_sd, layers, project_embed_dim):
         model.logit_scale.data.copy_(clip_sd['logit_scale'])
 
 
-def _clip_openai_timesformer(clip_name, vision_kwargs, vision_width, text_width, text_heads, vision_layers,
-                             num_frames, timesformer_gated_xattn, drop_path_rate, timesformer_freeze_space,
-                             temperature_init, project_embed_dim, kwargs):
+def _openai_timesformer_tower(clip_name, vision_kwargs, vision_layers, num_frames, timesformer_gated_xattn,
+                              drop_path_rate, timesformer_freeze_space):
+    """The video tower of the CLIP_OPENAI_TIMESFORMER_* constructors (CLIP and DistilBERT text sides alike): construction,
+    the OpenAI-CLIP weights when present and the freeze-space logic (models.py:320-349, 498-527). Returns the tower and the
+    CLIP state dict (None without LAVILA_CLIP_WEIGHTS_DIR)."""
     vision_model = SpaceTimeTransformer(
         num_frames=num_frames, time_init='zeros', attention_style='frozen-in-time', ln_pre=True,
         act_layer=QuickGELU, is_tanh_gating=timesformer_gated_xattn, drop_path_rate=drop_path_rate,
@@ -472,6 +566,14 @@ def _clip_openai_timesformer(clip_name, vision_kwargs, vision_width, text_width,
     vision_model.head = nn.Identity()
     vision_model.pre_logits = nn.Identity()
     vision_model.fc = nn.Identity()
+    return vision_model, clip_sd
+
+
+def _clip_openai_timesformer(clip_name, vision_kwargs, vision_width, text_width, text_heads, vision_layers,
+                             num_frames, timesformer_gated_xattn, drop_path_rate, timesformer_freeze_space,
+                             temperature_init, project_embed_dim, kwargs):
+    vision_model, clip_sd = _openai_timesformer_tower(clip_name, vision_kwargs, vision_layers, num_frames,
+                                                      timesformer_gated_xattn, drop_path_rate, timesformer_freeze_space)
     model = CLIP(embed_dim=project_embed_dim, vision_width=vision_width, vision_model=vision_model,
                  context_length=77, vocab_size=49408, transformer_width=text_width,
                  transformer_heads=text_heads, transformer_layers=12, tempearture_init=temperature_init, **kwargs)
@@ -510,6 +612,74 @@ def CLIP_OPENAI_TIMESFORMER_LARGE_336PX(
     return _clip_openai_timesformer('ViT-L/14@336px', vk, 1024, 768, 12, 24, num_frames, timesformer_gated_xattn,
                                     drop_path_rate, timesformer_freeze_space, temperature_init, project_embed_dim,
                                     kwargs)
+
+
+def load_pretrained_distilbert(name):
+    """The reference fetches the checkpoint from the hub (`DistilBertModel.from_pretrained`, models.py:529-531). Offline:
+    LAVILA_DISTILBERT_WEIGHTS_DIR/<name>.pt holding the HF state_dict, else the tower keeps its initialisation."""
+    root = os.environ.get('LAVILA_DISTILBERT_WEIGHTS_DIR')
+    if not root:
+        import warnings
+        warnings.warn(f'lavila_amd: pretrained {name} weights are NOT loaded (no network; set '
+                      'LAVILA_DISTILBERT_WEIGHTS_DIR): the text tower keeps its random initialisation, unlike the '
+                      'reference constructor', stacklevel=3)
+        return None
+    path = os.path.join(root, name + '.pt')
+    if not os.path.isfile(path):
+        raise RuntimeError(f'DistilBERT checkpoint {name} not found at {path}')
+    return torch.load(path, map_location='cpu', weights_only=True)
+
+
+def _clip_openai_timesformer_distilbert(clip_name, vision_kwargs, vision_layers, num_frames, timesformer_gated_xattn,
+                                        drop_path_rate, timesformer_freeze_space, temperature_init, project_embed_dim,
+                                        kwargs):
+    """The common body of models.py:494-657: the TimeSformer tower of _clip_openai_timesformer (its CLIP weights loaded with
+    strict=False as there) and distilbert-base-uncased as `textual`. The config holds dropout = attention_dropout = 0.0
+    (from_pretrained's is 0.1): lavila_amd.distilbert has no dropout."""
+    vision_model, clip_sd = _openai_timesformer_tower(clip_name, vision_kwargs, vision_layers, num_frames,
+                                                      timesformer_gated_xattn, drop_path_rate, timesformer_freeze_space)
+    if clip_sd is not None:
+        vis = {k[len('visual.'):]: v for k, v in clip_sd.items() if k.startswith('visual.')}
+        print(vision_model.load_state_dict(remap_keys(vis, transformer_layers=vision_layers), strict=False))
+    text_model = DistilBertModel(distilbert_config('distilbert-base-uncased'))
+    sd = load_pretrained_distilbert('distilbert-base-uncased')
+    if sd is not None:
+        text_model.load_state_dict(sd, strict=True)
+    kwargs.pop('text_use_cls_token')  # ignore args.use_cls_token since DistilBert does not have pooler on top
+    return CLIP_HF(embed_dim=project_embed_dim, vision_width=vision_model.embed_dim, vision_model=vision_model,
+                   text_width=768, text_model=text_model, text_use_cls_token=True, text_is_regressive=False,
+                   tempearture_init=temperature_init, **kwargs)
+
+
+def CLIP_OPENAI_TIMESFORMER_BASE_DISTILBERT_BASE(
+    num_frames=4, timesformer_gated_xattn=False, drop_path_rate=0, timesformer_freeze_space=False,
+    temperature_init=0.07, project_embed_dim=256, **kwargs,
+):
+    """models.py:494-545: TSF-B/16 @224 + DistilBERT (768 wide, 12 heads, 6 layers). `text_use_cls_token` must be among
+    the kwargs, as in the reference (it is popped and ignored)."""
+    return _clip_openai_timesformer_distilbert('ViT-B/16', {}, 12, num_frames, timesformer_gated_xattn, drop_path_rate,
+                                               timesformer_freeze_space, temperature_init, project_embed_dim, kwargs)
+
+
+def CLIP_OPENAI_TIMESFORMER_LARGE_DISTILBERT_BASE(
+    num_frames=4, timesformer_gated_xattn=False, drop_path_rate=0, timesformer_freeze_space=False,
+    temperature_init=0.07, project_embed_dim=256, **kwargs,
+):
+    """models.py:548-601: TSF-L/14 @224 + DistilBERT."""
+    vk = dict(img_size=224, patch_size=14, embed_dim=1024, depth=24, num_heads=16)
+    return _clip_openai_timesformer_distilbert('ViT-L/14', vk, 24, num_frames, timesformer_gated_xattn, drop_path_rate,
+                                               timesformer_freeze_space, temperature_init, project_embed_dim, kwargs)
+
+
+def CLIP_OPENAI_TIMESFORMER_LARGE_336PX_DISTILBERT_BASE(
+    num_frames=4, timesformer_gated_xattn=False, drop_path_rate=0, timesformer_freeze_space=False,
+    temperature_init=0.07, project_embed_dim=256, **kwargs,
+):
+    """models.py:604-657: TSF-L/14 @336 + DistilBERT, the published high-resolution recipe (docs/PRETRAIN.md)."""
+    vk = dict(img_size=336, patch_size=14, embed_dim=1024, depth=24, num_heads=16)
+    return _clip_openai_timesformer_distilbert('ViT-L/14@336px', vk, 24, num_frames, timesformer_gated_xattn,
+                                               drop_path_rate, timesformer_freeze_space, temperature_init,
+                                               project_embed_dim, kwargs)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1648,6 +1648,50 @@ def causal_attention(qkv, heads, bias=None):
     return _CausalAttnFn.apply(lowp(qkv), bias, heads)
 
 
+class _KeymaskAttnFn(torch.autograd.Function):
+    """lvl_keymask_attn_fwd / _bwd on three separate tensors: q [B, Lq, D] (Lq query rows per sample; Lq = 1 is the row-0
+    form), k / v [B, Tk, D], keymask uint8 [B, Tk] (non-zero = visible) or None."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, keymask, heads):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        C.require_device(q, k, v, keymask)
+        B, Tk, D = k.shape
+        if D != heads * 64:
+            raise C.HipExtensionError(f'key-masked attention: width {D} != heads*64 ({heads} heads)')
+        if q.shape[0] != B or q.shape[-1] != D or v.shape != k.shape or q.dtype != k.dtype or v.dtype != k.dtype:
+            raise C.HipExtensionError(f'key-masked attention: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, '
+                                      f'v {tuple(v.shape)} {v.dtype} do not belong together')
+        if keymask is not None and (keymask.dtype != torch.uint8 or tuple(keymask.shape) != (B, Tk)):
+            raise C.HipExtensionError(f'key-masked attention: the mask must be uint8 [{B}, {Tk}]')
+        qrep = q.numel() // (B * D) if B else 1
+        out = torch.empty_like(q)
+        C.check(C.lib().lvl_keymask_attn_fwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(keymask), C.ptr(out), B, qrep, Tk, heads, D, D,
+                                             Tk * D, Tk, C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_fwd')
+        ctx.save_for_backward(q, k, v)
+        ctx.keymask = keymask                  # a byte mask (no gradient, not an output): kept as a plain attribute
+        ctx.cfg = (B, qrep, Tk, heads, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v = ctx.saved_tensors
+        B, qrep, Tk, H, D = ctx.cfg
+        dout = dout.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ws = C.workspace('keymask_attn_bwd', B * qrep * H, Tk, q.device)
+        C.check(C.lib().lvl_keymask_attn_bwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(ctx.keymask), C.ptr(dout), C.ptr(dq),
+                                             C.ptr(dk), C.ptr(dv), C.ptr(ws), B, qrep, Tk, H, D, D, Tk * D, Tk,
+                                             C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_bwd')
+        return dq, dk, dv, None, None
+
+
+def keymask_attention(q, k, v, keymask, heads):
+    """Bidirectional attention whose keys are hidden per sample (DistilBERT under an attention_mask): softmax over the
+    visible keys of each sample, exact zeros for hidden ones; keymask uint8 [B, Tk], non-zero = visible, None = all."""
+    return _KeymaskAttnFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads)
+
+
 # --------------------------------------------------------------------------------------------------
 # contrastive head (raw kernels; the autograd wrapper + collectives live in lavila_amd/loss.py)
 # --------------------------------------------------------------------------------------------------
