@@ -137,16 +137,38 @@ __device__ __forceinline__ void gm_store16(void* p, uint4 v) { *reinterpret_cast
 // GM_AUDIT (debug build only, tests/test_gpu_gemm_tails.py): every wave counts the vector-memory stores its epilogue
 // ISSUES, at the issue sites, and records them with the vmcnt allowance the next tile's first K blocks use (see NS below).
 // Per lane: byte j of gm_aud_st = stores issued in row group j while the lane was live, gm_aud_cp = column-partial stores.
+//
+// FILL-ORDER AUDIT (same build, tests/test_gpu_gemm_kblocks.py). The store count shows that an allowance is not larger than
+// the stores behind it; it does not show that the fill a barrier waits for is OLDER than the operations its vmcnt(N) leaves
+// in flight -- the statement that depends on the number of K blocks per tile. Every wave numbers the vector-memory
+// operations it certainly issues (aud_seq: each fill, wave 0's bias DMA and counter atomic, the epilogue's stores as counted
+// above; the aux_in loads are left out -- an operation that is not counted only makes the fills in front of it older than
+// the audit assumes) and keeps, in wave-uniform integers:
+//   aud_done        max over every `s_waitcnt vmcnt(N)` written in the kernel of aud_seq - N: operations numbered <= aud_done
+//                   have completed (they return in issue order)
+//   aud_fill_*[t]   aud_seq after this wave's second fill of slot type t in the ring half, aud_bias*[i & 3] / aud_pull the same
+//                   for wave 0's bias image of tile ordinal i and its counter atomic
+// and checks `number <= aud_done` where the kernel relies on it (check codes GM_CHK_*): at every GM_BAR for the slot the
+// phase behind it reads, at init_acc for the bias image (the drain behind a tail tile's epilogue is entered into aud_done
+// only behind that check: the other waves have the image through the last BARRIER behind a wait of wave 0, not through a
+// wait of wave 0 alone), at publish for the counter reply, at the epilogue's re-read of xA / wA for both slots.
+// A wave's audit header holds {records, violations, code of the first violation, tightest margin aud_done - number seen}.
 #ifdef GM_AUDIT
+#define GM_AUD(...) __VA_ARGS__
 #define GM_AUD_STORE(j) (gm_aud_st += 1u << (8 * (j)))
 #define GM_AUD_COLPART() (++gm_aud_cp)
 constexpr int GM_AUDIT_CAP = 255;      // records per wave (one per tile boundary)
+// first-violation code: 1 << 30 | check << 24 | min(K block, 4095) << 12 | min(tile ordinal, 4095); K block = nb for the
+// checks inside and behind an epilogue, tile ordinal = the tile being multiplied or finished
+enum { GM_CHK_OPEN_X0 = 0, GM_CHK_OPEN_W0 = 1, GM_CHK_P0_W1 = 2, GM_CHK_P1_X1 = 3, GM_CHK_P2_X0 = 4, GM_CHK_P3_W0 = 5,
+       GM_CHK_BIAS = 6, GM_CHK_PULL = 7, GM_CHK_REREAD_X0 = 8, GM_CHK_REREAD_W0 = 9 };
 __device__ __forceinline__ int gm_wave_max(int v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
   return v;
 }
 #else
+#define GM_AUD(...)
 #define GM_AUD_STORE(j) ((void)0)
 #define GM_AUD_COLPART() ((void)0)
 #endif
@@ -190,18 +212,49 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   // that covers the atomic (tests/test_boundary_cpu.py checks in the ISA that nothing else touches the register).
   uint32_t pend = 0;
   unsigned* const ctr = sched + xcd;
+#ifdef GM_AUDIT
+  // fill-order audit (see GM_AUDIT above): wave-uniform, scalar registers only
+  int aud_seq = 0, aud_done = 0, aud_pull = 0, aud_at = 0;      // aud_at: min(K block, 4095) << 12 | min(tile ordinal, 4095)
+  int aud_viol = 0, aud_first = 0, aud_margin = 0x7fffffff;
+  int aud_fill_lo[4] = {0, 0, 0, 0}, aud_fill_hi[4] = {0, 0, 0, 0};      // by slot type; ring half 0 / 1
+  int aud_bias0 = 0, aud_bias1 = 0, aud_bias2 = 0, aud_bias3 = 0;       // by tile ordinal & 3 (wave 0)
+  auto aud_here = [&](int ti, int kb) { aud_at = min(kb, 4095) << 12 | min(ti, 4095); };
+  auto aud_wait = [&](int n) { aud_done = max(aud_done, aud_seq - n); };
+  auto aud_check = [&](int number, int chk) {
+    const int margin = aud_done - number;
+    aud_margin = min(aud_margin, margin);
+    aud_first = margin < 0 && aud_viol == 0 ? 1 << 30 | chk << 24 | aud_at : aud_first + 0;      // (selects: no new basic blocks)
+    aud_viol += margin < 0 ? 1 : 0;
+  };
+  // (`+ 0`: a conditional of two lvalues is an lvalue -- a select of ADDRESSES, which would put the integers into scratch)
+  auto aud_slot = [&](int chk, int type, int half) { aud_check(half ? aud_fill_hi[type] + 0 : aud_fill_lo[type] + 0, chk); };
+  auto aud_bias_set = [&](int i) {
+    aud_bias0 = (i & 3) == 0 ? aud_seq + 0 : aud_bias0 + 0;
+    aud_bias1 = (i & 3) == 1 ? aud_seq + 0 : aud_bias1 + 0;
+    aud_bias2 = (i & 3) == 2 ? aud_seq + 0 : aud_bias2 + 0;
+    aud_bias3 = (i & 3) == 3 ? aud_seq + 0 : aud_bias3 + 0;
+  };
+  auto aud_bias_get = [&](int i) {
+    const int odd = (i & 1) ? aud_bias1 + 0 : aud_bias0 + 0, odd2 = (i & 1) ? aud_bias3 + 0 : aud_bias2 + 0;
+    return (i & 2) ? odd2 + 0 : odd + 0;
+  };
+#endif
   // (lane 0 only: EXEC is narrowed inside the asm -- a divergent C++ branch here would make the compiler treat the
   // loop-carried tile cursor as divergent and move the DMA base addresses into vector registers)
   uint64_t exec_save;
   auto pull = [&]() {
-    if (wave == 0)
+    if (wave == 0) {
       asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tglobal_atomic_add %0, %2, %3, %4 sc0\n\ts_mov_b64 exec, %1"
                    : "=v"(pend), "=&s"(exec_save) : "v"(0u), "v"(1u), "s"(ctr) : "memory");
+      GM_AUD(aud_pull = ++aud_seq;)
+    }
   };
   auto publish = [&]() {
-    if (wave == 0)
+    if (wave == 0) {
+      GM_AUD(aud_check(aud_pull, GM_CHK_PULL);)
       asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_write_b32 %1, %2\n\ts_mov_b64 exec, %0"
                    : "=&s"(exec_save) : "v"((uint32_t)(uintptr_t)smem + MBOX_OFF), "v"(pend) : "memory");
+    }
   };
   // (an LDS read in asm: through a volatile C++ pointer the compiler emits a FLAT load and waits vmcnt(0) for it -- a
   // full drain of the run-ahead fills once per tile, 2-4 % of a launch on the dynamic schedule until round 6)
@@ -262,6 +315,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       const char* base = reinterpret_cast<const char*>(bias + tn * TN);
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(off), "s"(base)
                    : "memory", "m0");
+      GM_AUD(++aud_seq; aud_bias_set(i);)
     }
   };
   auto fetch_advance = [&]() {
@@ -299,6 +353,10 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
         __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(par + type) * SLOT + (uint32_t)wave * 1024 + h * 8192);
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0v), "v"(off), "s"(base)
                  : "memory", "m0");
+    GM_AUD(++aud_seq; if (h == 1) {
+      aud_fill_hi[type] = par ? aud_seq + 0 : aud_fill_hi[type] + 0;
+      aud_fill_lo[type] = par ? aud_fill_lo[type] + 0 : aud_seq + 0;
+    })
   };
   auto issue_group = [&](int type, int par) {
     issue_fill(type, par, 0);
@@ -336,6 +394,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   auto init_acc = [&](int ti) {
     if (EPI != 2 && bias != nullptr) {
       const uint8_t* bias_img = smem + BIAS_OFF + (ti & 3) * 1024;
+      GM_AUD(if (wave == 0) aud_check(aud_bias_get(ti), GM_CHK_BIAS);)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -560,6 +619,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
         }
         if (j == 3) {                      // re-read of xA / wA
           __builtin_amdgcn_sched_barrier(0);
+          GM_AUD(aud_slot(GM_CHK_REREAD_X0, S_X0, par); aud_slot(GM_CHK_REREAD_W0, S_W0, par);)
           read_x(par + S_X0, xA);
           read_w(par + S_W0, wA);
           __builtin_amdgcn_sched_barrier(0);
@@ -612,8 +672,9 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #define GM_STAMP() do { } while (0)
 #endif
 #ifdef GM_AUDIT
-  // [gridDim.x][8 waves][1 + GM_AUDIT_CAP][4] ints behind the column partials (as GM_TRACE): a header {records} and, for
-  // every tile ordinal i >= 1, {tm, tn of tile i-1, stores the wave issued in tile i-1's epilogue, allowance used}
+  // [gridDim.x][8 waves][1 + GM_AUDIT_CAP][4] ints behind the column partials (as GM_TRACE): a header {records, fill-order
+  // violations, code of the first one, tightest margin (0x7fffffff: the wave made no check)} and, for every tile ordinal
+  // i >= 1, {tm, tn of tile i-1, stores the wave issued in tile i-1's epilogue, allowance used}
   int* const audit = reinterpret_cast<int*>(colpart + ((EPI == 2 || EPI == 5) ? (size_t)2 * (ntiles / tiles_n) * N : 0)) +
                      ((size_t)bid * 8 + wave) * (1 + GM_AUDIT_CAP) * 4;
   int aud_n = 0, aud_rec[4] = {0, 0, 0, 0};
@@ -622,6 +683,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     my_tiles = 0;                               // as if the queues were drained
   } else if (dyn) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    GM_AUD(aud_wait(0);)
     publish();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -655,10 +717,12 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   // until the fills of the slot the next phase reads have landed: fills return in order, so "all but the N newest
   // vector-memory operations" with N = the operations issued after that slot's fills (10 / 8 / 10 / 10 for P0..P3;
   // the bias image and the epilogue's stores only make the wait stricter). The barrier is the bare s_barrier: a
-  // fence would drain the run-ahead fills.
-#define GM_BAR(N)                                                     \
+  // fence would drain the run-ahead fills. (CHK: the GM_AUDIT build's check of the slot(s) the phase behind the barrier
+  // reads; dropped from every other build.)
+#define GM_BAR(N, CHK)                                                \
   do {                                                                \
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");          \
+    GM_AUD(aud_wait(N); CHK;)                                         \
     __builtin_amdgcn_s_barrier();                                     \
     asm volatile("" ::: "memory");                                    \
     __builtin_amdgcn_sched_barrier(0);                                \
@@ -676,7 +740,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       }                                                                                                   \
     }                                                                                                     \
   } while (0)
-  GM_BAR(12);                            // X0 and W0 of block 0 have landed
+  GM_BAR(12, (aud_slot(GM_CHK_OPEN_X0, S_X0, 0), aud_slot(GM_CHK_OPEN_W0, S_W0, 0)));      // X0 and W0 of block 0 have landed
   read_x(S_X0, xA);
   read_w(S_W0, wA);
   __builtin_amdgcn_sched_barrier(0);
@@ -696,6 +760,12 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   // the stores counted at the issue sites and the allowance used (tests/test_gpu_gemm_tails.py checks slack <= issued).
   // (f32-class mode: its 32 / 64 wider stores would overflow the 6-bit vmcnt field together with the fills -- no
   // allowance there: the first blocks of the next tile also wait for the previous tile's stores)
+  // K BLOCKS PER TILE. "Filled before that epilogue, with exactly the counted operations behind" holds for the slots the two
+  // blocks behind an epilogue read at every nb >= 2 (the GM_AUDIT build's fill-order audit checks every barrier at nb = 1 .. 9
+  // and finds the tightest margin 0: tests/test_gpu_gemm_kblocks.py). At nb = 1 a tile is ONE block and the fetch cursor runs two
+  // TILES ahead: what P0 / P1 read behind tile i's epilogue was filled during tile i-1's block, in front of tile i-1's epilogue
+  // too -- the stores of two epilogues lie behind those fills and the allowance counts one. Those two waits are stricter than
+  // they need be by NS there, never looser; P2 / P3 (filled during tile i's block) are exact again.
   constexpr int NS = F32O ? 0 : (EPI == 1 || EPI == 4 ? 32 : 16);
   auto k_block = [&](auto a0_, auto a1_) {
     constexpr int A0 = decltype(a0_)::value, A1 = decltype(a1_)::value;
@@ -721,13 +791,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       if (k == 0) issue_fill(S_X1, par, 0);
       if (k == 4) issue_fill(S_X1, par, 1);
     };
-    GM_BAR(10 + A0);
+    GM_BAR(10 + A0, aud_slot(GM_CHK_P0_W1, S_W1, par));
     GM_PHASE(xA, wA, acc[0][0], rd_w1, dm_none);
-    GM_BAR(8 + A0);
+    GM_BAR(8 + A0, aud_slot(GM_CHK_P1_X1, S_X1, par));
     GM_PHASE(xA, wB, acc[0][1], rd_x1, dm_x0w0);
-    GM_BAR(10 + A1);
+    GM_BAR(10 + A1, aud_slot(GM_CHK_P2_X0, S_X0, par ^ 4));
     GM_PHASE(xB, wB, acc[1][1], rd_x0, dm_w1);
-    GM_BAR(10 + A1);
+    GM_BAR(10 + A1, aud_slot(GM_CHK_P3_W0, S_W0, par ^ 4));
     GM_PHASE(xB, wA, acc[1][0], rd_w0, dm_x1);
     fetch_advance();
     par ^= 4;
@@ -744,15 +814,21 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       }
       ++aud_n;
 #endif
+      GM_AUD(aud_here(i, 0);)
       k_block(IS{}, IS{});
+      GM_AUD(aud_here(i, 1);)
       if (nb > 1) k_block(IS{}, I0{});
       j = 2;
     }
     for (; j < nb; ++j) {
+      GM_AUD(aud_here(i, j);)
       if (dyn && j == 2) {
         // K block 2: the counter reply asked for before the previous tile's epilogue is an epilogue and 16 fills old;
         // "all but the 10 newest" -- the wait the next barrier performs anyway -- has it in its register
-        if (wave == 0) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+        if (wave == 0) {
+          asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+          GM_AUD(aud_wait(10);)
+        }
         publish();
       }
       k_block(I0{}, I0{});
@@ -765,8 +841,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     // here the fills in front of it are the ones the next barriers wait for (the next tile's blocks 0 and 1 were
     // fetched before this point), and the epilogue (~3 us) plus two K blocks pass before anything behind it is awaited.
     // (Issued at the top of a tile the reply delayed that tile's first fills: +3 % on the K = 768 shapes.)
+    GM_AUD(aud_here(i, nb);)
     if (dyn && my_tiles == 0x7fffffff) pull();
-    const int pair = get_pair(i);
+    // (static schedule: recomputed, not get_pair(i) -- the two-entry store is indexed by i & 1, and with fewer than three K
+    // blocks per tile the fetch cursor has called fetch_tile(i + 2) -> set_pair(i + 2) BEFORE this epilogue: in the prologue
+    // at nb = 1, at the end of this tile's last block at nb = 2. Tile i's results then went to tile i + 2's place and tile i
+    // was never written. The dynamic schedule runs from DYN_MIN_NB on: its cursor wraps three blocks before the end.)
+    const int pair = dyn ? get_pair(i) : xstart + bid / nx + i * wpx;
     int tm, tn;
     decode_tile(pair, tm, tn);
     epilogue(tm, tn, i);
@@ -778,6 +859,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       int issued = gm_wave_max((int)gm_aud_cp);
 #pragma unroll
       for (int q = 0; q < 4; ++q) issued += gm_wave_max((int)((gm_aud_st >> (8 * q)) & 255u));
+      issued = __builtin_amdgcn_readfirstlane(issued);
+      aud_seq += issued;
       aud_rec[0] = tm;
       aud_rec[1] = tn;
       aud_rec[2] = issued;
@@ -787,6 +870,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #endif
     GM_STAMP();
     init_acc(i + 1);
+    // (the drain counts only from here: the OTHER waves have wave 0's bias image through the last barrier, not through it)
+    GM_AUD(if (tail) aud_wait(0);)
     __builtin_amdgcn_sched_barrier(0);
   }
   }
@@ -794,7 +879,12 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
 #undef GM_PHASE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // drain the run-ahead fills before this workgroup's LDS is freed
 #ifdef GM_AUDIT
-  if (lane == 0) audit[0] = aud_n;
+  if (lane == 0) {
+    audit[0] = aud_n;
+    audit[1] = aud_viol;
+    audit[2] = aud_first;
+    audit[3] = aud_margin;
+  }
 #endif
   // the last pull's reply is never consumed: keep its register reserved until the drain above has delivered it
   asm volatile("" ::"v"(pend));

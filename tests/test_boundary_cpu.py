@@ -264,17 +264,17 @@ def test_weight_cache_sees_out_of_band_parameter_writes():
     assert torch.equal(ops.weight_copies(p)[0].float(), p.detach().to(torch.bfloat16).float())
 
 
-def _isa(tmp_path, name):
+def _isa(tmp_path, name, defines=()):
     import shutil
     import subprocess
     hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
     if not os.path.exists(hipcc):
         pytest.skip('hipcc not available')
     src = os.path.join(ROOT, 'lavila_amd', 'csrc', name + '.hip')
-    out = tmp_path / (name + '.s')
+    out = tmp_path / (name + ''.join('.' + d for d in defines) + '.s')
     from lavila_amd.build import EXTRA_FLAGS          # the per-file flags of the shipped build
     subprocess.run([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-S',
-                    '--cuda-device-only', *EXTRA_FLAGS.get(name + '.hip', []), src, '-o', str(out)], check=True,
+                    '--cuda-device-only', *['-D' + d for d in defines], *EXTRA_FLAGS.get(name + '.hip', []), src, '-o', str(out)], check=True,
                    capture_output=True, timeout=900)
     return open(out).read().split('\n')
 
@@ -346,7 +346,10 @@ def test_gemm_tile_counter_reply_register_is_untouched_in_isa(tmp_path):
     csrc/wgrad_mfma.hip). That is only sound if the compiler never copies, spills or reuses that register between the
     request and the LDS publish behind the covering vmcnt wait. Checked where it can be checked without a GPU: in the
     gfx950 ISA of every instantiation (see _check_parked_reply_registers); the kernels of the benched configuration must
-    also be free of scratch spills (a spill reload is a vector-memory operation inside the counted vmcnt schedule)."""
+    also be free of scratch spills (a spill reload is a vector-memory operation inside the counted vmcnt schedule). The
+    GM_AUDIT build of the GEMM (tests/test_gpu_gemm_tails.py, tests/test_gpu_gemm_kblocks.py) counts the vector-memory
+    operations of that schedule: it must not add any of its own -- no VGPR spill and no private segment at all in any
+    instantiation (its bookkeeping is wave-uniform and lives in scalar registers), by the code-object metadata."""
     lines = _isa(tmp_path, 'gemm_tn_mfma')
     bodies = list(_kernel_bodies(lines, 'gemm_tn_kernel'))
     assert len(bodies) == 10                # 6 bf16 epilogues + 4 f32-class ones (Lb1E: float32 results)
@@ -357,6 +360,17 @@ def test_gemm_tile_counter_reply_register_is_untouched_in_isa(tmp_path):
             mf = [i for i, l in enumerate(body) if l.startswith('v_mfma')]
             assert not any('scratch_' in l for l in body[mf[0]:mf[-1]]), f'VGPR spills inside the tile loop of {name}'
         _check_parked_reply_registers(name, body, 3)           # first hand-out, tile 1, the per-tile pull
+    meta = {}
+    for l in _isa(tmp_path, 'gemm_tn_mfma', defines=('GM_AUDIT',)):
+        m = re.match(r'\s+\.(name|private_segment_fixed_size|vgpr_spill_count):\s+(\S+)', l)
+        if m and m.group(1) == 'name':
+            cur = meta.setdefault(m.group(2), {})          # (.name precedes the two figures in a kernel's metadata)
+        elif m:
+            cur[m.group(1)] = int(m.group(2))
+    meta = {k: v for k, v in meta.items() if 'gemm_tn_kernel' in k}
+    assert len(meta) == 10
+    for name, v in meta.items():
+        assert v == {'private_segment_fixed_size': 0, 'vgpr_spill_count': 0}, (name, v)
     lines = _isa(tmp_path, 'wgrad_mfma')
     bodies = list(_kernel_bodies(lines, 'wgrad_kernel'))
     assert len(bodies) == 16
