@@ -33,7 +33,8 @@ enum { LVL_F32 = 0, LVL_BF16 = 1 };
 enum { LVL_OK = 0, LVL_EINVAL = -22, LVL_ENOSYS = -38, LVL_EHIP = -5 };
 enum { LVL_ATTN_SPACE = 0, LVL_ATTN_TIME = 1, LVL_ATTN_CAUSAL = 2 /* lvl_attention_fast_path only */ };
 enum { LVL_EPI_BIAS = 0, LVL_EPI_BIAS_QUICKGELU = 1, LVL_EPI_QUICKGELU_BWD = 2, LVL_EPI_BIAS_RESIDUAL = 3,
-       LVL_EPI_BIAS_QUICKGELU_DERIV = 4, LVL_EPI_MUL_AUX_COLSUM = 5 };
+       LVL_EPI_BIAS_QUICKGELU_DERIV = 4, LVL_EPI_MUL_AUX_COLSUM = 5, LVL_EPI_BIAS_GELU = 6, LVL_EPI_GELU_BWD = 7,
+       LVL_EPI_BIAS_GELU_DERIV = 8 };
 /* activations of the narrator decoder's MLPs (lvl_act_inplace) */
 enum { LVL_ACT_GELU_NEW = 0, LVL_ACT_SQRELU = 1, LVL_ACT_GELU_ERF = 2 };
 
@@ -612,12 +613,22 @@ int lvl_sample_next_token(const void* logits, int64_t row_stride, int rows, int 
  *                            not u, and the forward holds s in a register (one exp2 + one reciprocal serve both outputs)
  *   LVL_EPI_MUL_AUX_COLSUM   (bf16 only) y = acc * aux_in; colsum[N] f32 = column sums of y: LVL_EPI_QUICKGELU_BWD on the
  *                            stored derivative (no transcendental in the backward's epilogue)
+ *   LVL_EPI_BIAS_GELU        LVL_EPI_BIAS_QUICKGELU with the exact GELU y = 0.5 u (1 + erf(u / sqrt 2)) (nn.GELU(), the default
+ *                            act_layer of the reference's SpaceTimeTransformer): aux_out = u = bf16(acc + bias), y = gelu(u) on
+ *                            the ROUNDED u with the arithmetic of lvl_act_fwd(LVL_ACT_GELU_ERF), which rebuilds y from the kept
+ *                            u to the bit
+ *   LVL_EPI_GELU_BWD         LVL_EPI_QUICKGELU_BWD for the same: y = acc * gelu'(aux_in), gelu'(u) = Phi(u) + u phi(u) (the
+ *                            arithmetic of lvl_act_bwd); colsum as there
+ *   LVL_EPI_BIAS_GELU_DERIV  (bf16 only) LVL_EPI_BIAS_QUICKGELU_DERIV for the same: u = acc + bias (f32, not rounded);
+ *                            y = gelu(u); aux_out = gelu'(u), in [-0.129, 1.129]; one erf serves both outputs. The backward
+ *                            is LVL_EPI_MUL_AUX_COLSUM on the stored derivative
  * aux_out / aux_in: [M,N] bf16. N % 256 == 0 and K % 64 == 0 (operands < 4 GiB), else LVL_ENOSYS. Workspace (QUICKGELU_BWD /
- * MUL_AUX_COLSUM only): lvl_workspace_floats("linear_tn", M, N) floats.
+ * MUL_AUX_COLSUM / GELU_BWD only): lvl_workspace_floats("linear_tn", M, N) floats.
  * dtype = LVL_F32 selects the F32-CLASS MODE of the same kernel (the parity configuration, north_star "within 1e-3
  * fp32"): x [M, 3K0] and w [N, 3K0] are the bf16 term images lvl_split_bf16x3 writes (role 0 for x, role 1 for w;
  * K = 3*K0, K0 % 64 == 0), so that one pass accumulates xh.wh + xh.wl + xl.wh in f32 (~2^-17 relative per product);
- * y, aux_out and aux_in are FLOAT32 [M,N] and the QuickGELU epilogues see the unrounded pre-activation. Same tiling,
+ * y, aux_out and aux_in are FLOAT32 [M,N] and the QuickGELU / GELU epilogues see the unrounded pre-activation
+ * (the two *_DERIV epilogues and MUL_AUX_COLSUM are bf16 only: LVL_ENOSYS). Same tiling,
  * LDS-DMA ring, MFMA schedule, bias path and tile schedule as the bf16 mode.
  * sched (nullable): the launch's TILE-COUNTER block, 16 x uint32 (64-byte aligned), ZERO on entry; the kernel leaves it
  * zero again when its last workgroup exits, so a caller may hand the same block to the next launch on the SAME stream

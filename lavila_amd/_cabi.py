@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'liblavila_hip.so')
 LVL_F32, LVL_BF16 = 0, 1
 ATTN_SPACE, ATTN_TIME = 0, 1
 EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_QUICKGELU_BWD, EPI_BIAS_RESIDUAL, EPI_BIAS_QUICKGELU_DERIV, EPI_MUL_AUX_COLSUM = 0, 1, 2, 3, 4, 5
+EPI_BIAS_GELU, EPI_GELU_BWD, EPI_BIAS_GELU_DERIV = 6, 7, 8      # the exact (erf) GELU twins of epilogues 1, 2, 4
 LN_PLAIN, LN_GENERAL = 1, 2          # flags of lvl_layernorm_*_mixed
 ACT_GELU_NEW, ACT_SQRELU, ACT_GELU_ERF = 0, 1, 2
 

@@ -28,7 +28,7 @@ ARCH = 'gfx950'
 # LayerNorm forward (+20 % WITHOUT them), the time attention and the streaming kernels keep the default.
 _NO_SLP = ['-fno-slp-vectorize']
 EXTRA_FLAGS = {'attn_space_mfma.hip': ['-fno-honor-nans'], 'attn_space_stream.hip': ['-fno-honor-nans'],
-               'gemm_tn_mfma.hip': _NO_SLP, 'attn_space_bwd.hip': _NO_SLP}
+               'gemm_tn_mfma.hip': _NO_SLP, 'gemm_tn_gelu.hip': _NO_SLP, 'attn_space_bwd.hip': _NO_SLP}
 
 
 def _hipcc():

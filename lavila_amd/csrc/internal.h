@@ -23,6 +23,10 @@ int lvl_launch_column_reduce_tail(const float* part, int nparts, int width, int 
 int64_t lvl_qkv_bias_ws_floats(int D);
 int lvl_qkv_bias_sources(const void* dqkv, const void* dout, float* dbias, float* ws, int64_t rows, int D, int dtype,
                          bool zero_k, const float* v_src, hipStream_t st);
+// gemm_tn_gelu.hip: one launch of the persistent TN GEMM with an exact-GELU epilogue (LVL_EPI_BIAS_GELU / _GELU_BWD /
+// _BIAS_GELU_DERIV; f32: the f32-class mode), for lvl_linear_tn's dispatch
+int lvl_launch_tn_gelu(const void* x, const void* w, const float* bias, void* y, void* aux_out, const void* aux_in,
+                       float* colpart, int64_t M, int N, int K, uint32_t* sched, int epilogue, int f32, hipStream_t st);
 // gemm_tn_edge.hip: the 64 / 128 / 192 columns behind the full tiles of lvl_linear_tn_ragged
 int lvl_launch_tn_edge(const void* x, const void* w, const float* bias, void* y, int64_t M, int N, int K, int n_first,
                        hipStream_t st);

@@ -5,7 +5,8 @@ swallowed exactly as the reference's **kwargs do), output dict keys and state_di
 main_pretrain.py / eval_zeroshot.py drive it unchanged. Built: the dual-encoder pretraining path
 and the narrator on TimeSformer towers (`VCLM_OPENAI_TIMESFORMER_*`, :887-1198; lavila_amd.narrator +
 lavila_amd.gpt2_gated) and the classification fine-tune's `VideoClassifier` / `VideoClassifierMultiHead` (:24-72). The
-per-frame ViT narrators (`VCLM_OPENAI_VIT*`) and DistilBERT are absent.
+per-frame ViT narrators (`VCLM_OPENAI_VIT*`) are absent; `CLIP_HF` (:176-290) runs on DistilBERT with the default projection
+(`CLIP_OPENAI_TIMESFORMER_*_DISTILBERT_BASE`, `CLIP_HF_TIMESFORMER_DISTILBERT_BASE`).
 """
 import contextlib
 import os
@@ -680,6 +681,46 @@ def CLIP_OPENAI_TIMESFORMER_LARGE_336PX_DISTILBERT_BASE(
     return _clip_openai_timesformer_distilbert('ViT-L/14@336px', vk, 24, num_frames, timesformer_gated_xattn,
                                                drop_path_rate, timesformer_freeze_space, temperature_init,
                                                project_embed_dim, kwargs)
+
+
+def load_pretrained_vit(name):
+    """The reference builds timm's ImageNet ViT with pretrained=True here (`timm.models.vision_transformer.
+    vit_base_patch16_224`, models.py:698) and loads its state dict into the TimeSformer with strict=False. Offline:
+    LAVILA_VIT_WEIGHTS_DIR/<name>.pt holding timm's state_dict, else the tower keeps its seeded initialisation."""
+    root = os.environ.get('LAVILA_VIT_WEIGHTS_DIR')
+    if not root:
+        import warnings
+        warnings.warn(f'lavila_amd: pretrained {name} weights are NOT loaded (no network; set LAVILA_VIT_WEIGHTS_DIR): the '
+                      'video tower keeps its seeded initialisation, unlike the reference constructor', stacklevel=3)
+        return None
+    path = os.path.join(root, name + '.pt')
+    if not os.path.isfile(path):
+        raise RuntimeError(f'ViT checkpoint {name} not found at {path}')
+    return torch.load(path, map_location='cpu', weights_only=True)
+
+
+def CLIP_HF_TIMESFORMER_DISTILBERT_BASE(num_frames=4, drop_path_rate=0, temperature_init=0.07, project_embed_dim=256,
+                                        **kwargs):
+    """models.py:691-720: the default-constructed SpaceTimeTransformer (the Frozen-in-Time / ImageNet-ViT tower: exact GELU,
+    no ln_pre and so a patch-embedding bias, LayerNorm eps 1e-6) from timm's vit_base_patch16_224 + DistilBERT, default
+    projection. The tower's MLPs run on the fused chain's exact-GELU GEMM epilogues (ops.mlp, ops.ACT_GELU).
+    `text_use_cls_token` must be among the kwargs, as in the reference (it is popped and ignored)."""
+    vision_model = SpaceTimeTransformer(num_frames=num_frames, time_init='zeros', attention_style='frozen-in-time',
+                                        drop_path_rate=drop_path_rate)
+    vit_sd = load_pretrained_vit('vit_base_patch16_224')
+    if vit_sd is not None:
+        vision_model.load_state_dict(vit_sd, strict=False)
+    vision_model.head = nn.Identity()
+    vision_model.pre_logits = nn.Identity()
+    vision_model.fc = nn.Identity()
+    text_model = DistilBertModel(distilbert_config('distilbert-base-uncased'))
+    sd = load_pretrained_distilbert('distilbert-base-uncased')
+    if sd is not None:
+        text_model.load_state_dict(sd, strict=True)
+    kwargs.pop('text_use_cls_token')  # ignore args.use_cls_token since DistilBert does not have pooler on top
+    return CLIP_HF(embed_dim=project_embed_dim, vision_width=vision_model.embed_dim, vision_model=vision_model,
+                   text_width=768, text_model=text_model, text_use_cls_token=True, text_is_regressive=False,
+                   tempearture_init=temperature_init, **kwargs)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -417,27 +417,53 @@ class _LinearFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+# The activations of the fused MLP: the epilogues of lvl_linear_tn that apply them (keeping u / keeping act'(u) / the backward
+# on a kept u) and the kernel that rebuilds the hidden activation from a kept u (selective recompute). The bf16 backward on a
+# kept DERIVATIVE is LVL_EPI_MUL_AUX_COLSUM for both.
+ACT_QUICKGELU, ACT_GELU = 'quickgelu', 'gelu'
+_MLP_EPILOGUES = {ACT_QUICKGELU: (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV, C.EPI_QUICKGELU_BWD),
+                  ACT_GELU: (C.EPI_BIAS_GELU, C.EPI_BIAS_GELU_DERIV, C.EPI_GELU_BWD)}
+
+
+def _mlp_epilogues(act):
+    if act not in _MLP_EPILOGUES:
+        raise ValueError(f'act={act!r}: the fused MLP takes {ACT_QUICKGELU!r} (x * sigmoid(1.702 x)) or {ACT_GELU!r} (the exact '
+                         'erf GELU, nn.GELU())')
+    return _MLP_EPILOGUES[act]
+
+
+def gelu_apply_raw(u):
+    """a = GELU(u) (exact, erf) with the arithmetic of linear_tn_raw's EPI_BIAS_GELU epilogue (lvl_act_fwd,
+    LVL_ACT_GELU_ERF): rebuilds the hidden activation from the kept pre-activation to the bit."""
+    C.require_device(u)
+    a = torch.empty_like(u)
+    C.check(C.lib().lvl_act_fwd(C.ptr(u), C.ptr(a), u.numel(), C.ACT_GELU_ERF, C.dtype_code(u), C.stream_ptr()), 'lvl_act_fwd')
+    return a
+
+
 class _MlpFn(torch.autograd.Function):
-    """y = fc2(QuickGELU(fc1(x) + b1)) without fc2's bias (the caller leaves it pending for the next fused
+    """y = fc2(act(fc1(x) + b1)), act = QuickGELU or the exact GELU (`act`), without fc2's bias (the caller leaves it pending for the next fused
     residual + LayerNorm): timesformer.py:52-58 / openai_model.py:189-192. Two lvl_linear_tn calls forward (the
     first one adds the bias, applies the activation and keeps what the backward needs), and in backward the QuickGELU
     derivative and the fc1 bias gradient are the epilogue of fc2's input-gradient GEMM: the [rows, 4D] tensors are
     touched by GEMM epilogues only. What is kept: bf16 keeps quickgelu'(u) itself -- the forward epilogue has
     sigmoid(1.702 u) in a register, the backward epilogue then is one multiply (LVL_EPI_BIAS_QUICKGELU_DERIV /
     LVL_EPI_MUL_AUX_COLSUM); the f32-class mode keeps the pre-activation u (LVL_EPI_BIAS_QUICKGELU /
-    LVL_EPI_QUICKGELU_BWD)."""
+    LVL_EPI_QUICKGELU_BWD). The exact GELU runs the same way on its own epilogues (LVL_EPI_BIAS_GELU_DERIV, whose one erf
+    serves gelu(u) and gelu'(u), then LVL_EPI_MUL_AUX_COLSUM; LVL_EPI_BIAS_GELU / LVL_EPI_GELU_BWD where u is kept)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, ln=None):
+    def forward(ctx, x, w1, b1, w2, ln=None, act=ACT_QUICKGELU):
         x2 = x.reshape(-1, x.shape[-1])
         if not x2.is_contiguous():
             x2 = x2.contiguous()
         f32 = ctx.f32 = x.dtype == torch.float32        # f32-class mode: term images in, float32 u / a / y
         sel = ctx.sel = ln is not None                  # selective recompute: keep u, neither x (a LayerNorm output) nor a
+        ctx.act = act
+        keep_u, keep_deriv, _ = _mlp_epilogues(act)
         w1b, w1t = weight_copies(w1, f32)
         w2b, w2t = weight_copies(w2, f32)
-        a, u = linear_tn_raw(split3(x2, 0) if f32 else x2, w1b, _f32(b1),
-                             C.EPI_BIAS_QUICKGELU if (f32 or sel) else C.EPI_BIAS_QUICKGELU_DERIV, f32=f32)
+        a, u = linear_tn_raw(split3(x2, 0) if f32 else x2, w1b, _f32(b1), keep_u if (f32 or sel) else keep_deriv, f32=f32)
         y = linear_tn_raw(split3(a, 0) if f32 else a, w2b, None, C.EPI_BIAS, f32=f32)
         if sel:
             ctx.save_for_backward(*ln.saved(), u, w1t, w2t)
@@ -460,28 +486,29 @@ class _MlpFn(torch.autograd.Function):
         if ctx.f32:
             dy2 = dy2.float()
         dx, dw1, db1, dw2 = _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept if ctx.sel else None)
-        return dx, dw1, db1, dw2, None
+        return dx, dw1, db1, dw2, None, None
 
 
 def _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept, need=(0, 1, 2, 3)):
-    """The backward of fc2(QuickGELU(fc1(x) + b1)) shared by _MlpFn and _MlpResidualLayerNormFn: (dx, dw1, db1, dw2) for
+    """The backward of fc2(act(fc1(x) + b1)) (ctx.act) shared by _MlpFn and _MlpResidualLayerNormFn: (dx, dw1, db1, dw2) for
     the gradient dy2 [rows, D] of fc2's output. need: positions of x, w1, b1, w2 among the Function's inputs.
-    Plain: x2 and a were kept; u is quickgelu'(u) in bf16 (one multiply in the epilogue) and the pre-activation in f32.
-    Selective (ctx.sel): u is the pre-activation in both; a = QuickGELU(u) and then x = the LayerNorm output of the recipe
+    Plain: x2 and a were kept; u is act'(u) in bf16 (one multiply in the epilogue) and the pre-activation in f32.
+    Selective (ctx.sel): u is the pre-activation in both; a = act(u) and then x = the LayerNorm output of the recipe
     `kept` are rebuilt one after the other, each right before the weight-gradient GEMM that reads it and only if that
     gradient is wanted, so that at most one [rows, 4D] and one [rows, D] rebuilt tensor are alive at a time."""
     w1dt, b1dt, w2dt, xshape = ctx.meta[0], ctx.meta[1], ctx.meta[2], ctx.meta[-1]
     f32, sel = ctx.f32, ctx.sel
     gx, gw1, gb1, gw2 = (ctx.needs_input_grad[i] for i in need)
     wgrad = _wgrad_f32 if f32 else _wgrad
+    bwd_on_u = _mlp_epilogues(ctx.act)[2]
     if f32:
-        du, db1 = linear_tn_raw(split3(dy2, 0), w2t, None, C.EPI_QUICKGELU_BWD, aux_in=u, f32=True)
+        du, db1 = linear_tn_raw(split3(dy2, 0), w2t, None, bwd_on_u, aux_in=u, f32=True)
     else:
-        du, db1 = linear_tn_raw(dy2, w2t, None, C.EPI_QUICKGELU_BWD if sel else C.EPI_MUL_AUX_COLSUM, aux_in=u)
+        du, db1 = linear_tn_raw(dy2, w2t, None, bwd_on_u if sel else C.EPI_MUL_AUX_COLSUM, aux_in=u)
     dw2 = None
     if gw2:
         if sel:
-            a = quickgelu_apply_raw(u)
+            a = quickgelu_apply_raw(u) if ctx.act == ACT_QUICKGELU else gelu_apply_raw(u)
         dw2 = wgrad(dy2, a, w2dt)
     del a, u
     if f32:
@@ -496,22 +523,41 @@ def _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept, need=(0, 1, 2, 3)):
     return dx, dw1, (db1.to(b1dt) if (b1dt is not None and gb1) else None), dw2
 
 
+def _mlp_fused_ok(x, w1, b1, w2):
+    """Whether _MlpFn takes the MLP: bf16 on the benched kernels, or float32 on their f32-class mode."""
+    rows = x.numel() // x.shape[-1]
+    if (x.dtype == torch.bfloat16 and x.is_cuda and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1])
+            and _tn_ok(rows, w1.shape[1], w1.shape[0]) and _tn_ok(rows, w2.shape[0], w2.shape[1])
+            and _tn_ok(rows, w2.shape[1], w2.shape[0])):
+        return True
+    return (x.dtype == torch.float32 and x.is_cuda and b1 is not None and w1.dtype == torch.float32
+            and _tn_ok_f32(rows, w1.shape[0], w1.shape[1]) and _tn_ok_f32(rows, w1.shape[1], w1.shape[0])
+            and _tn_ok_f32(rows, w2.shape[0], w2.shape[1]) and _tn_ok_f32(rows, w2.shape[1], w2.shape[0]))
+
+
 def mlp_quickgelu(x, w1, b1, w2, ln=None):
     """fc2(QuickGELU(fc1(x))) minus fc2's bias; fused GEMM epilogues in bf16, composed kernels otherwise.
     ln: the LnRecipe of x (selective activation recompute: neither x nor the hidden activation is kept by the fused
     function; the composed form keeps the hidden activation and rebuilds x only)."""
     x = _act(x)
     ln = _ln_for(ln, x)
-    rows = x.numel() // x.shape[-1]
-    if (x.dtype == torch.bfloat16 and x.is_cuda and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1])
-            and _tn_ok(rows, w1.shape[1], w1.shape[0]) and _tn_ok(rows, w2.shape[0], w2.shape[1])
-            and _tn_ok(rows, w2.shape[1], w2.shape[0])):
-        return _MlpFn.apply(x, w1, b1, w2, ln)
-    if (x.dtype == torch.float32 and x.is_cuda and b1 is not None and w1.dtype == torch.float32
-            and _tn_ok_f32(rows, w1.shape[0], w1.shape[1]) and _tn_ok_f32(rows, w1.shape[1], w1.shape[0])
-            and _tn_ok_f32(rows, w2.shape[0], w2.shape[1]) and _tn_ok_f32(rows, w2.shape[1], w2.shape[0])):
-        return _MlpFn.apply(x, w1, b1, w2, ln)      # the same fused epilogues in f32-class mode
+    if _mlp_fused_ok(x, w1, b1, w2):
+        return _MlpFn.apply(x, w1, b1, w2, ln, ACT_QUICKGELU)      # bf16, or the same fused epilogues in f32-class mode
     return linear(bias_quick_gelu(linear(x, w1, ln=ln), b1), w2)
+
+
+def mlp(x, w1, b1, w2, act, ln=None):
+    """fc2(act(fc1(x))) minus fc2's bias for act = ACT_QUICKGELU (mlp_quickgelu) or ACT_GELU, the exact erf GELU of nn.GELU():
+    the same fused GEMM epilogues (bf16 and f32-class), and where the fused form does not take the shapes or dtypes, the
+    composed form: Linear + bias, the activation as a torch op, Linear. ln: as in mlp_quickgelu."""
+    _mlp_epilogues(act)
+    if act == ACT_QUICKGELU:
+        return mlp_quickgelu(x, w1, b1, w2, ln=ln)
+    x = _act(x)
+    ln = _ln_for(ln, x)
+    if _mlp_fused_ok(x, w1, b1, w2):
+        return _MlpFn.apply(x, w1, b1, w2, ln, ACT_GELU)
+    return linear(torch.nn.functional.gelu(linear(x, w1, b1, ln=ln)), w2)
 
 
 def linear_wgrad_raw(dy, x, want_dbias: bool, ws_floats: int = -1):
@@ -567,27 +613,31 @@ def sched_block(device, words=16):
     return pool[0][pool[1]]
 
 
+_TN_TWO_OUT = (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV, C.EPI_BIAS_GELU, C.EPI_BIAS_GELU_DERIV)      # write aux_out
+_TN_COLSUM = (C.EPI_QUICKGELU_BWD, C.EPI_MUL_AUX_COLSUM, C.EPI_GELU_BWD)      # read aux_in, leave column sums
+
+
 def linear_tn_raw(x, w, bias=None, epilogue=C.EPI_BIAS, aux_in=None, f32=False):
     """One lvl_linear_tn call on bf16 tensors: y[M,N] = epilogue(x[M,K] . w[N,K]^T).
-    Returns y (EPI_BIAS; EPI_BIAS_RESIDUAL: + aux_in [M,N]), (y, u) (EPI_BIAS_QUICKGELU), (y, quickgelu'(u))
-    (EPI_BIAS_QUICKGELU_DERIV) or (y, colsum) (EPI_QUICKGELU_BWD, EPI_MUL_AUX_COLSUM).
+    Returns y (EPI_BIAS; EPI_BIAS_RESIDUAL: + aux_in [M,N]), (y, u) (EPI_BIAS_QUICKGELU, EPI_BIAS_GELU), (y, act'(u))
+    (EPI_BIAS_QUICKGELU_DERIV, EPI_BIAS_GELU_DERIV) or (y, colsum) (EPI_QUICKGELU_BWD, EPI_GELU_BWD, EPI_MUL_AUX_COLSUM).
     f32=True: the kernel's f32-class mode -- x, w are bf16 term images (split3), y / u / aux_in float32."""
     C.require_device(x, w, bias, aux_in)
     M, K = x.shape
     N = w.shape[0]
     y = torch.empty(M, N, dtype=torch.float32 if f32 else torch.bfloat16, device=x.device)
     aux_out = colsum = ws = None
-    if epilogue in (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV):
+    if epilogue in _TN_TWO_OUT:
         aux_out = torch.empty_like(y)
-    elif epilogue in (C.EPI_QUICKGELU_BWD, C.EPI_MUL_AUX_COLSUM):
+    elif epilogue in _TN_COLSUM:
         colsum = torch.empty(N, dtype=torch.float32, device=x.device)
         ws = C.workspace('linear_tn', M, N, x.device)
     C.check(C.lib().lvl_linear_tn(C.ptr(x), C.ptr(w), C.ptr(bias), C.ptr(y), C.ptr(aux_out), C.ptr(aux_in),
                                   C.ptr(colsum), C.ptr(ws), C.ptr(sched_block(x.device)), M, N, K, epilogue,
                                   C.LVL_F32 if f32 else C.LVL_BF16, C.stream_ptr()), 'lvl_linear_tn')
-    if epilogue in (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV):
+    if epilogue in _TN_TWO_OUT:
         return y, aux_out
-    if epilogue in (C.EPI_QUICKGELU_BWD, C.EPI_MUL_AUX_COLSUM):
+    if epilogue in _TN_COLSUM:
         return y, colsum
     return y
 
@@ -1037,13 +1087,13 @@ def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=N
 
 
 class _MlpResidualLayerNormFn(torch.autograd.Function):
-    """(s, h) = (res + fc2(QuickGELU(fc1(x) + b1)) + b2, LayerNorm(s)): `x = x + mlp(norm2(x))` of one block and the first
+    """(s, h) = (res + fc2(act(fc1(x) + b1)) + b2, LayerNorm(s)): `x = x + mlp(norm2(x))` of one block and the first
     LayerNorm of the NEXT consumer (timesformer.py:196 / 183; openai_model.py:200 / 199) -- _MlpFn with the residual
     epilogue on its second GEMM, then one plain LayerNorm pass. Backward = LayerNorm backward (adds the stream's own
     gradient, leaves ds and its column sums = d b2), then _MlpFn's backward on ds."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, rec=None):
+    def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, rec=None, act=ACT_QUICKGELU):
         x2 = x.reshape(-1, x.shape[-1])
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         res2 = res.reshape(-1, res.shape[-1])
@@ -1052,7 +1102,9 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
         sel = ctx.sel = ln is not None       # selective recompute, as in _MlpFn: keep u, neither x nor a
         w1b, w1t = weight_copies(w1)
         w2b, w2t = weight_copies(w2)
-        a, u = linear_tn_raw(x2, w1b, _f32(b1), C.EPI_BIAS_QUICKGELU if sel else C.EPI_BIAS_QUICKGELU_DERIV)
+        ctx.act = act
+        keep_u, keep_deriv, _ = _mlp_epilogues(act)
+        a, u = linear_tn_raw(x2, w1b, _f32(b1), keep_u if sel else keep_deriv)
         s = linear_tn_raw(a, w2b, _f32(b2), C.EPI_BIAS_RESIDUAL, aux_in=res2)
         g, b = _f32(gamma), _f32(beta)
         h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
@@ -1081,13 +1133,14 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
         with torch.autocast('cuda', enabled=False):
             dx, dw1, db1, dw2 = _mlp_backward(ctx, dsum, x2, u, a, w1t, w2t, kept)
         return (dx, dw1, db1, dw2, dcol.to(b2dt) if (b2dt is not None and ctx.needs_input_grad[4]) else None,
-                dsum.reshape(dh.shape), dg.to(gdt), dbeta.to(betadt), None, None, None)
+                dsum.reshape(dh.shape), dg.to(gdt), dbeta.to(betadt), None, None, None, None)
 
 
-def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, recipe=False):
+def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, recipe=False, act=ACT_QUICKGELU):
     """(s, h) = (res + Mlp(x), LayerNorm(s)) with the residual add in fc2's GEMM epilogue, or None when the configuration
-    is not the benched bf16 one (the caller then composes mlp_quickgelu + add_layer_norm). ln: the LnRecipe of x (see
-    mlp_quickgelu); recipe: see layer_norm."""
+    is not the benched bf16 one (the caller then composes mlp + add_layer_norm). ln: the LnRecipe of x (see
+    mlp_quickgelu); recipe: see layer_norm; act: ACT_QUICKGELU or ACT_GELU (see mlp)."""
+    _mlp_epilogues(act)
     x, res = _act(x), lowp(res)
     rows = x.numel() // x.shape[-1]
     if not (RESIDUAL_EPILOGUE and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and x.is_cuda
@@ -1095,7 +1148,7 @@ def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, r
             and _tn_ok(rows, w2.shape[0], w2.shape[1]) and _tn_ok(rows, w2.shape[1], w2.shape[0])):
         return None
     rec = LnRecipe() if recipe else None
-    s, h = _MlpResidualLayerNormFn.apply(x, w1, b1, w2, b2, res, gamma, beta, eps, _ln_for(ln, x), rec)
+    s, h = _MlpResidualLayerNormFn.apply(x, w1, b1, w2, b2, res, gamma, beta, eps, _ln_for(ln, x), rec, act)
     return (s, _narrow(h), rec) if recipe else (s, _narrow(h))
 
 

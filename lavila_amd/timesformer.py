@@ -94,9 +94,22 @@ class QuickGELUAct(nn.Module):
         return ops.bias_quick_gelu(x, None)
 
 
+def classify_act(act):
+    """The activation of an Mlp as the fused MLP kernels know it: ops.ACT_QUICKGELU (QuickGELU: every CLIP_OPENAI_* tower),
+    ops.ACT_GELU (nn.GELU with approximate='none', the exact erf GELU: the default of SpaceTimeTransformer, the ImageNet-ViT
+    tower of CLIP_HF_TIMESFORMER_DISTILBERT_BASE) or None (anything else -- the tanh approximation included: it runs as the
+    module it is, between two Linear kernels)."""
+    if type(act).__name__ in ('QuickGELU', 'QuickGELUAct'):
+        return ops.ACT_QUICKGELU
+    if isinstance(act, nn.GELU) and getattr(act, 'approximate', 'none') == 'none':
+        return ops.ACT_GELU
+    return None
+
+
 class Mlp(nn.Module):
     """fc2(act(fc1(x))) -- timesformer.py:42-58. With QuickGELU (all CLIP_OPENAI_* models) the fc1 bias add
-    and the activation run as one HIP kernel on the raw GEMM output."""
+    and the activation run as one HIP kernel on the raw GEMM output; on the block chain QuickGELU and the exact GELU both
+    live in the GEMM epilogues (`act_kind`, ops.mlp)."""
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
@@ -106,7 +119,8 @@ class Mlp(nn.Module):
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
         self.drop = nn.Dropout(drop)
-        self._fused_act = type(self.act).__name__ in ('QuickGELU', 'QuickGELUAct')
+        self.act_kind = classify_act(self.act)          # classified once: ops.ACT_QUICKGELU, ops.ACT_GELU or None (unfused)
+        self._fused_act = self.act_kind == ops.ACT_QUICKGELU
 
     def hidden(self, x):
         if self._fused_act:
@@ -246,7 +260,7 @@ class PendingMlp:
     def materialize(self):
         """The MLP branch as a tensor (fc2's bias still pending), for consumers that want the composed form."""
         m = self.mlp
-        return ops.mlp_quickgelu(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, ln=self.ln)
+        return ops.mlp(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.act_kind, ln=self.ln)
 
 
 class ScaledBranch:
@@ -274,7 +288,7 @@ def _close_pending(res, pend, pend_bias, norm, selective=False):
     if isinstance(pend, PendingMlp):
         m = pend.mlp
         fused = ops.mlp_residual_layer_norm(pend.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, pend_bias, res, norm.weight,
-                                            norm.bias, norm.eps, ln=pend.ln, recipe=selective)
+                                            norm.bias, norm.eps, ln=pend.ln, recipe=selective, act=m.act_kind)
         if fused is not None:
             return fused
         pend = pend.materialize()
@@ -326,8 +340,8 @@ class SpaceTimeBlock(nn.Module):
 
     def _mlp_branch(self, h2):
         """fc2(act(fc1(h2))) without fc2's bias, which stays pending."""
-        if self.mlp._fused_act:
-            return ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight)
+        if self.mlp.act_kind is not None:
+            return ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind)
         return ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight)
 
     def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False, selective=False):
@@ -400,10 +414,10 @@ class SpaceTimeBlock(nn.Module):
         r2 = r2[0] if r2 else None
         if self._dropping():
             return x1, self.drop_path(self.mlp(h2)), None
-        if self.mlp._fused_act:
+        if self.mlp.act_kind is not None:
             if defer_mlp and ops.RESIDUAL_EPILOGUE and h2.dtype == torch.bfloat16 and x1.dtype == torch.bfloat16:
                 return x1, PendingMlp(h2, self.mlp, r2), self.mlp.fc2.bias      # enqueued by the next consumer (_close_pending)
-            return (x1, ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, ln=r2),
+            return (x1, ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind, ln=r2),
                     self.mlp.fc2.bias)
         return x1, ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight), self.mlp.fc2.bias
 
@@ -447,8 +461,9 @@ class SpaceTimeBlock(nn.Module):
             x1, h2 = ops.scaled_add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, c_s, 1, n2.weight, n2.bias, n2.eps)
             return x1, ScaledBranch(self._mlp_branch(h2), c_m), self.mlp.fc2.bias
         x1, h2 = ops.add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, n2.weight, n2.bias, n2.eps, keep_sum=True)
-        if self.mlp._fused_act:
-            return x1, ops.mlp_quickgelu(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight), self.mlp.fc2.bias
+        if self.mlp.act_kind is not None:
+            return (x1, ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind),
+                    self.mlp.fc2.bias)
         return x1, ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight), self.mlp.fc2.bias
 
     def forward(self, x, einops_from_space, einops_to_space, einops_from_time, einops_to_time,

@@ -41,3 +41,9 @@ int lvl_launch_column_reduce(const float*, int, int, int, float*, float*, float*
 int lvl_launch_tn_edge(const void*, const void*, const float*, void*, int64_t, int, int, int, hipStream_t) {
   return lvl_fail(-38, "linear_tn_ragged: the edge kernel is not linked into this debug build");
 }
+// lvl_linear_tn's exact-GELU epilogues live in gemm_tn_gelu.hip; a debug build of gemm_tn_mfma.hip alone refuses them, a debug
+// build of gemm_tn_gelu.hip brings its own definition (hence weak)
+__attribute__((weak)) int lvl_launch_tn_gelu(const void*, const void*, const float*, void*, void*, const void*, float*, int64_t,
+                                             int, int, uint32_t*, int, int, hipStream_t) {
+  return lvl_fail(-38, "linear_tn: the exact-GELU kernels are not linked into this debug build");
+}
