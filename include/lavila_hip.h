@@ -200,7 +200,9 @@ int lvl_embed_tokens_bwd(const void* dx, float* dpos, float* dtem, float* ws, in
  * unused ids zero) and d pos [ctx, W] f32
  * (row l = sum over the batch, rows >= L zero) -- without a sort, without float atomics and without memset nodes (torch's
  * embedding_dense_backward sorts with rocPRIM above 3072 rows, whose histogram memsets become unreliable memset NODES in a
- * replayed hipGraph). ws: lvl_text_embed_bwd_ws(B, L, V) int32 words. W <= 2048. */
+ * replayed hipGraph). ws: lvl_text_embed_bwd_ws(B, L, V) int32 words. W <= 2048.
+ * dtable or dpos may be NULL (a frozen parameter): a NULL dtable skips the [V, W] zero-fill, the census and the table
+ * kernel (ws is then unused and may be NULL too), a NULL dpos skips the positional kernel; both NULL is LVL_EINVAL. */
 int lvl_text_embed_fwd(const int64_t* tokens, int64_t tok_stride, const float* table, const float* pos, void* x, int B,
                        int L, int W, int V, int dtype, void* stream);
 int64_t lvl_text_embed_bwd_ws(int B, int L, int V);

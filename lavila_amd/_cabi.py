@@ -84,6 +84,7 @@ SIGNATURES = {
     'lvl_embed_tokens_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_text_embed_fwd': (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'lvl_text_embed_bwd_ws': (_L, [_I, _I, _I]),
+    # (dx, tokens, tok_stride, dtable | NULL, dpos | NULL, ws (NULL allowed with a NULL dtable), B, L, W, V, ctx, dtype, stream)
     'lvl_text_embed_bwd': (_I, [_P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_debug_time_bwd_rider': (_I, [_I]),
     'lvl_linear_skinny': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -203,25 +203,31 @@ extern "C" int64_t lvl_text_embed_bwd_ws(int B, int L, int V) { return (int64_t)
 
 extern "C" int lvl_text_embed_bwd(const void* dx, const int64_t* tokens, int64_t tok_stride, float* dtable, float* dpos,
                                   int* ws, int B, int L, int W, int V, int ctx, int dtype, void* stream) {
-  LVL_REQUIRE(dx && tokens && dtable && dpos && ws, "text_embed_bwd: null pointer");
+  // dtable or dpos may be null (a frozen parameter): its kernels are not launched; ws is only needed for dtable
+  LVL_REQUIRE(dx && tokens && (dtable || dpos) && (ws || !dtable), "text_embed_bwd: null pointer");
   LVL_REQUIRE(B > 0 && L > 0 && V > 0 && W > 0 && W % 8 == 0 && W <= 2048 && ctx >= L && tok_stride >= L,
               "text_embed_bwd: bad shape B=%d L=%d W=%d V=%d ctx=%d", B, L, W, V, ctx);
   LVL_REQUIRE((int64_t)B * L < (1ll << 31), "text_embed_bwd: too many token rows");
   LVL_REQUIRE(lvl_aligned16(dtable) && lvl_aligned16(dpos) && lvl_aligned16(dx),
               "text_embed_bwd: dtable / dpos / dx must be 16-byte aligned");
+  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "text_embed_bwd: unknown dtype %d", dtype);   // before any launch
   hipStream_t st = (hipStream_t)stream;
   const int R = B * L;
-  int* tok32 = ws;
-  int* first = ws + R;
-  int* count = first + V;
-  if (int rc = lvl_zero_f32(dtable, (size_t)V * W, st)) return rc;
-  hipLaunchKernelGGL(text_embed_init_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, first, count, V);
-  hipLaunchKernelGGL(text_embed_census_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, tokens, tok_stride, tok32,
-                     first, count, R, L, V);
-  LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((text_embed_bwd_table_kernel<T>), dim3((unsigned)R), dim3(kTabWaves * 64), 0, st,
-                                               (const T*)dx, tok32, first, count, dtable, R, W));
-  LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((text_embed_bwd_pos_kernel<T>), dim3((unsigned)ctx), dim3(512), 0, st,
-                                               (const T*)dx, dpos, B, L, W));
+  if (dtable) {
+    int* tok32 = ws;
+    int* first = ws + R;
+    int* count = first + V;
+    if (int rc = lvl_zero_f32(dtable, (size_t)V * W, st)) return rc;
+    hipLaunchKernelGGL(text_embed_init_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, first, count, V);
+    hipLaunchKernelGGL(text_embed_census_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, tokens, tok_stride,
+                       tok32, first, count, R, L, V);
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((text_embed_bwd_table_kernel<T>), dim3((unsigned)R), dim3(kTabWaves * 64), 0,
+                                                 st, (const T*)dx, tok32, first, count, dtable, R, W));
+  }
+  if (dpos) {
+    LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((text_embed_bwd_pos_kernel<T>), dim3((unsigned)ctx), dim3(512), 0, st,
+                                                 (const T*)dx, dpos, B, L, W));
+  }
   LVL_CHECK_LAUNCH("text_embed_bwd");
   return LVL_OK;
 }

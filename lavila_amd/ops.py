@@ -1403,36 +1403,52 @@ class _TextEmbedFn(torch.autograd.Function):
         tab, p = _f32(table), _f32(pos)
         C.require_device(tab, p)
         x = torch.empty(B, L, W, dtype=out_dtype, device=table.device)
-        C.check(C.lib().lvl_text_embed_fwd(C.ptr(text), text.stride(0), C.ptr(tab), C.ptr(p), C.ptr(x), B, L, W, V,
+        C.check(C.lib().lvl_text_embed_fwd(C.ptr(text), _token_stride(text), C.ptr(tab), C.ptr(p), C.ptr(x), B, L, W, V,
                                            C.dtype_code(x), C.stream_ptr()), 'lvl_text_embed_fwd')
-        ctx.text = text                       # an index tensor (no gradient, not an output): kept as a plain attribute
+        ctx.save_for_backward(text)           # saved, not a plain attribute: an in-place write before backward then raises
         ctx.meta = (V, W, pos.shape[0], table.dtype, pos.dtype)
         return x
 
     @staticmethod
     def backward(ctx, dx):
-        text = ctx.text
+        text, = ctx.saved_tensors
         B, L = text.shape
         V, W, ctx_len, tdt, pdt = ctx.meta
+        want_table, want_pos = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_table or want_pos):
+            return None, None, None, None
         dx = dx.contiguous()
-        dtable = torch.empty(V, W, dtype=torch.float32, device=dx.device)
-        dpos = torch.empty(ctx_len, W, dtype=torch.float32, device=dx.device)
-        ws = torch.empty(int(C.lib().lvl_text_embed_bwd_ws(B, L, V)), dtype=torch.int32, device=dx.device)
-        C.check(C.lib().lvl_text_embed_bwd(C.ptr(dx), C.ptr(text), text.stride(0), C.ptr(dtable), C.ptr(dpos), C.ptr(ws),
-                                           B, L, W, V, ctx_len, C.dtype_code(dx), C.stream_ptr()), 'lvl_text_embed_bwd')
-        return None, dtable.to(tdt), dpos.to(pdt), None
+        # a frozen table (or frozen positions) gets a null pointer: no dense [V, W] zero-fill and build for nothing
+        dtable = torch.empty(V, W, dtype=torch.float32, device=dx.device) if want_table else None
+        dpos = torch.empty(ctx_len, W, dtype=torch.float32, device=dx.device) if want_pos else None
+        ws = (torch.empty(int(C.lib().lvl_text_embed_bwd_ws(B, L, V)), dtype=torch.int32, device=dx.device)
+              if want_table else None)
+        C.check(C.lib().lvl_text_embed_bwd(C.ptr(dx), C.ptr(text), _token_stride(text), C.ptr(dtable), C.ptr(dpos),
+                                           C.ptr(ws), B, L, W, V, ctx_len, C.dtype_code(dx), C.stream_ptr()),
+                'lvl_text_embed_bwd')
+        return (None, dtable.to(tdt) if want_table else None, dpos.to(pdt) if want_pos else None, None)
+
+
+def _token_stride(text):
+    """Row stride of a [B, L] token view for the kernels. torch leaves the stride of a size-1 dimension arbitrary (`col.t()`
+    of an [L, 1] tensor reports (1, 1)); with one row it is never used, so L is passed."""
+    return text.shape[1] if text.shape[0] == 1 else text.stride(0)
 
 
 def text_embed(text, table, pos, out_dtype):
-    """CLIP.encode_text's first two lines on the own kernels when they apply (a device int64 [B, L] view whose rows are
-    contiguous, float32 table / positions of a width that is a multiple of 8 and at most 2048); None otherwise (the caller
-    keeps nn.Embedding)."""
+    """CLIP.encode_text's first two lines on the own kernels when they apply (device int64 [B, L] tokens with unit inner
+    stride on the table's device, float32 table / positions of a width that is a multiple of 8 and at most 2048); None
+    otherwise (the caller keeps nn.Embedding). Never raises on tokens nn.Embedding accepts: a `text[:, :L]` view is read in
+    place through its row stride, a single row is read with stride L whatever torch reports for it, and a batch whose rows
+    overlap (row stride below L: `ids.expand(B, L)`) is read from a contiguous copy."""
     if not (text.is_cuda and text.dtype == torch.int64 and text.dim() == 2 and text.stride(1) == 1
-            and text.shape[0] > 0 and text.shape[1] > 0
+            and text.shape[0] > 0 and text.shape[1] > 0 and text.device == table.device and pos.device == table.device
             and table.dtype == torch.float32 and pos.dtype == torch.float32 and table.is_contiguous()
             and pos.is_contiguous() and table.shape[1] % 8 == 0 and table.shape[1] <= 2048
             and pos.shape[0] >= text.shape[1] and out_dtype in (torch.float32, torch.bfloat16)):
         return None
+    if text.shape[0] > 1 and text.stride(0) < text.shape[1]:
+        text = text.contiguous()
     return _TextEmbedFn.apply(text, table, pos, out_dtype)
 
 
