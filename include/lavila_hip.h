@@ -556,6 +556,51 @@ int lvl_keymask_attn_bwd(const void* q, const void* k, const void* v, const uint
                          void* dk, void* dv, float* ws, int contexts, int qrep, int Tk, int H, int64_t q_stride,
                          int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, int dtype, void* stream);
 
+/* ---- dropout of the DistilBERT text tower (opt-in, distilbert.TEXT_DROPOUT) -------------------------------------------
+ * transformers' modeling_distilbert.py calls dropout 1 + 2 n_layers times per forward: on the embedding behind
+ * embeddings.LayerNorm [B, L, D]; per layer on the attention probabilities behind the masked softmax [B, H, L, L]
+ * (attention_dropout) and on the output of ffn.lin2 with its bias, before + sa_output and output_layer_norm [B, L, D]
+ * (dropout). Nothing is dropped behind out_lin.
+ * THE MASK CONTRACT. The generator is the decoder's (csrc/dropout.h, above): same Philox, threshold and float32 scale.
+ *   Sites: 0 = the embedding; layer n: 1 + 2 n = attention probabilities, 2 + 2 n = FFN output.
+ *   Row sites over [B, L, D]: e = (b * L + i) * D + c, L = the positions the tower runs on (after the trim).
+ *   Attention sites: e = ((((b * H + h) * L + i) << s) | j for query position i and key j; s = 8 for Tk <= 256 (the decoder's
+ *   mapping), else the smallest s with 2^s >= Tk (9 for DistilBERT's 512 positions).
+ *   A call that computes a SUBSET of the rows addresses the elements of the full call: the row entry points take
+ *   row_index_stride (row r of the call has e = r * row_index_stride + c: D for all rows, L * D for row 0 of every sample),
+ *   the attention entry points take idx_qrep (query i of context b is row b * idx_qrep + i of the index: L when qrep == 1).
+ *   P is the softmax over the visible keys exactly as in lvl_keymask_attn_fwd, the row sum runs over ALL visible keys;
+ *   Pd = keep ? scale * P : 0 (rounded to bf16 where P is), O = Pd V. A hidden key keeps P = dS = 0 and exact-zero dk / dv
+ *   rows; a context with no visible key gets the uniform distribution and THEN dropout. Backward: dP = keep ? scale *
+ *   (dO V^T) : 0, delta = sum_j P dP (= dO . O), dS = P o (dP - delta), dV = Pd^T dO.
+ * lvl_keymask_attn_drop_fwd / _bwd: the operands of lvl_keymask_attn_fwd / _bwd plus idx_qrep (>= qrep), seed, site, p in
+ *   [0, 1). p == 0 runs lvl_keymask_attn_fwd / _bwd (same kernels, same bits). bf16 with Tk <= 256: the <DROP, KEYMASK>
+ *   instantiations of the MFMA rows attention; float32, and bf16 with Tk > 256: the shape-generic kernels, whose (m, l) and
+ *   (lse, delta) are those of the undropped softmax and whose backward passes regenerate keep from the index. One Philox
+ *   call serves four consecutive keys. Same workspace as lvl_keymask_attn_bwd, every addressed element written on every
+ *   call, no atomics, bit-reproducible.
+ * lvl_dropout_add_layernorm_fwd / _bwd: the FFN site. s = round(fma(keep ? scale : 0, y, res)), h = LayerNorm(s); returns
+ *   the kept sum, mean and rstd (lvl_gated_add_layernorm_train_drop with gate NULL and a row index stride: with
+ *   row_index_stride == D its bits; p = 0: the bits of lvl_gated_add_layernorm_train). _bwd writes ds and dy = (keep ?
+ *   scale : 0) * ds, dgamma, dbeta; dadd nullable; ws: lvl_workspace_floats("gated_add_layernorm_bwd", rows, D). bf16 and
+ *   float32; D % 8 == 0, D <= 4096, row_index_stride % 8 == 0 and >= D.
+ * The embedding site is lvl_dropout_apply over the [B L, D] rows (it always runs on all rows). */
+int lvl_keymask_attn_drop_fwd(const void* q, const void* k, const void* v, const uint8_t* keymask, void* out, int contexts,
+                              int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
+                              int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p, int dtype,
+                              void* stream);
+int lvl_keymask_attn_drop_bwd(const void* q, const void* k, const void* v, const uint8_t* keymask, const void* dout,
+                              void* dq, void* dk, void* dv, float* ws, int contexts, int qrep, int Tk, int H,
+                              int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride,
+                              int idx_qrep, uint64_t seed, uint32_t site, float p, int dtype, void* stream);
+int lvl_dropout_add_layernorm_fwd(const void* res, const void* y, const float* gamma, const float* beta, float eps,
+                                  void* sum_out, void* h_out, float* mean, float* rstd, int rows, int D,
+                                  int64_t row_index_stride, uint64_t seed, uint32_t site, float p, int dtype, void* stream);
+int lvl_dropout_add_layernorm_bwd(const void* dh, const void* s, const float* gamma, const float* mean, const float* rstd,
+                                  const void* dadd, void* ds, void* dy, float* dgamma, float* dbeta, float* ws, int rows,
+                                  int D, int64_t row_index_stride, uint64_t seed, uint32_t site, float p, int dtype,
+                                  void* stream);
+
 /* ---- packed caption rows: the narrator's teacher-forced pass on the rows that carry a label -------------------------
  * A batch of B captions of up to L positions keeps len_b = cu[b + 1] - cu[b] leading rows each; cu [B + 1] int32 (device),
  * cu[0] = 0, R = cu[B] packed rows.

@@ -110,6 +110,10 @@ SIGNATURES = {
     'lvl_attn_rows_drop_bwd': (_I, [_P] * 7 + [_I, _I, _I, _I, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
     'lvl_keymask_attn_fwd': (_I, [_P] * 5 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _P]),
     'lvl_keymask_attn_bwd': (_I, [_P] * 9 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _P]),
+    'lvl_keymask_attn_drop_fwd': (_I, [_P] * 5 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_keymask_attn_drop_bwd': (_I, [_P] * 9 + [_I, _I, _I, _I, _L, _L, _L, _L, _I, _U64, _U32, _F, _I, _P]),
+    'lvl_dropout_add_layernorm_fwd': (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _L, _U64, _U32, _F, _I, _P]),
+    'lvl_dropout_add_layernorm_bwd': (_I, [_P] * 11 + [_I, _I, _L, _U64, _U32, _F, _I, _P]),
     'lvl_rows_pack': (_I, [_P, _L, _L, _P, _I, _I, _I, _P, _I, _P]),
     'lvl_rows_unpack': (_I, [_P, _P, _I, _I, _I, _P, _L, _L, _I, _P]),
 }

@@ -37,6 +37,7 @@ struct AttnDrop {
   uint64_t seed;
   uint32_t site, thr;
   float scale;
+  int idx_qrep;                // query rows per context in the element index (the forward's)
 };
 
 // q / dq rows `qs` elements apart, keys / values / dk / dv rows `kvs` apart and contexts `kvctx` apart; dout [rows, D]
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
     const float linv = 1.f / l;
     uint64_t keep = 0;                             // DROP: bit 4 k + r = keep of key k*16 + g*4 + r for this lane's query
     if constexpr (DROP) {
-      const uint64_t dgrp = (((uint64_t)(ctx * H + h) * qrep + qrow) << 6) | (uint64_t)g;
+      const uint64_t dgrp = (((uint64_t)(ctx * H + h) * drop.idx_qrep + qrow) << 6) | (uint64_t)g;
 #pragma unroll
       for (int k = 0; k < NKT; ++k) {
         const uint32_t kb = lvl_drop::group_keep(drop.seed, drop.site, dgrp + 4 * k, drop.thr);
@@ -253,6 +254,23 @@ int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v
   return LVL_OK;
 }
 
+// called by lvl_keymask_attn_drop_bwd (keymask_attn.hip) for bf16, Tk <= 256, p > 0
+int lvl_launch_keymask_attn_mfma_drop_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
+                                          void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H,
+                                          int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
+                                          int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p,
+                                          hipStream_t st) {
+  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), idx_qrep};
+  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<true, false, true>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<true, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
+                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
+                     (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, Tk, H, qrep,
+                     drop, mask, (size_t)mask_ctx_stride);
+  LVL_CHECK_LAUNCH("keymask_attn_drop_bwd (mfma)");
+  return LVL_OK;
+}
+
 extern "C" int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows,
                                        int qrep, int Tk, int H, int dtype, void* stream) {
   LVL_REQUIRE(rows == 0 || (q && kv && dout && dq && dkv), "cross_attn_rows_bwd: null pointer");
@@ -296,7 +314,7 @@ extern "C" int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* 
                     NKT * 16, dtype, Tk);
   if (contexts == 0) return LVL_OK;
   const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p)};
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), qrep};
 #define LVL_AR(DR, CA)                                                                                                 \
   do {                                                                                                                 \
     if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<DR, CA>>()) return rc;                                       \

@@ -16,6 +16,8 @@
 //   DROP: P = softmax(S) over all unmasked keys, Pd = keep ? P / (1 - p) : 0 rounded to bf16 where P is, O = Pd . V.
 //         The mask is dropout.h's over e = (((ctx * H + h) * qrep + i) << 8) | j: the four keys a lane holds in one score
 //         fragment (j = k*16 + g*4 + r) share one Philox call, generated where the fragment is packed; nothing is stored.
+//         (The index takes drop.idx_qrep for qrep: the same number, except when a key-masked call computes a subset of
+//         the query rows of a larger one.)
 #include "attn_mfma_common.h"
 #include "dropout.h"
 #include "internal.h"
@@ -32,6 +34,8 @@ struct AttnDrop {
   uint64_t seed;
   uint32_t site, thr;
   float scale;
+  int idx_qrep;                // query rows per context in the element index: qrep, or the full call's when this call
+                               // computes a subset of its rows (lvl_keymask_attn_drop_fwd)
 };
 
 // q rows at q + row * qs, keys at kp + ctx * kvctx + j * kvs (+ head), values at vp alike; out [rows, D]
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     // element group of (this query, key tile k, lane group g): e >> 2 with e = (query id << 8) | key
-    const uint64_t dgrp = (((uint64_t)(ctx * H + h) * qrep + qrow) << 6) | (uint64_t)g;
+    const uint64_t dgrp = (((uint64_t)(ctx * H + h) * (DROP ? drop.idx_qrep : qrep) + qrow) << 6) | (uint64_t)g;
 #pragma unroll
     for (int j = 0; j < NKT / 2; ++j) {
       if constexpr (DROP) {                        // l above is the sum over ALL unmasked keys
@@ -175,6 +179,21 @@ int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v
   return LVL_OK;
 }
 
+// called by lvl_keymask_attn_drop_fwd (keymask_attn.hip) for bf16, Tk <= 256, p > 0
+int lvl_launch_keymask_attn_mfma_drop_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
+                                          int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                                          int64_t kv_ctx_stride, int64_t mask_ctx_stride, int idx_qrep, uint64_t seed,
+                                          uint32_t site, float p, hipStream_t st) {
+  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), idx_qrep};
+  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<true, false, true>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_mfma_kernel<true, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
+                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
+                     (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, drop, mask, (size_t)mask_ctx_stride);
+  LVL_CHECK_LAUNCH("keymask_attn_drop_fwd (mfma)");
+  return LVL_OK;
+}
+
 // The dropout-capable rows attention of the training decoder: q [contexts * qrep rows, stride q_stride], keys k and values
 // v [contexts][Tk rows, stride kv_stride] with contexts kv_ctx_stride apart (strides in elements), out [rows, H*64].
 extern "C" int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* v, void* out, int contexts, int qrep, int Tk,
@@ -200,7 +219,7 @@ extern "C" int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* 
       (const uint16_t*)v == (const uint16_t*)k + D)
     return lvl_cross_attn_rows_fwd(q, k, out, contexts * qrep, qrep, Tk, H, dtype, stream);
   const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p)};
+  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), qrep};
 #define LVL_AR(DR, CA)                                                                                                 \
   do {                                                                                                                 \
     if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<DR, CA>>()) return rc;                                           \

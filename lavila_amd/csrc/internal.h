@@ -48,3 +48,14 @@ int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v
 int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
                                      void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride,
                                      int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st);
+// their <DROP, KEYMASK> twins behind lvl_keymask_attn_drop_fwd / _bwd (p > 0): the mask of dropout.h over
+// e = ((((ctx * H + h) * idx_qrep + i) << 8) | j
+int lvl_launch_keymask_attn_mfma_drop_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
+                                          int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
+                                          int64_t kv_ctx_stride, int64_t mask_ctx_stride, int idx_qrep, uint64_t seed,
+                                          uint32_t site, float p, hipStream_t st);
+int lvl_launch_keymask_attn_mfma_drop_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
+                                          void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H,
+                                          int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
+                                          int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p,
+                                          hipStream_t st);

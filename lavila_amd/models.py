@@ -636,7 +636,8 @@ def _clip_openai_timesformer_distilbert(clip_name, vision_kwargs, vision_layers,
                                         kwargs):
     """The common body of models.py:494-657: the TimeSformer tower of _clip_openai_timesformer (its CLIP weights loaded with
     strict=False as there) and distilbert-base-uncased as `textual`. The config holds dropout = attention_dropout = 0.0
-    (from_pretrained's is 0.1): lavila_amd.distilbert has no dropout."""
+    (from_pretrained's is 0.1) unless text dropout is switched on (distilbert.TEXT_DROPOUT / LAVILA_TEXT_DROPOUT=1), which
+    gives it transformers' 0.1 / 0.1."""
     vision_model, clip_sd = _openai_timesformer_tower(clip_name, vision_kwargs, vision_layers, num_frames,
                                                       timesformer_gated_xattn, drop_path_rate, timesformer_freeze_space)
     if clip_sd is not None:

@@ -1761,6 +1761,98 @@ def keymask_attention(q, k, v, keymask, heads):
     return _KeymaskAttnFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads)
 
 
+class _KeymaskAttnDropFn(torch.autograd.Function):
+    """_KeymaskAttnFn with dropout on the probabilities (lvl_keymask_attn_drop_fwd / _bwd). No mask is saved: the backward
+    regenerates it from ctx.drop = (idx_qrep, seed, site, p); idx_qrep = query rows per sample of the FULL call, so that the
+    row-0 form (Lq = 1, idx_qrep = L) draws the mask elements of row 0 of the full call."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, keymask, heads, idx_qrep, seed, site, p):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        C.require_device(q, k, v, keymask)
+        B, Tk, D = k.shape
+        if D != heads * 64:
+            raise C.HipExtensionError(f'key-masked attention: width {D} != heads*64 ({heads} heads)')
+        if q.shape[0] != B or q.shape[-1] != D or v.shape != k.shape or q.dtype != k.dtype or v.dtype != k.dtype:
+            raise C.HipExtensionError(f'key-masked attention: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, '
+                                      f'v {tuple(v.shape)} {v.dtype} do not belong together')
+        if keymask is not None and (keymask.dtype != torch.uint8 or tuple(keymask.shape) != (B, Tk)):
+            raise C.HipExtensionError(f'key-masked attention: the mask must be uint8 [{B}, {Tk}]')
+        qrep = q.numel() // (B * D) if B else 1
+        out = torch.empty_like(q)
+        ctx.drop = (int(idx_qrep), int(seed), int(site), float(p))
+        C.check(C.lib().lvl_keymask_attn_drop_fwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(keymask), C.ptr(out), B, qrep, Tk, heads,
+                                                  D, D, Tk * D, Tk, *ctx.drop, C.dtype_code(q), C.stream_ptr()),
+                'lvl_keymask_attn_drop_fwd')
+        ctx.save_for_backward(q, k, v)
+        ctx.keymask = keymask
+        ctx.cfg = (B, qrep, Tk, heads, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v = ctx.saved_tensors
+        B, qrep, Tk, H, D = ctx.cfg
+        dout = dout.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ws = C.workspace('keymask_attn_bwd', B * qrep * H, Tk, q.device)
+        C.check(C.lib().lvl_keymask_attn_drop_bwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(ctx.keymask), C.ptr(dout), C.ptr(dq),
+                                                  C.ptr(dk), C.ptr(dv), C.ptr(ws), B, qrep, Tk, H, D, D, Tk * D, Tk, *ctx.drop,
+                                                  C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_drop_bwd')
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def keymask_attention_drop(q, k, v, keymask, heads, idx_qrep, seed, site, p):
+    """keymask_attention with dropout p on the probabilities: mask element ((((b * heads + h) * idx_qrep + i) << s) | j of
+    (seed, site) -- include/lavila_hip.h, the text tower's mask contract."""
+    return _KeymaskAttnDropFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads, idx_qrep, seed, site, p)
+
+
+class _DropoutAddLnFn(torch.autograd.Function):
+    """h = LayerNorm(res + (keep ? scale : 0) * y) (lvl_dropout_add_layernorm_fwd / _bwd; DistilBERT's FFN site). The kept sum
+    and the row statistics are saved, the mask is regenerated from ctx.drop = (row_index_stride, seed, site, p)."""
+
+    @staticmethod
+    def forward(ctx, res, y, gamma, beta, eps, row_index_stride, seed, site, p):
+        res, y = res.contiguous(), y.contiguous()
+        rows, D = _rows_cols(res)
+        g, b = _f32(gamma), _f32(beta)
+        C.require_device(res, y, g, b)
+        s, h = torch.empty_like(res), torch.empty_like(res)
+        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+        ctx.drop = (int(row_index_stride), int(seed), int(site), float(p))
+        C.check(C.lib().lvl_dropout_add_layernorm_fwd(C.ptr(res), C.ptr(y), C.ptr(g), C.ptr(b), float(eps), C.ptr(s), C.ptr(h),
+                                                      C.ptr(mean), C.ptr(rstd), rows, D, *ctx.drop, C.dtype_code(res),
+                                                      C.stream_ptr()), 'lvl_dropout_add_layernorm_fwd')
+        ctx.save_for_backward(s, g, mean, rstd)
+        ctx.pdt = (gamma.dtype, beta.dtype)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        s, g, mean, rstd = ctx.saved_tensors
+        rows, D = _rows_cols(s)
+        dh = dh.contiguous()
+        ds, dy = torch.empty_like(s), torch.empty_like(s)
+        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
+        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
+        C.check(C.lib().lvl_dropout_add_layernorm_bwd(C.ptr(dh), C.ptr(s), C.ptr(g), C.ptr(mean), C.ptr(rstd), None, C.ptr(ds),
+                                                      C.ptr(dy), C.ptr(dgamma), C.ptr(dbeta), C.ptr(ws), rows, D, *ctx.drop,
+                                                      C.dtype_code(s), C.stream_ptr()), 'lvl_dropout_add_layernorm_bwd')
+        return ds, dy, dgamma.to(ctx.pdt[0]), dbeta.to(ctx.pdt[1]), None, None, None, None, None
+
+
+def dropout_add_layer_norm(res, y, weight, bias, eps, row_index_stride, seed, site, p):
+    """LayerNorm(res + dropout(y)): mask element row * row_index_stride + col of (seed, site); row_index_stride is the width
+    when the call holds all rows of the site, L * width when it holds row 0 of every sample."""
+    res = lowp(res)
+    if res.dtype not in (torch.float32, torch.bfloat16):
+        raise C.HipExtensionError(f'dropout_add_layer_norm is built for float32 and bfloat16 rows, got {res.dtype}')
+    return _narrow(_DropoutAddLnFn.apply(res, y.to(res.dtype), weight, bias, eps, row_index_stride, seed, site, p))
+
+
 # --------------------------------------------------------------------------------------------------
 # contrastive head (raw kernels; the autograd wrapper + collectives live in lavila_amd/loss.py)
 # --------------------------------------------------------------------------------------------------
