@@ -55,6 +55,7 @@ import torch.distributed as dist
 
 from . import models as _models
 from . import narrator as _narrator
+from . import openai_model as _openai_model
 from . import ops
 
 _active = threading.local()
@@ -204,6 +205,9 @@ class GraphedTrainStep:
             raise NotImplementedError('GraphedTrainStep: CLIP_HF is not capturable (the step is called with (video, tokens): '
                                       'it carries no attention mask, and the DistilBERT tower trims each batch to its longest '
                                       'caption from a host read); run it with the eager loop')
+        if isinstance(bare, _openai_model.CLIP) or isinstance(getattr(bare, 'visual', None), _openai_model.VisionTransformer):
+            raise NotImplementedError('GraphedTrainStep: the per-frame OpenAI CLIP models (CLIP_OPENAI_VIT*, VCLM_OPENAI_VIT*) '
+                                      'have not been captured and replayed on this step; run them with the eager loop')
         if not torch.cuda.is_available():
             raise RuntimeError('GraphedTrainStep needs a HIP device (hipGraph capture)')
         for grp in optimizer.param_groups:

@@ -5,7 +5,8 @@ swallowed exactly as the reference's **kwargs do), output dict keys and state_di
 main_pretrain.py / eval_zeroshot.py drive it unchanged. Built: the dual-encoder pretraining path
 and the narrator on TimeSformer towers (`VCLM_OPENAI_TIMESFORMER_*`, :887-1198; lavila_amd.narrator +
 lavila_amd.gpt2_gated) and the classification fine-tune's `VideoClassifier` / `VideoClassifierMultiHead` (:24-72). The
-per-frame ViT narrators (`VCLM_OPENAI_VIT*`) are absent; `CLIP_HF` (:176-290) runs on DistilBERT with the default projection
+per-frame OpenAI CLIPs (`CLIP_OPENAI_VIT*`, :1201-1218) and their narrators (`VCLM_OPENAI_VIT*`, :723-884) run on
+lavila_amd.openai_model.VisionTransformer; `CLIP_HF` (:176-290) runs on DistilBERT with the default projection
 (`CLIP_OPENAI_TIMESFORMER_*_DISTILBERT_BASE`, `CLIP_HF_TIMESFORMER_DISTILBERT_BASE`).
 """
 import contextlib
@@ -23,7 +24,8 @@ from .distilbert import DistilBertModel, distilbert_config
 from .gpt2_gated import GPT2LMHeadModel as GatedGPT2LMHeadModel
 from .gpt2_gated import augment_gpt2_config, gpt2_config
 from .narrator import VCLM_HF
-from .openai_model import QuickGELU, Transformer
+from .openai_model import CLIP as OpenAICLIP
+from .openai_model import QuickGELU, Transformer, build_model
 from .timesformer import LayerNorm, SpaceTimeTransformer
 from .utils import remap_keys, rsetattr  # noqa: F401  (re-exported like the reference)
 
@@ -778,21 +780,8 @@ def load_gpt2_weights(text_decoder, gpt2_sd):
     return loaded
 
 
-def _vclm_openai_timesformer(clip_name, vision_kwargs, vision_width, vision_layers, gpt2_name, cross_attn_freq, text_width,
-                             heads, gated_xattn, random_init_gpt2, freeze_lm_vclm, freeze_visual_vclm,
-                             freeze_visual_vclm_temporal, num_frames, timesformer_gated_xattn, kwargs):
-    """The common body of models.py:887-1198's TimeSformer narrators."""
-    vision_model = SpaceTimeTransformer(
-        num_frames=num_frames, time_init='zeros', attention_style='frozen-in-time', ln_pre=True,
-        act_layer=QuickGELU, is_tanh_gating=timesformer_gated_xattn, **vision_kwargs)
-    clip_sd = load_openai_clip(clip_name, 'cpu')
-    if clip_sd is not None:
-        print(f"=> Loading CLIP ({clip_name}) weights")
-        vis = {k[len('visual.'):]: v for k, v in clip_sd.items() if k.startswith('visual.')}
-        print(vision_model.load_state_dict(remap_keys(vis, transformer_layers=vision_layers), strict=False))
-    vision_model.head = nn.Identity()
-    vision_model.pre_logits = nn.Identity()
-    vision_model.fc = nn.Identity()
+def _vclm_decoder(gpt2_name, cross_attn_freq, gated_xattn, random_init_gpt2, freeze_lm_vclm):
+    """The gated-cross-attention GPT-2 of every narrator constructor: config, pretrained weights when present, LM freeze."""
     # gpt2_config() holds resid / embd / attn_pdrop = 0.0, or transformers' 0.1 (what the reference's GPT2Config carries
     # here) when the decoder's dropout is switched on (LAVILA_DECODER_DROPOUT=1, gpt2_gated.DECODER_DROPOUT)
     config = augment_gpt2_config(gpt2_config(gpt2_name), cross_attn_freq=cross_attn_freq, gated_xattn=gated_xattn)
@@ -805,6 +794,34 @@ def _vclm_openai_timesformer(clip_name, vision_kwargs, vision_width, vision_laye
     if freeze_lm_vclm:
         print('Freeze the LM part of TextDecoder of VCLM')
         text_decoder.freeze_lm_weights()
+    return text_decoder
+
+
+def _vclm_openai_timesformer(clip_name, vision_kwargs, vision_width, vision_layers, gpt2_name, cross_attn_freq, text_width,
+                             heads, gated_xattn, random_init_gpt2, freeze_lm_vclm, freeze_visual_vclm,
+                             freeze_visual_vclm_temporal, num_frames, timesformer_gated_xattn, kwargs):
+    """The common body of models.py:723-1198's narrators. vision_kwargs None: the per-frame tower, `.visual` of the OpenAI
+    CLIP `clip_name` (models.py:723-884); a dict: the TimeSformer tower built from it (models.py:887-1198)."""
+    if vision_kwargs is None:
+        if freeze_visual_vclm or freeze_visual_vclm_temporal:
+            flag = 'freeze_visual_vclm' if freeze_visual_vclm else 'freeze_visual_vclm_temporal'
+            raise NotImplementedError(f'{flag}=True: openai_model.VisionTransformer has no freeze_spatial_weights / '
+                                      'freeze_temporal_weights (the reference constructor fails on the same call with an '
+                                      'AttributeError); the flags belong to the TimeSformer narrators')
+        vision_model = _clip_openai_vit(clip_name).visual
+    else:
+        vision_model = SpaceTimeTransformer(
+            num_frames=num_frames, time_init='zeros', attention_style='frozen-in-time', ln_pre=True,
+            act_layer=QuickGELU, is_tanh_gating=timesformer_gated_xattn, **vision_kwargs)
+        clip_sd = load_openai_clip(clip_name, 'cpu')
+        if clip_sd is not None:
+            print(f"=> Loading CLIP ({clip_name}) weights")
+            vis = {k[len('visual.'):]: v for k, v in clip_sd.items() if k.startswith('visual.')}
+            print(vision_model.load_state_dict(remap_keys(vis, transformer_layers=vision_layers), strict=False))
+        vision_model.head = nn.Identity()
+        vision_model.pre_logits = nn.Identity()
+        vision_model.fc = nn.Identity()
+    text_decoder = _vclm_decoder(gpt2_name, cross_attn_freq, gated_xattn, random_init_gpt2, freeze_lm_vclm)
     if freeze_visual_vclm:
         print('Freeze the spatial part of VideoEncoder of VCLM')
         vision_model.freeze_spatial_weights()
@@ -862,3 +879,83 @@ def VCLM_OPENAI_TIMESFORMER_LARGE_336PX_GPT2_XL(gated_xattn=False, freeze_lm_vcl
     return _vclm_openai_timesformer('ViT-L/14@336px', dict(_TSF_L14_336), 1024, 24, 'gpt2-xl', 3, 1600, 25, gated_xattn,
                                     False, freeze_lm_vclm, freeze_visual_vclm, freeze_visual_vclm_temporal, num_frames,
                                     timesformer_gated_xattn, kwargs)
+
+
+# --------------------------------------------------------------------------------------------------
+# per-frame OpenAI CLIP (the zero-shot baseline) and its narrators: openai_model.VisionTransformer towers
+# --------------------------------------------------------------------------------------------------
+# name -> (embed_dim, resolution, vision layers, vision width, patch, text width, text heads); context 77, vocabulary
+# 49408 and 12 text layers everywhere (the published ViT checkpoints of openai_clip.py:31-41)
+_OPENAI_VIT = {
+    'ViT-B/32': (512, 224, 12, 768, 32, 512, 8),
+    'ViT-B/16': (512, 224, 12, 768, 16, 512, 8),
+    'ViT-L/14': (768, 224, 24, 1024, 14, 768, 12),
+    'ViT-L/14@336px': (768, 336, 24, 1024, 14, 768, 12),
+}
+
+
+def _clip_openai_vit(name):
+    """`load_openai_clip(name)[0]` of the reference (openai_clip.py:104-146 -> build_model): the OpenAI CLIP `name` in
+    float32, from the checkpoint when LAVILA_CLIP_WEIGHTS_DIR holds it, else from the published hyperparameters with its
+    seeded initialisation (load_openai_clip warns)."""
+    clip_sd = load_openai_clip(name, 'cpu')
+    if clip_sd is not None:
+        print(f"=> Loading CLIP ({name}) weights")
+        return build_model(clip_sd)
+    embed_dim, resolution, layers, width, patch, text_width, text_heads = _OPENAI_VIT[name]
+    return OpenAICLIP(embed_dim, resolution, layers, width, patch, 77, 49408, text_width, text_heads, 12).eval()
+
+
+def CLIP_OPENAI_VITB32(**kwargs):
+    """models.py:1201-1203: OpenAI CLIP ViT-B/32 (50 tokens per frame)."""
+    return _clip_openai_vit('ViT-B/32')
+
+
+def CLIP_OPENAI_VITB16(**kwargs):
+    """models.py:1206-1208: OpenAI CLIP ViT-B/16 (197 tokens per frame)."""
+    return _clip_openai_vit('ViT-B/16')
+
+
+def CLIP_OPENAI_VITL14(**kwargs):
+    """models.py:1211-1213: OpenAI CLIP ViT-L/14 (257 tokens per frame)."""
+    return _clip_openai_vit('ViT-L/14')
+
+
+def CLIP_OPENAI_VITL14_336PX(**kwargs):
+    """models.py:1216-1218: OpenAI CLIP ViT-L/14 at 336 pixels (577 tokens per frame)."""
+    return _clip_openai_vit('ViT-L/14@336px')
+
+
+def _vclm_openai_vit(clip_name, vision_width, gpt2_name, text_width, heads, gated_xattn, freeze_lm_vclm, freeze_visual_vclm,
+                     freeze_visual_vclm_temporal, kwargs):
+    kwargs.pop('text_use_cls_token')          # as in the reference: must be among the kwargs, is ignored
+    return _vclm_openai_timesformer(clip_name, None, vision_width, None, gpt2_name, 2, text_width, heads, gated_xattn, False,
+                                    freeze_lm_vclm, freeze_visual_vclm, freeze_visual_vclm_temporal, None, None, kwargs)
+
+
+def VCLM_OPENAI_VITB16_GPT2_LARGE(gated_xattn=False, freeze_lm_vclm=False, freeze_visual_vclm=False,
+                                  freeze_visual_vclm_temporal=False, **kwargs):
+    """models.py:723-761: per-frame ViT-B/16 + GPT-2 Large (1280 wide, 36 layers), cross-attention in every 2nd block."""
+    return _vclm_openai_vit('ViT-B/16', 768, 'gpt2-large', 1280, 20, gated_xattn, freeze_lm_vclm, freeze_visual_vclm,
+                            freeze_visual_vclm_temporal, kwargs)
+
+
+def VCLM_OPENAI_VITB16_GPT2_XL(gated_xattn=False, freeze_lm_vclm=False, freeze_visual_vclm=False,
+                               freeze_visual_vclm_temporal=False, **kwargs):
+    """models.py:764-802: per-frame ViT-B/16 + GPT-2 XL (1600 wide, 48 layers), cross-attention in every 2nd block."""
+    return _vclm_openai_vit('ViT-B/16', 768, 'gpt2-xl', 1600, 25, gated_xattn, freeze_lm_vclm, freeze_visual_vclm,
+                            freeze_visual_vclm_temporal, kwargs)
+
+
+def VCLM_OPENAI_VITL14_GPT2_XL(gated_xattn=False, freeze_lm_vclm=False, freeze_visual_vclm=False,
+                               freeze_visual_vclm_temporal=False, **kwargs):
+    """models.py:805-843: per-frame ViT-L/14 + GPT-2 XL."""
+    return _vclm_openai_vit('ViT-L/14', 1024, 'gpt2-xl', 1600, 25, gated_xattn, freeze_lm_vclm, freeze_visual_vclm,
+                            freeze_visual_vclm_temporal, kwargs)
+
+
+def VCLM_OPENAI_VITL14_336PX_GPT2_XL(gated_xattn=False, freeze_lm_vclm=False, freeze_visual_vclm=False,
+                                     freeze_visual_vclm_temporal=False, **kwargs):
+    """models.py:846-884: per-frame ViT-L/14 at 336 pixels + GPT-2 XL."""
+    return _vclm_openai_vit('ViT-L/14@336px', 1024, 'gpt2-xl', 1600, 25, gated_xattn, freeze_lm_vclm, freeze_visual_vclm,
+                            freeze_visual_vclm_temporal, kwargs)

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from . import _cabi as C
 from . import ops
+from .openai_model import VisionTransformer
 from .timesformer import SpaceTimeTransformer, _like_caller
 
 
@@ -195,12 +196,20 @@ class VCLM_HF(nn.Module):
 
     def encode_image(self, image, use_checkpoint=False):
         """image [B,C,T,H,W] -> [B, num_img_queries, text_width] (narrator.py:63-90). The reference permutes the clip to
-        BTCHW with a copy and the features to BDN and back; here the tower reads BCTHW in place and hands [B, T, D] on."""
-        if not isinstance(self.visual, SpaceTimeTransformer):
-            raise NotImplementedError('VCLM_HF.encode_image: only the SpaceTimeTransformer tower is built (narrator.py:73-76)')
+        BTCHW with a copy and the features to BDN and back; here the tower reads BCTHW in place and hands [B, T, D] on.
+        SpaceTimeTransformer: all 1 + T*N tokens of the clip. openai_model.VisionTransformer (narrator.py:64-70): the tower
+        per frame, the N patch rows of every frame (no cls, no ln_post) as [B, T*N, D] -- the reference's view / permute /
+        flatten / permute round trip is the identity on (b, t)-major rows; dropping the cls rows is the one gather."""
         with ops.model_forward():
-            tok = self.visual.patch_embed.tokens_from_bcthw(image)
-            x = self.visual._features_from_tokens(tok, image.shape[2], use_checkpoint, False)   # [B, 1 + F*N, D]
+            if isinstance(self.visual, VisionTransformer):
+                x = self.visual.forward_clip(image, use_checkpoint=use_checkpoint, cls_at_last=False)     # [B*T, N, D]
+                x = x.reshape(image.shape[0], -1, x.shape[-1])                                             # [B, T*N, D]
+            elif isinstance(self.visual, SpaceTimeTransformer):
+                tok = self.visual.patch_embed.tokens_from_bcthw(image)
+                x = self.visual._features_from_tokens(tok, image.shape[2], use_checkpoint, False)   # [B, 1 + F*N, D]
+            else:
+                raise NotImplementedError('VCLM_HF.encode_image: only the SpaceTimeTransformer and openai_model.'
+                                          'VisionTransformer towers are built (narrator.py:64-76)')
             pooled = self.img_attn_pool(self.img_queries, x)          # queries shared by the batch: projected once
             return _like_caller(self.img_attn_pool_norm(pooled), image, self.img_queries)
 

@@ -1388,6 +1388,10 @@ class _EmbedTokensFn(torch.autograd.Function):
 
 
 def embed_tokens(pe, cls_token, pos_embed, temporal_embed, frames, n_per_frame):
+    """temporal_embed None (the per-frame ViT of openai_model.VisionTransformer: frames == 1, no temporal embedding): a zero
+    row stands in for it; the C entry is called as for every other caller."""
+    if temporal_embed is None:
+        temporal_embed = torch.zeros(1, max(1, frames), pe.shape[-1], dtype=torch.float32, device=pe.device)
     return _EmbedTokensFn.apply(lowp(pe), cls_token, pos_embed, temporal_embed, frames, n_per_frame)
 
 

@@ -161,27 +161,7 @@ class VideoPatchEmbed(nn.Module):
     def _tokens(self, video, frame_major):
         if self.patch_size[0] != self.patch_size[1]:
             raise NotImplementedError('non-square patches')
-        w = self.proj.weight
-        patches = ops.patchify(video, self.patch_size[0], _compute_dtype(w), frame_major=frame_major)
-        w2 = w.reshape(w.shape[0], -1)
-        k = w2.shape[1]
-        if k % 64 and patches.is_cuda and w2.shape[0] % 256 == 0:
-            # 14 x 14 patches: 3*14*14 = 588 contraction elements. The MFMA GEMMs walk K in blocks of 64: zero columns up
-            # to 640 on both operands (exact) keep the patch embedding of the TSF-L/14 towers on lvl_linear_tn /
-            # lvl_linear_wgrad; the weight gradient comes back through the pad's slice
-            pad = 64 - k % 64
-            patches = F.pad(patches, (0, pad))
-            if torch.is_grad_enabled() and w.requires_grad:
-                w2 = F.pad(w2, (0, pad))        # part of the autograd graph: one pad (and one cast) per training step
-            else:
-                # inference: ONE padded copy per parameter state, so that ops.weight_copies' cache (keyed on the tensor it
-                # is handed) hits on every later call instead of re-padding and re-casting per forward
-                key = (w._version, w.data_ptr(), ops._generation, w.dtype)
-                hit = _padded_patch_weights.get(self.proj)
-                if hit is None or hit[0] != key:
-                    hit = _padded_patch_weights[self.proj] = (key, F.pad(w2.detach(), (0, pad)))
-                w2 = hit[1]
-        return ops.linear(patches, w2, self.proj.bias)
+        return conv_patch_tokens(self.proj, video, self.patch_size[0], frame_major)
 
     def forward(self, x):
         """Reference signature: x [B,F,C,H,W] -> [B*F, D, H/P, W/P] (timesformer.py:79-84)."""
@@ -193,6 +173,33 @@ class VideoPatchEmbed(nn.Module):
 
 
 _padded_patch_weights = __import__('weakref').WeakKeyDictionary()     # Conv2d module -> (state key, zero-padded [D, 640] weight)
+
+
+def conv_patch_tokens(conv, video, patch, frame_major):
+    """The stride-P Conv2d `conv` (weight [D, 3, P, P], optional bias) on every frame of a clip ([B,C,F,H,W], or
+    [B,F,C,H,W] when frame_major) as the HIP patch gather + one GEMM against the weight viewed as [D, 3*P*P]:
+    -> [B, F*N, D], rows (b, f, n)-major. Shared by VideoPatchEmbed and openai_model.VisionTransformer."""
+    w = conv.weight
+    patches = ops.patchify(video, patch, _compute_dtype(w), frame_major=frame_major)
+    w2 = w.reshape(w.shape[0], -1)
+    k = w2.shape[1]
+    if k % 64 and patches.is_cuda and w2.shape[0] % 256 == 0:
+        # 14 x 14 patches: 3*14*14 = 588 contraction elements. The MFMA GEMMs walk K in blocks of 64: zero columns up
+        # to 640 on both operands (exact) keep the patch embedding of the L/14 towers on lvl_linear_tn /
+        # lvl_linear_wgrad; the weight gradient comes back through the pad's slice
+        pad = 64 - k % 64
+        patches = F.pad(patches, (0, pad))
+        if torch.is_grad_enabled() and w.requires_grad:
+            w2 = F.pad(w2, (0, pad))        # part of the autograd graph: one pad (and one cast) per training step
+        else:
+            # inference: ONE padded copy per parameter state, so that ops.weight_copies' cache (keyed on the tensor it
+            # is handed) hits on every later call instead of re-padding and re-casting per forward (ADVICE r4)
+            key = (w._version, w.data_ptr(), ops._generation, w.dtype)
+            hit = _padded_patch_weights.get(conv)
+            if hit is None or hit[0] != key:
+                hit = _padded_patch_weights[conv] = (key, F.pad(w2.detach(), (0, pad)))
+            w2 = hit[1]
+    return ops.linear(patches, w2, conv.bias)
 
 
 class VarAttention(nn.Module):
