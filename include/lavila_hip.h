@@ -12,6 +12,9 @@
  *   - `dtype` selects the activation element type: LVL_F32 (parity path) or LVL_BF16 (perf path);
  *     statistics, parameters (gamma/beta/bias/pos-embeds) and workspaces are always float32
  *   - row-major, innermost dimension contiguous, base pointers 16-byte aligned
+ *   - sizes: row counts are int64_t and every offset that grows with the rows (or with the batch) is formed in 64 bits, so
+ *     a tensor may exceed 2^31 elements / 4 GiB unless the entry point names a limit; the limits that exist are listed
+ *     per entry point in DESIGN.md, "Operand-size limits" (the 4 GiB inputs of lvl_linear_tn are the one on the training path)
  *   - `stream` is a hipStream_t passed as void*; every call is asynchronous and stream-ordered,
  *     never allocates, never synchronises, and is hipGraph-capturable
  *   - return value: 0 on success, negative LVL_E* otherwise (lvl_last_error() gives the text);
@@ -194,7 +197,8 @@ int lvl_embed_tokens_bwd(const void* dx, float* dpos, float* dtem, float* ws, in
  * x[b, l, :] = table[tokens[b, l], :] + pos[l, :]   (CLIP.encode_text, models.py:152-153: `self.token_embedding(text)`
  * + `self.positional_embedding`; under autocast the sum is rounded once to `dtype`). tokens: int64, row stride
  * tok_stride elements (a `text[:, :L]` view of the [B, 77] batch is read in place), ids clamped to [0, V); table [V, W],
- * pos [>= L, W] f32; x [B, L, W] dtype. W % 4 == 0 (forward), W % 8 == 0 (backward).
+ * pos [>= L, W] f32; x [B, L, W] dtype. W % 4 == 0 (forward), W % 8 == 0 (backward). B * L < 2^31 token rows (both calls:
+ * LVL_EINVAL otherwise); x and dx may exceed 2^31 elements.
  * lvl_text_embed_bwd: autograd of the same two lines -- d table [V, W] f32 (= nn.Embedding's dense backward: row v is the
  * sum of the dx rows whose token is v, added in a fixed order -- eight contiguous row ranges, ascending inside each; rows of
  * unused ids zero) and d pos [ctx, W] f32
@@ -669,8 +673,13 @@ int lvl_sample_next_token(const void* logits, int64_t row_stride, int rows, int 
  *   LVL_EPI_BIAS_GELU_DERIV  (bf16 only) LVL_EPI_BIAS_QUICKGELU_DERIV for the same: u = acc + bias (f32, not rounded);
  *                            y = gelu(u); aux_out = gelu'(u), in [-0.129, 1.129]; one erf serves both outputs. The backward
  *                            is LVL_EPI_MUL_AUX_COLSUM on the stored derivative
- * aux_out / aux_in: [M,N] bf16. N % 256 == 0 and K % 64 == 0 (operands < 4 GiB), else LVL_ENOSYS. Workspace (QUICKGELU_BWD /
+ * aux_out / aux_in: [M,N] bf16. N % 256 == 0 and K % 64 == 0, else LVL_ENOSYS. Workspace (QUICKGELU_BWD /
  * MUL_AUX_COLSUM / GELU_BWD only): lvl_workspace_floats("linear_tn", M, N) floats.
+ * Sizes: the two INPUT operands must stay below 4 GiB each -- M*K*2 < 2^32 and N*K*2 < 2^32 bytes (K as passed, i.e. 3*K0 in
+ * the f32-class mode), else LVL_ENOSYS before anything is launched: the kernel fetches x and w with 32-bit byte offsets. The
+ * largest M is therefore floor((2^32 - 1) / (2 K)). y, aux_out and aux_in have NO such limit (64-bit row offsets; M*N*2, or
+ * M*N*4 in the f32-class mode, may exceed 4 GiB and M*N may exceed 2^31 elements); ceil(M / 256) * (N / 256) must stay below
+ * 2^31 tiles (LVL_EINVAL).
  * dtype = LVL_F32 selects the F32-CLASS MODE of the same kernel (the parity configuration, north_star "within 1e-3
  * fp32"): x [M, 3K0] and w [N, 3K0] are the bf16 term images lvl_split_bf16x3 writes (role 0 for x, role 1 for w;
  * K = 3*K0, K0 % 64 == 0), so that one pass accumulates xh.wh + xh.wl + xl.wh in f32 (~2^-17 relative per product);
@@ -694,7 +703,8 @@ int lvl_linear_tn(const void* x, const void* w, const float* bias, void* y, void
  * persistent kernel over the N / 256 full column tiles (the launch it issues for w[:256 * (N / 256)], with N as the output
  * stride; `sched` as there) and an edge kernel for the 64 / 128 / 192 columns behind them (alone when N < 256). No atomics,
  * fixed summation order: repeats are bit-identical. epilogue must be LVL_EPI_BIAS and dtype LVL_BF16 (others: LVL_ENOSYS;
- * unknown values LVL_EINVAL); operands below 4 GiB and 16-byte aligned pointers as for lvl_linear_tn. */
+ * unknown values LVL_EINVAL); x and w below 4 GiB each (LVL_ENOSYS otherwise), no limit on y, and 16-byte aligned pointers as
+ * for lvl_linear_tn. */
 int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* y, uint32_t* sched, int64_t M, int N,
                          int K, int epilogue, int dtype, void* stream);
 
@@ -710,7 +720,8 @@ int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* 
  * the other splits of its tile, so a compute unit held by another kernel delays the launch by a fraction of a unit
  * instead of a second round. With all CUs available nobody steals and the result is bit-identical to the static plan
  * (NULL). f32-class weight gradients use the same entry with row-STACKED term images (lvl_split_bf16x3 with
- * dst_term_stride = rows_padded * cols): dy3 [3M,N] = (h; h; l), x3 [3M,K] = (h; l; h); dw is float32 either way. */
+ * dst_term_stride = rows_padded * cols): dy3 [3M,N] = (h; h; l), x3 [3M,K] = (h; l; h); dw is float32 either way.
+ * Sizes: no limit on dy or x (64-bit row pointers per lane; M / 32 < 2^31 row blocks): both may exceed 4 GiB. */
 int lvl_linear_wgrad(const void* dy, const void* x, float* dw, float* dbias, float* ws, uint32_t* sched, int64_t M,
                      int N, int K, int dtype, void* stream);
 /* What lvl_linear_wgrad would launch for (M, N, K) under the current lvl_set_compute_units limit (host-side query, no

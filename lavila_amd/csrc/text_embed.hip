@@ -189,6 +189,8 @@ extern "C" int lvl_text_embed_fwd(const int64_t* tokens, int64_t tok_stride, con
   LVL_REQUIRE(tokens && table && pos && x, "text_embed_fwd: null pointer");
   LVL_REQUIRE(B >= 0 && L > 0 && V > 0 && W > 0 && W % 4 == 0 && tok_stride >= L,
               "text_embed_fwd: bad shape B=%d L=%d W=%d V=%d stride=%lld", B, L, W, V, (long long)tok_stride);
+  // one workgroup per token row, the row index an int in the kernel (lvl_text_embed_bwd has the same limit)
+  LVL_REQUIRE((int64_t)B * L < (1ll << 31), "text_embed_fwd: too many token rows");
   LVL_REQUIRE(lvl_aligned16(table) && lvl_aligned16(pos) && (reinterpret_cast<uintptr_t>(x) & 7) == 0,
               "text_embed_fwd: table / pos must be 16-byte aligned, x 8-byte aligned");
   if (B == 0) return LVL_OK;

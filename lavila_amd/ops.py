@@ -274,7 +274,7 @@ def _wgrad_f32(dy2, x2, wdt):
     """dW = dy^T x for float32 operands: lvl_linear_wgrad on row-stacked term images (f32-class, see split3)."""
     n_out, n_in = dy2.shape[1], x2.shape[1]
     ws_floats = C.lib().lvl_workspace_floats(b'linear_wgrad', n_out, n_in) if (F32_MFMA and dy2.is_cuda) else -1
-    if ws_floats < 0 or dy2.shape[0] * max(n_in, n_out) * 6 >= (1 << 32):
+    if ws_floats < 0 or not _wgrad_f32_ok(dy2.shape[0], n_out, n_in):
         return (dy2.t() @ x2).to(wdt)
     dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
     x2 = x2 if x2.is_contiguous() else x2.contiguous()
@@ -283,6 +283,25 @@ def _wgrad_f32(dy2, x2, wdt):
 
 def _tn_ok_f32(rows: int, n_out: int, n_in: int) -> bool:
     return F32_MFMA and _tn_ok(rows, n_out, 3 * n_in)
+
+
+def _wgrad_f32_ok(rows: int, n_out: int, n_in: int) -> bool:
+    """The size gate of _wgrad_f32: the row-stacked term images (3 x rows of bf16) of both operands stay below 4 GiB.
+    lvl_linear_wgrad itself has no such limit (64-bit row pointers; DESIGN.md, "Operand-size limits"): the gate keeps the
+    float32 path inside what the suite runs."""
+    return rows * max(n_in, n_out) * 6 < (1 << 32)
+
+
+def _skinny_ok(rows: int, n_out: int, n_in: int) -> bool:
+    """Inference Linears that lvl_linear_tn does not tile go to lvl_linear_skinny: operands below 2 GiB."""
+    return (rows > 0 and not _tn_ok(rows, n_out, n_in) and n_out % 16 == 0 and n_in % 64 == 0
+            and rows * max(n_in, n_out) * 2 < (1 << 31))
+
+
+def _skinny_f32_ok(rows: int, n_out: int, n_in: int) -> bool:
+    """The same for float32 rows on lvl_linear_skinny_f32c (term images of 3 x n_in, float32 output): below 2 GiB."""
+    return (rows > 0 and not _tn_ok_f32(rows, n_out, n_in) and n_out % 16 == 0 and n_in % 32 == 0
+            and rows * max(3 * n_in, n_out) * 4 < (1 << 31))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -789,8 +808,7 @@ def linear(x, weight, bias=None, ln=None):
         # inference, widths the 256-column-panel kernel does not tile (the narrator's pooling projection to_kv
         # [128 x 768], coca.py:78): the strip / LDS-tile kernel of the decoder (lvl_linear_skinny) instead of the library
         rows, n_in, n_out = x.numel() // x.shape[-1], x.shape[-1], weight.shape[0]
-        if (rows > 0 and not _tn_ok(rows, n_out, n_in) and n_out % 16 == 0 and n_in % 64 == 0
-                and rows * max(n_in, n_out) * 2 < (1 << 31)):
+        if _skinny_ok(rows, n_out, n_in):
             x2 = x.reshape(-1, n_in)
             return linear_skinny_raw(x2 if x2.is_contiguous() else x2.contiguous(), weight_copies(weight)[0],
                                      _f32(bias)).reshape(*x.shape[:-1], n_out)
@@ -800,8 +818,7 @@ def linear(x, weight, bias=None, ln=None):
         # float32 inference on widths the panel kernel does not tile (small towers, the narrator's pooling projections,
         # round 5): the strip kernel's f32-class mode instead of the library GEMM
         rows, n_in, n_out = x.numel() // x.shape[-1], x.shape[-1], weight.shape[0]
-        if (rows > 0 and not _tn_ok_f32(rows, n_out, n_in) and n_out % 16 == 0 and n_in % 32 == 0
-                and rows * max(3 * n_in, n_out) * 4 < (1 << 31)):
+        if _skinny_f32_ok(rows, n_out, n_in):
             return linear_f32_rows(x.reshape(-1, n_in), weight_copies(weight, f32=True)[0],
                                    _f32(bias)).reshape(*x.shape[:-1], n_out)
     return _LinearFn.apply(x, weight, bias, _ln_for(ln, x))

@@ -131,10 +131,10 @@ def pad8(t):
     return torch.cat([t, t.new_zeros((-M) % 8, t.shape[1])]).contiguous(), M
 
 
-def check_random_vs_float64(kern, out, d):
+def check_random_vs_float64(kern, out, d, colsum=True):
     """gemm_tn_cases.check_random_vs_float64's bars for epilogues 1, 2, 4 (bf16) and 1, 2 (f32-class), applied to their
     GELU twins 6, 7, 8: one bf16 rounding (2^-8 relative, with margin) plus the f32 accumulation (2^-14 |x| |w|);
-    f32-class mode: 3 2^-17 |x| |w|."""
+    f32-class mode: 3 2^-17 |x| |w|. colsum=False: a window of rows of a larger call (its column sums are checked elsewhere)."""
     name, epi, f32, with_bias, aux = kern
     M = d['M']
     y = out['y'].double()
@@ -150,7 +150,8 @@ def check_random_vs_float64(kern, out, d):
         else:
             ref = acc * gelu_grad64(d['f32_u'].double())
             assert ((y - ref).abs() <= 1.6 * bound + 2e-6 * ref.abs()).all(), name
-            torch.testing.assert_close(out['colsum'].double(), ref.sum(0), atol=1e-3 * M ** 0.5, rtol=1e-4)
+            if colsum:
+                torch.testing.assert_close(out['colsum'].double(), ref.sum(0), atol=1e-3 * M ** 0.5, rtol=1e-4)
     else:
         xd, wd = d['x'].double(), d['w'].double()
         acc = xd @ wd.t()
@@ -165,19 +166,20 @@ def check_random_vs_float64(kern, out, d):
             dd = out['aux_out'].double()
             assert ((dd - gelu_grad64(u)).abs() <= 2.0 ** -8 * gelu_grad64(u).abs() + 1.2 * eps + 1e-5).all(), name
         else:
-            check_bwd_vs_float64(name, out, acc, gelu_grad64(d['u'].double()), eps)
+            check_bwd_vs_float64(name, out, acc, gelu_grad64(d['u'].double()), eps, colsum)
     for v in out.values():
         assert torch.isfinite(v.float()).all(), name
 
 
-def check_bwd_vs_float64(name, out, acc, a, eps):
+def check_bwd_vs_float64(name, out, acc, a, eps, colsum=True):
     """bf16 epilogue 7 as check_random_vs_float64 holds epilogue 2: y = acc * a rounded once, the column sums of the
     unrounded f32 products (a row dropped, doubled or taken from behind M would exceed this)."""
     ref = acc * a
     err = 1.2 * eps * a.abs() + 1e-5 * acc.abs()
     assert ((out['y'].double() - ref).abs() <= 2.0 ** -8 * ref.abs() + err).all(), name
-    cs, want = out['colsum'].double(), ref.sum(0)
-    assert ((cs - want).abs() <= 2.0 ** -12 * ref.abs().sum(0) + err.sum(0) + 1e-4).all(), name
+    if colsum:
+        cs, want = out['colsum'].double(), ref.sum(0)
+        assert ((cs - want).abs() <= 2.0 ** -12 * ref.abs().sum(0) + err.sum(0) + 1e-4).all(), name
 
 
 def ns(kern):

@@ -154,9 +154,11 @@ def int_data(N, M, seed, k_bf16, k_f32):
     return d
 
 
-def check_random_vs_float64(kern, out, d):
+def check_random_vs_float64(kern, out, d, colsum=True):
     """float64 reference of one kernel on the random operands: one bf16 rounding (2^-8 relative, with margin) plus the
-    f32 accumulation (2^-14 |x| |w|); f32-class mode: 3 2^-17 |x| |w| (test_gpu_f32_class.py)"""
+    f32 accumulation (2^-14 |x| |w|); f32-class mode: 3 2^-17 |x| |w| (test_gpu_f32_class.py). colsum=False: `out` and `d`
+    are a window of rows of a larger call; its column sums (over all rows) are checked elsewhere
+    (test_gpu_large_operands.py)."""
     name, epi, f32, with_bias, aux = kern
     M = d['M']
     y = out['y'].double()
@@ -177,7 +179,8 @@ def check_random_vs_float64(kern, out, d):
         else:
             ref = acc * _qg_grad(d['f32_u'].double())
             assert ((y - ref).abs() <= 1.6 * bound + 2e-6 * ref.abs()).all(), name
-            torch.testing.assert_close(out['colsum'].double(), ref.sum(0), atol=1e-3 * M ** 0.5, rtol=1e-4)
+            if colsum:
+                torch.testing.assert_close(out['colsum'].double(), ref.sum(0), atol=1e-3 * M ** 0.5, rtol=1e-4)
         return
     xd, wd = d['x'].double(), d['w'].double()
     acc = xd @ wd.t()
@@ -200,8 +203,9 @@ def check_random_vs_float64(kern, out, d):
         err = 1.2 * eps * a.abs() + 1e-5 * acc.abs()
         assert ((y - ref).abs() <= 2.0 ** -8 * ref.abs() + err).all(), name
         # column sums (of the unrounded f32 products): a row dropped, doubled or taken from behind M would exceed this
-        cs, want = out['colsum'].double(), ref.sum(0)
-        assert ((cs - want).abs() <= 2.0 ** -12 * ref.abs().sum(0) + err.sum(0) + 1e-4).all(), name
+        if colsum:
+            cs, want = out['colsum'].double(), ref.sum(0)
+            assert ((cs - want).abs() <= 2.0 ** -12 * ref.abs().sum(0) + err.sum(0) + 1e-4).all(), name
     for v in out.values():
         assert torch.isfinite(v.float()).all(), name
 

@@ -332,3 +332,41 @@ def split3_ref(x):
     hf = h.float()
     l = torch.where(hf.abs() <= 3.38e38, x - hf, torch.zeros_like(x)).to(torch.bfloat16)
     return h, l
+
+
+# ---- lvl_layernorm_bwd against the models above (test_gpu_rowops_at_scale.py, test_gpu_large_operands.py) ------------------
+def row_chunks(rows, cols):
+    step = max(1, (1 << 25) // max(cols, 1))
+    return [(r, min(r + step, rows)) for r in range(0, rows, step)]
+
+
+def ln_bwd_check(within, tag, dt, out, dy, x, x2, b, gamma, mean, rstd, dadd, plain):
+    """One lvl_layernorm_bwd result (out = dx, dx_plain, dgamma, dbeta, dxsum) against float64, in row chunks: dx, dx_plain
+    elementwise and dgamma / dbeta / dxsum within the error models above. within(name, got, want, bound, what): the caller's
+    assertion |got - want| <= 2 bound (test_gpu_rowops_at_scale._within records the worst ratio)."""
+    dx, dxp, dgamma, dbeta, dxsum = out
+    rows, cols = x.shape
+    n_add = (1 if x2 is not None else 0) + (1 if b is not None else 0)
+    sg, sb, sx = (torch.zeros(cols, dtype=torch.float64, device=x.device) for _ in range(3))
+    ag, ab, ax = (torch.zeros(cols, dtype=torch.float64, device=x.device) for _ in range(3))
+    eg = torch.zeros(cols, dtype=torch.float64, device=x.device)
+    for r0, r1 in row_chunks(rows, cols):
+        sl = slice(r0, r1)
+        s64 = ln_sum64(x[sl], x2[sl] if x2 is not None else None, b)
+        absum = x[sl].double().abs() + (x2[sl].double().abs() if x2 is not None else 0) + \
+            (b.double().abs() if b is not None else 0)
+        da = dadd[sl] if dadd is not None else None
+        dxp64, dx64, t64 = ln_bwd_ref(dy[sl], s64, gamma, mean[sl], rstd[sl], da)
+        ep, ex, et = ln_bwd_bounds(dy[sl], s64, absum, n_add, gamma, mean[sl], rstd[sl], da, cols, dt)
+        within(f'ln_bwd dx {str(dt)[6:]}', dx[sl], dx64, ex, tag)
+        if plain:
+            within(f'ln_bwd dx_plain {str(dt)[6:]}', dxp[sl], dxp64, ep, tag)
+        own = (dxp if plain else dx)[sl].double()         # dxsum sums the kernel's own rounded output
+        sg += t64.sum(0); ag += t64.abs().sum(0); eg += et.sum(0)
+        sb += dy[sl].double().sum(0); ab += dy[sl].double().abs().sum(0)
+        sx += own.sum(0); ax += own.abs().sum(0)
+    # column sums: f32 chains of depth D (rows per wave, LDS combine, both colsum stages): D u sum|term|
+    depth = ln_bwd_depth(rows)
+    within('ln_bwd dgamma', dgamma, sg, eg + (depth + 1) * U * ag, tag)
+    within('ln_bwd dbeta', dbeta, sb, depth * U * ab, tag)
+    within('ln_bwd dxsum', dxsum, sx, depth * U * ax, tag)

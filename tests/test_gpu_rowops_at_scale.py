@@ -220,33 +220,8 @@ def _ln_bwd_run(dy, x, x2, b, gamma, mean, rstd, dadd, plain):
 
 
 def _ln_bwd_check(tag, dt, out, dy, x, x2, b, gamma, mean, rstd, dadd, plain):
-    """dx, dx_plain elementwise and dgamma / dbeta / dxsum against float64 (error models: rowops_reference)."""
-    dx, dxp, dgamma, dbeta, dxsum = out
-    rows, cols = x.shape
-    n_add = (1 if x2 is not None else 0) + (1 if b is not None else 0)
-    sg, sb, sx = (torch.zeros(cols, dtype=torch.float64, device=DEV) for _ in range(3))
-    ag, ab, ax = (torch.zeros(cols, dtype=torch.float64, device=DEV) for _ in range(3))
-    eg = torch.zeros(cols, dtype=torch.float64, device=DEV)
-    for r0, r1 in _chunks(rows, cols):
-        sl = slice(r0, r1)
-        s64 = R.ln_sum64(x[sl], x2[sl] if x2 is not None else None, b)
-        absum = x[sl].double().abs() + (x2[sl].double().abs() if x2 is not None else 0) + \
-            (b.double().abs() if b is not None else 0)
-        da = dadd[sl] if dadd is not None else None
-        dxp64, dx64, t64 = R.ln_bwd_ref(dy[sl], s64, gamma, mean[sl], rstd[sl], da)
-        ep, ex, et = R.ln_bwd_bounds(dy[sl], s64, absum, n_add, gamma, mean[sl], rstd[sl], da, cols, dt)
-        _within(f'ln_bwd dx {str(dt)[6:]}', dx[sl], dx64, ex, tag)
-        if plain:
-            _within(f'ln_bwd dx_plain {str(dt)[6:]}', dxp[sl], dxp64, ep, tag)
-        own = (dxp if plain else dx)[sl].double()         # dxsum sums the kernel's own rounded output
-        sg += t64.sum(0); ag += t64.abs().sum(0); eg += et.sum(0)
-        sb += dy[sl].double().sum(0); ab += dy[sl].double().abs().sum(0)
-        sx += own.sum(0); ax += own.abs().sum(0)
-    # column sums: f32 chains of depth D (rows per wave, LDS combine, both colsum stages): D u sum|term|
-    depth = R.ln_bwd_depth(rows)
-    _within('ln_bwd dgamma', dgamma, sg, eg + (depth + 1) * R.U * ag, tag)
-    _within('ln_bwd dbeta', dbeta, sb, depth * R.U * ab, tag)
-    _within('ln_bwd dxsum', dxsum, sx, depth * R.U * ax, tag)
+    """dx, dx_plain elementwise and dgamma / dbeta / dxsum against float64 (rowops_reference.ln_bwd_check)."""
+    R.ln_bwd_check(_within, tag, dt, out, dy, x, x2, b, gamma, mean, rstd, dadd, plain)
 
 
 def _ln_bwd_case(variant, dt, rows, cols, seed, marks=True):
