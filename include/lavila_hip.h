@@ -56,6 +56,13 @@ int lvl_debug_late_workgroups(int mod);
  * otherwise force a whole extra round of tiles (tools/probe_cu_contention.py). Process-wide; call before sizing
  * workspaces (lvl_workspace_floats("linear_wgrad") depends on it). Nothing in the reference corresponds to it. */
 int lvl_set_compute_units(int n);
+/* MFMA shape of lvl_linear_tn's K loop for bf16 results, epilogues 0-5 (lvl_linear_tn_ragged included): 32 =
+ * v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16, 0 (default) = the library's own choice per (N, K, epilogue),
+ * taken from measurement (profiles/gemm_mfma_shape.txt). Anything else is refused with LVL_EINVAL and changes nothing.
+ * Process-wide. The f32-class mode (LVL_F32) and the exact-GELU epilogues 6-8 run on 32x32x16 whatever is set. The two
+ * shapes return the same results, bit for bit: the MFMAs of both give the same accumulators for a K block (measured on
+ * gfx950, tests/test_gpu_gemm_mfma_shape.py), and the column sums of epilogues 2 / 5 are formed in one order. */
+int lvl_set_gemm_mfma_shape(int shape);
 const char* lvl_last_error(void);
 /* number of float32 workspace elements a call needs (host-side query, no device work) */
 int64_t lvl_workspace_floats(const char* op, int64_t rows, int64_t cols);

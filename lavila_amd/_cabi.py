@@ -27,6 +27,7 @@ _U64, _U32 = _c.c_uint64, _c.c_uint32
 SIGNATURES = {
     'lvl_version': (_c.c_char_p, []),
     'lvl_set_compute_units': (_I, [_I]),
+    'lvl_set_gemm_mfma_shape': (_I, [_I]),
     'lvl_debug_late_workgroups': (_I, [_I]),
     'lvl_last_error': (_c.c_char_p, []),
     'lvl_workspace_floats': (_L, [_c.c_char_p, _L, _L]),

@@ -1,4 +1,5 @@
-// The persistent TN GEMM kernel template (gemm_tn_kernel<EPI, F32O>) and its launcher (launch_tn), described at the top of
+// The persistent TN GEMM kernel templates (gemm_tn_kernel<EPI, F32O> on v_mfma_f32_32x32x16_bf16, gemm_tn_mfma16<EPI> on
+// v_mfma_f32_16x16x32_bf16: one body, gemm_tn_body) and their launcher (launch_tn), described at the top of
 // gemm_tn_mfma.hip. A header because two translation units instantiate it: gemm_tn_mfma.hip (epilogues 0-5: every C entry
 // point and their dispatch) and gemm_tn_gelu.hip (the exact-GELU epilogues 6-8). Everything here sits in an anonymous
 // namespace: each unit gets its own instantiations.
@@ -13,6 +14,7 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 gm_bf16x8;
 typedef __attribute__((ext_vector_type(16))) float gm_f32x16;
+typedef __attribute__((ext_vector_type(4))) float gm_f32x4;
 
 namespace {
 
@@ -28,6 +30,10 @@ enum { S_X0 = 0, S_X1 = 1, S_W0 = 2, S_W1 = 3 };
 
 __device__ __forceinline__ gm_f32x16 mfma32(uint4 a, uint4 b, gm_f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gm_bf16x8, a), __builtin_bit_cast(gm_bf16x8, b),
+                                                 c, 0, 0, 0);
+}
+__device__ __forceinline__ gm_f32x4 mfma16(uint4 a, uint4 b, gm_f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gm_bf16x8, a), __builtin_bit_cast(gm_bf16x8, b),
                                                  c, 0, 0, 0);
 }
 
@@ -52,6 +58,16 @@ __device__ __forceinline__ float qgelu_grad1(float y, float r) { return fmaf((1.
 __device__ __forceinline__ uint4 widen_pair(uint2 a, uint2 b) {
   const auto r0 = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
   const auto r1 = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
+  return make_uint4(r0[0], r1[0], r0[1], r1[1]);
+}
+// The same for the 16x16x32 accumulator map: the four 16-lane groups g = lane >> 4 hold four adjacent 8-byte pieces
+// (columns 4g .. 4g+3) of one output row, for two neighbouring 16-column groups `a` and `b`. permlane16_swap exchanges
+// the odd 16-lane groups of its first operand with the even ones of its second: group 0 ends with columns 0-7 of a,
+// group 1 with columns 0-7 of b, group 2 with columns 8-15 of a, group 3 with columns 8-15 of b -- 16 contiguous bytes
+// at column (g & 1) * 16 + (g >> 1) * 8 of the 32.
+__device__ __forceinline__ uint4 widen_quad(uint2 a, uint2 b) {
+  const auto r0 = __builtin_amdgcn_permlane16_swap(a.x, b.x, false, false);
+  const auto r1 = __builtin_amdgcn_permlane16_swap(a.y, b.y, false, false);
   return make_uint4(r0[0], r1[0], r0[1], r1[1]);
 }
 
@@ -100,14 +116,18 @@ __device__ __forceinline__ int gm_wave_max(int v) {
 #define GM_AUD_COLPART() ((void)0)
 #endif
 
-template <int EPI, bool F32O>
-__global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
-                                                      const float* __restrict__ bias, void* __restrict__ Yv,
-                                                      void* __restrict__ aux_out_v,
-                                                      const void* __restrict__ aux_in_v,
-                                                      float* __restrict__ colpart, int64_t M, int N, int K,
-                                                      int tiles_n, int ntiles, unsigned* __restrict__ sched,
-                                                      int late_mod) {
+// The kernel body; MS = the MFMA shape of the K loop: 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (bf16
+// results only). The shape changes three things and nothing else -- which rows and chunks a fragment read takes, the
+// MFMAs of a phase (16 instead of 8 for the same 64 x 32 x 64 quadrant; the read and refill slots ride behind every
+// second one), and the accumulator map the epilogue and the bias initialisation follow: tile walk, ring, fills, swizzle,
+// barriers, allowances, schedules and audit are the same text. The two __global__ wrappers are behind it.
+template <int EPI, bool F32O, int MS>
+__device__ __forceinline__ void gemm_tn_body(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
+                                             const float* __restrict__ bias, void* __restrict__ Yv,
+                                             void* __restrict__ aux_out_v, const void* __restrict__ aux_in_v,
+                                             float* __restrict__ colpart, int64_t M, int N, int K, int tiles_n,
+                                             int ntiles, unsigned* __restrict__ sched, int late_mod) {
+  static_assert(MS == 32 || (MS == 16 && !F32O), "MFMA shape: 32x32x16, or 16x16x32 for the bf16 results");
   using out_t = std::conditional_t<F32O, float, uint16_t>;      // element type of y / aux_out / aux_in
   out_t* __restrict__ const Y = static_cast<out_t*>(Yv);
   out_t* __restrict__ const aux_out = static_cast<out_t*>(aux_out_v);
@@ -293,32 +313,71 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   // ---- fragment addresses -----------------------------------------------------------------------------------------
   // 32x32x16 operand: lane l carries row (l & 31), contraction elements 8*(l>>5) .. +7 of the K=16 slice kk, i.e.
   // logical chunk 2*kk + (l>>5) of the row's eight 16-byte chunks.
-  const int r5 = lane & 31, hi = lane >> 5;
+  // 16x16x32 operand: lane l carries row (l & 15), contraction elements 8*(l>>4) .. +7 of the K=32 slice ks, i.e. logical
+  // chunk 4*ks + (l>>4). A wave's share of a slot is the same 8 X / 4 W fragments: X fragment ks*4 + rg = rows 16 rg .. +15
+  // of its 64, W fragment ks*2 + cg = rows 16 cg .. +15 of its 32.
+  // SWIZZLE, both shapes: physical chunk = logical chunk ^ ((row>>1) & 7). A ds_read_b128 is served in four groups of 16
+  // lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- and a group is conflict-free when its 16 lanes
+  // hit 16 different 16-byte columns of the 256-byte bank row, column = 8 (row & 1) + physical chunk: the 8 rows of one
+  // parity need 8 different physical chunks. 32x32x16: a group is 16 consecutive rows of one logical chunk c; per parity
+  // (row>>1) & 7 takes all 8 values, so does c ^ it. 16x16x32: a group is rows 0-3 and 12-15 with logical chunk c and rows
+  // 4-11 with c ^ 1, or the other way round (lanes 16 apart differ in bit 0 of l>>4; the upper two groups: c ^ 2, c ^ 3); per parity
+  // q = (row>>1) & 7 is {0, 1, 6, 7} under c and {2, 3, 4, 5} under c ^ 1, physical chunks c ^ {0, 1, 6, 7} and
+  // c ^ {3, 2, 5, 4}: all 8 again. The fill side is therefore the same for both shapes. (Without the swizzle, or with a
+  // swizzle on bits the lane groups do not separate, this read is 2-way.)
+  const int r5 = MS == 16 ? lane & 15 : lane & 31, hi = MS == 16 ? lane >> 4 : lane >> 5;
   const int r5_ = r5, hi_ = hi;
   uint32_t xa[4], wa[4];
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const int offk = ((2 * kk + hi) ^ ((r5 >> 1) & 7)) * 16;
+  for (int kk = 0; kk < (MS == 16 ? 2 : 4); ++kk) {
+    const int offk = (((MS == 16 ? 4 : 2) * kk + hi) ^ ((r5 >> 1) & 7)) * 16;
     xa[kk] = (uint32_t)((wm * 64 + r5) * 128 + offk);
     wa[kk] = (uint32_t)((wn * 32 + r5) * 128 + offk);
   }
+  // slot byte offset of the lane's share of X fragment k (0..7) / W fragment k (0..3)
+  auto x_off = [&](int k) { return MS == 16 ? xa[k >> 2] + (k & 3) * 2048 : xa[k & 3] + (k >> 2) * 4096; };
+  auto w_off = [&](int k) { return MS == 16 ? wa[k >> 1] + (k & 1) * 2048 : wa[k]; };
   auto read_x = [&](int slot, uint4 (&xf)[8]) {
     const uint8_t* b = smem + slot * SLOT;
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) xf[mt * 4 + kk] = *reinterpret_cast<const uint4*>(b + xa[kk] + mt * 4096);
+    for (int k = 0; k < 8; ++k) xf[k] = *reinterpret_cast<const uint4*>(b + x_off(k));
   };
   auto read_w = [&](int slot, uint4 (&wf)[4]) {
     const uint8_t* b = smem + slot * SLOT;
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) wf[kk] = *reinterpret_cast<const uint4*>(b + wa[kk]);
+    for (int kk = 0; kk < 4; ++kk) wf[kk] = *reinterpret_cast<const uint4*>(b + w_off(kk));
   };
 
   gm_f32x16 acc[2][2][2];           // [qm][qn][mt]
+  gm_f32x4 acc4[2][2][4][2];        // MS == 16: [qm][qn][rg][cg], 16 rows x 16 columns each (the same 128 registers)
   // The accumulators of tile ti START as the tile's bias (read straight from its LDS image into the accumulator
   // registers: no VALU work), so the epilogue has no bias add; without a bias they start at zero.
   auto init_acc = [&](int ti) {
+    if constexpr (MS == 16) {
+      // accumulator [rg][cg] of column group qn: the lane holds columns qn*32 + cg*16 + 4*hi .. +3 of row rg*16 + r5
+      if (EPI != 2 && bias != nullptr) {
+        const uint8_t* bias_img = smem + BIAS_OFF + (ti & 3) * 1024;
+        GM_AUD(if (wave == 0) aud_check(aud_bias_get(ti), GM_CHK_BIAS);)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int cg = 0; cg < 2; ++cg) {
+            const float4 b = *reinterpret_cast<const float4*>(bias_img + (wn * 64 + i * 32 + cg * 16 + 4 * hi) * 4);
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+              acc4[a >> 2][i][a & 3][cg][0] = b.x;
+              acc4[a >> 2][i][a & 3][cg][1] = b.y;
+              acc4[a >> 2][i][a & 3][cg][2] = b.z;
+              acc4[a >> 2][i][a & 3][cg][3] = b.w;
+            }
+          }
+      } else {
+#pragma unroll
+        for (int a = 0; a < 32; ++a)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc4[a >> 4][(a >> 3) & 1][(a >> 1) & 3][a & 1][r] = 0.f;
+      }
+    } else
     if (EPI != 2 && EPI != 7 && bias != nullptr) {
       const uint8_t* bias_img = smem + BIAS_OFF + (ti & 3) * 1024;
       GM_AUD(if (wave == 0) aud_check(aud_bias_get(ti), GM_CHK_BIAS);)
@@ -360,11 +419,82 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     constexpr bool COLSUM = EPI == 2 || EPI == 5 || EPI == 7;                 // column sums of y leave as a partial slab
     constexpr bool AUXIN = EPI == 2 || EPI == 3 || EPI == 5 || EPI == 7;      // an aux_in row rides with every result row
     constexpr bool TWO_OUT = EPI == 1 || EPI == 4 || EPI == 6 || EPI == 8;
-    float csum[COLSUM ? 32 : 1];          // value c = column (c>>4)*32 + ((c>>2)&3)*8 + 4*hi + (c&3) of the wave's 64
+    // value c = column (c>>4)*32 + ((c>>2)&3)*8 + 4*hi + (c&3) of the wave's 64. MS == 16: a lane holds 16 of the 64
+    // columns, but two rows of every 32-row group (h*16 + r5): value h*16 + c = column (c>>3)*32 + ((c>>2)&1)*16 + 4*hi +
+    // (c&3) of the rows of half h. Kept apart per half, so that the sums are formed in the ORDER of the 32x32x16 map -- per
+    // row of the 32 first over the four row groups, then rows r and r + 16, then the butterfly over 16 lanes -- and the
+    // column sums of the two shapes are the same floats, not only the same to rounding.
+    constexpr int NCS = 32;
+    float csum[COLSUM ? NCS : 1];
     if (COLSUM) {
 #pragma unroll
-      for (int c = 0; c < 32; ++c) csum[c] = 0.f;
+      for (int c = 0; c < NCS; ++c) csum[c] = 0.f;
     }
+    // One accumulator quad -- 4 consecutive output columns of one row, v -- through the epilogue's arithmetic: the packed
+    // bf16 result comes back, the second output of the two-output epilogues goes to upk; ab = the lane's 8 bytes of the
+    // aux_in row, rowv = 0 for a row behind M, ci = the quad's first column-sum value.
+    auto finish_quad = [&](float (&v)[4], const uint2 ab, const float rowv, const int ci, uint2& upk) -> uint2 {
+      if (EPI == 1) {
+        upk = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
+        // the activation sees the ROUNDED pre-activation (what the reference's bf16 Linear output holds and
+        // what the backward reads back)
+        float r;
+        qgelu1(bf16_lo(upk.x), v[0], r);
+        qgelu1(bf16_hi(upk.x), v[1], r);
+        qgelu1(bf16_lo(upk.y), v[2], r);
+        qgelu1(bf16_hi(upk.y), v[3], r);
+      }
+      if (EPI == 6) {                // epilogue 1 with the exact GELU (gelu_erf.h), on the ROUNDED pre-activation too
+        upk = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
+        v[0] = gelu_erf(bf16_lo(upk.x));
+        v[1] = gelu_erf(bf16_hi(upk.x));
+        v[2] = gelu_erf(bf16_lo(upk.y));
+        v[3] = gelu_erf(bf16_hi(upk.y));
+      }
+      if (EPI == 8) {                // y = gelu(u), aux_out = gelu'(u) = Phi(u) + u phi(u): one erf serves both
+        float g[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gelu_erf_pair(v[e], v[e], g[e]);
+        upk = make_uint2(f32x2_to_bf16x2(g[0], g[1]), f32x2_to_bf16x2(g[2], g[3]));
+      }
+      if (EPI == 4) {                // y = quickgelu(u), aux_out = quickgelu'(u): one exp2 + one rcp serve both
+        float g[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float y, r;
+          qgelu1(v[e], y, r);
+          g[e] = qgelu_grad1(y, r);
+          v[e] = y;
+        }
+        upk = make_uint2(f32x2_to_bf16x2(g[0], g[1]), f32x2_to_bf16x2(g[2], g[3]));
+      }
+      if (AUXIN) {
+        const float a4[4] = {bf16_lo(ab.x), bf16_hi(ab.x), bf16_lo(ab.y), bf16_hi(ab.y)};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (EPI == 3) v[e] += a4[e];        // + the residual row (bf16), in f32 before the one rounding of the sum
+          if (EPI == 5) v[e] *= a4[e];        // the forward left quickgelu'(u) itself
+          if (EPI == 2) {
+            float y, r;
+            qgelu1(a4[e], y, r);
+            v[e] *= qgelu_grad1(y, r);
+          }
+          if (EPI == 7) v[e] *= gelu_erf_grad(a4[e]);
+        }
+      }
+      if (COLSUM) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) csum[ci + e] = fmaf(v[e], rowv, csum[ci + e]);
+        // erff's branches cut the epilogue into basic blocks, and the compiler then sinks the whole chain of these
+        // fmas into the last one -- four row groups of products stay live instead of 32 sums (15 VGPRs spilled): the sum
+        // is made opaque here, per accumulator quad, so it is formed here
+        if (EPI == 7) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(csum[ci + e]));
+        }
+      }
+      return make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
+    };
     if constexpr (F32O) {
       // float32 results (f32-class mode): an accumulator quad IS 4 consecutive output columns of one row -> one
       // 16-byte store per quad (and one 16-byte aux access for the QuickGELU epilogues); same arithmetic as below
@@ -432,12 +562,22 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     constexpr int HOLD = UPFRONT == 4 ? 1 : 2;
     uint2 ub[AUXIN ? 4 : 1][8];
     auto load_u = [&](int j, uint2 (&dst)[8]) {
+      if constexpr (MS == 16) {       // [h*4 + qn*2 + cg]: the lane's 8 bytes of row h*16 + r5 in every 16-column group
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int64_t m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + h * 16 + r5;
+          const uint16_t* urow = reinterpret_cast<const uint16_t*>(aux_in) + (m < M ? m : M - 1) * (int64_t)N + n0 + wn * 64 + 4 * hi;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dst[h * 4 + q] = *reinterpret_cast<const uint2*>(urow + 16 * q);
+        }
+      } else {
       const int64_t m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + r5;
       const uint16_t* urow = reinterpret_cast<const uint16_t*>(aux_in) + (m < M ? m : M - 1) * (int64_t)N + n0 + wn * 64 + 4 * hi;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) dst[i * 4 + rq] = *reinterpret_cast<const uint2*>(urow + i * 32 + 8 * rq);
+      }
     };
     auto landed = [&](const uint2 (&src)[8]) {
 #pragma unroll
@@ -449,9 +589,29 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       __builtin_amdgcn_sched_barrier(0);
     }
     uint4 yv[AUXIN ? HOLD : 1][2][2], uv[2][2];      // [row group][qn][jj]: 16 bytes = columns qn*32 + 16*jj + 8*hi .. +7 of row r5
+    // MS == 16: [row group][h][qn]: 16 bytes = columns qn*32 + (hi&1)*16 + (hi>>1)*8 .. +7 of row h*16 + r5 (widen_quad)
     auto store_group = [&](int j, const uint4 (&y4)[2][2]) {
       // 16-byte stores: lower lanes take columns 16*jj .. +7, upper lanes 16*jj + 8 .. +15 of a column group
       // (an LDS-staged variant that leaves as full 128-byte lines measured no faster: the tail is not line-bound)
+      if constexpr (MS == 16) {
+        // the row guard is per 16-row group: the same 4 (8) stores per 32 rows, from two guarded halves
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int64_t m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + h * 16 + r5;
+          if (m < M) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              const int64_t o = m * (int64_t)N + n0 + wn * 64 + i * 32 + (hi & 1) * 16 + (hi >> 1) * 8;
+              gm_store16(Y + o, y4[h][i]);
+              GM_AUD_STORE(j);
+              if (TWO_OUT) {
+                gm_store16(aux_out + o, uv[h][i]);
+                GM_AUD_STORE(j);
+              }
+            }
+          }
+        }
+      } else {
       const int64_t m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + r5;
       if (m < M) {
 #pragma unroll
@@ -467,12 +627,36 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
             }
           }
       }
+      }
     };
 #pragma unroll
     for (int j = 0; j < 4; ++j) {          // row group (qm, mt): 32 rows
       const int64_t mg = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32;
       const float rowv = mg + r5 < M ? 1.f : 0.f;      // rows behind M (tail tile) stay out of the column sums
       uint4 (&y4)[2][2] = yv[AUXIN && j < HOLD ? j : 0];
+      if constexpr (MS == 16) {
+        // two 16-row groups h; per column group qn two accumulators cg of 16 columns, one quad each
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float rowh = mg + h * 16 + r5 < M ? 1.f : 0.f;
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            uint2 ypk[2], upk[2];
+#pragma unroll
+            for (int cg = 0; cg < 2; ++cg) {
+              const gm_f32x4& a4 = acc4[j >> 1][i][(j & 1) * 2 + h][cg];
+              float v[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = a4[e];
+              uint2 ab = make_uint2(0u, 0u);
+              if (AUXIN) ab = ub[j][h * 4 + i * 2 + cg];
+              ypk[cg] = finish_quad(v, ab, rowh, h * 16 + i * 8 + cg * 4, upk[cg]);
+            }
+            y4[h][i] = widen_quad(ypk[0], ypk[1]);
+            if (TWO_OUT) uv[h][i] = widen_quad(upk[0], upk[1]);
+          }
+        }
+      } else {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {        // column group qn
         const gm_f32x16& a16 = acc[j >> 1][i][j & 1];
@@ -482,73 +666,16 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = a16[4 * rq + e];
-          if (EPI == 1) {
-            upk[rq] = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
-            // the activation sees the ROUNDED pre-activation (what the reference's bf16 Linear output holds and
-            // what the backward reads back)
-            float r;
-            qgelu1(bf16_lo(upk[rq].x), v[0], r);
-            qgelu1(bf16_hi(upk[rq].x), v[1], r);
-            qgelu1(bf16_lo(upk[rq].y), v[2], r);
-            qgelu1(bf16_hi(upk[rq].y), v[3], r);
-          }
-          if (EPI == 6) {                // epilogue 1 with the exact GELU (gelu_erf.h), on the ROUNDED pre-activation too
-            upk[rq] = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
-            v[0] = gelu_erf(bf16_lo(upk[rq].x));
-            v[1] = gelu_erf(bf16_hi(upk[rq].x));
-            v[2] = gelu_erf(bf16_lo(upk[rq].y));
-            v[3] = gelu_erf(bf16_hi(upk[rq].y));
-          }
-          if (EPI == 8) {                // y = gelu(u), aux_out = gelu'(u) = Phi(u) + u phi(u): one erf serves both
-            float g[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) gelu_erf_pair(v[e], v[e], g[e]);
-            upk[rq] = make_uint2(f32x2_to_bf16x2(g[0], g[1]), f32x2_to_bf16x2(g[2], g[3]));
-          }
-          if (EPI == 4) {                // y = quickgelu(u), aux_out = quickgelu'(u): one exp2 + one rcp serve both
-            float g[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              float y, r;
-              qgelu1(v[e], y, r);
-              g[e] = qgelu_grad1(y, r);
-              v[e] = y;
-            }
-            upk[rq] = make_uint2(f32x2_to_bf16x2(g[0], g[1]), f32x2_to_bf16x2(g[2], g[3]));
-          }
-          if (AUXIN) {
-            const uint2 ab = ub[j][i * 4 + rq];
-            const float a4[4] = {bf16_lo(ab.x), bf16_hi(ab.x), bf16_lo(ab.y), bf16_hi(ab.y)};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              if (EPI == 3) v[e] += a4[e];        // + the residual row (bf16), in f32 before the one rounding of the sum
-              if (EPI == 5) v[e] *= a4[e];        // the forward left quickgelu'(u) itself
-              if (EPI == 2) {
-                float y, r;
-                qgelu1(a4[e], y, r);
-                v[e] *= qgelu_grad1(y, r);
-              }
-              if (EPI == 7) v[e] *= gelu_erf_grad(a4[e]);
-            }
-          }
-          if (COLSUM) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) csum[i * 16 + rq * 4 + e] = fmaf(v[e], rowv, csum[i * 16 + rq * 4 + e]);
-            // erff's branches cut the epilogue into basic blocks, and the compiler then sinks the whole chain of these
-            // fmas into the last one -- four row groups of products stay live instead of 32 sums (15 VGPRs spilled): the sum
-            // is made opaque here, per accumulator quad, so it is formed here
-            if (EPI == 7) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(csum[i * 16 + rq * 4 + e]));
-            }
-          }
-          ypk[rq] = make_uint2(f32x2_to_bf16x2(v[0], v[1]), f32x2_to_bf16x2(v[2], v[3]));
+          uint2 ab = make_uint2(0u, 0u);
+          if (AUXIN) ab = ub[j][i * 4 + rq];
+          ypk[rq] = finish_quad(v, ab, rowv, i * 16 + rq * 4, upk[rq]);
         }
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
           y4[i][jj] = widen_pair(ypk[2 * jj], ypk[2 * jj + 1]);
           if (TWO_OUT) uv[i][jj] = widen_pair(upk[2 * jj], upk[2 * jj + 1]);
         }
+      }
       }
       if constexpr (AUXIN) {
         if (j == 0 && UPFRONT < 4) {
@@ -580,14 +707,21 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     }
     if (COLSUM) {
       // column sums over the wave's 128 rows: 32 values per lane, summed over the 32 lanes of each half-wave by a
-      // halving butterfly (31 exchanges): lane r5 ends up with the total of value index c = r5
-      float (&cs)[COLSUM ? 32 : 1] = csum;
-      int cnt2 = 16;
+      // halving butterfly (31 exchanges): lane r5 ends up with the total of value index c = r5. MS == 16: the exchange
+      // over mask 16 (rows r and r + 16) is the add of the lane's own two halves, the other 15 exchanges run over the 16
+      // lanes of each quarter-wave.
+      float (&cs)[COLSUM ? NCS : 1] = csum;
+      int cnt2 = NCS / 2;
+      if constexpr (MS == 16) {
 #pragma unroll
-      for (int mask = 16; mask >= 1; mask >>= 1) {
+        for (int c = 0; c < 16; ++c) cs[c] = cs[c] + cs[c + 16];
+        cnt2 = 8;
+      }
+#pragma unroll
+      for (int mask = MS == 16 ? 8 : 16; mask >= 1; mask >>= 1) {
         const bool up = (lane & mask) != 0;
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < NCS / 2; ++c) {
           if (c < cnt2) {
             const float lo = cs[c], hv = cs[c + cnt2];
             const float send = up ? lo : hv, keep = up ? hv : lo;
@@ -597,7 +731,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
         cnt2 >>= 1;
       }
       const int c = r5;
-      const int col = (c >> 4) * 32 + ((c >> 2) & 3) * 8 + 4 * hi + (c & 3);
+      const int col = MS == 16 ? (c >> 3) * 32 + ((c >> 2) & 1) * 16 + 4 * hi + (c & 3)
+                               : (c >> 4) * 32 + ((c >> 2) & 3) * 8 + 4 * hi + (c & 3);
       colpart[(size_t)(tm * 2 + wm) * N + n0 + wn * 64 + col] = cs[0];
       GM_AUD_COLPART();
     }
@@ -676,7 +811,7 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     __builtin_amdgcn_sched_barrier(0);                                \
   } while (0)
   // 8 MFMAs; after MFMA k: rd(k) (one fragment read) and dm(k) (one refill DMA or nothing)
-#define GM_PHASE(xf, wf, c, rd, dm)                                                                       \
+#define GM_PHASE32(xf, wf, c, rd, dm)                                                                     \
   do {                                                                                                    \
     _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) {                                                    \
       _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) {                                                  \
@@ -687,6 +822,28 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
         __builtin_amdgcn_sched_barrier(0);                                                                \
       }                                                                                                   \
     }                                                                                                     \
+  } while (0)
+  // MS == 16: 16 MFMAs of half the cycles each; slot s = 0..7 is two of them and rd(s) / dm(s) ride behind the second, so a
+  // phase carries the reads and refills of GM_PHASE32 at the same places in time. Slot s multiplies W fragment s >> 1
+  // (K = 32 slice s >> 2, 16 columns cg = (s >> 1) & 1) with the X fragments of row groups 2 (s & 1), 2 (s & 1) + 1 of that
+  // slice: W fragment kk has been used for the last time behind slot 2 kk + 1, as rd_w0 needs it.
+#define GM_PHASE16(xf, wf, c, rd, dm)                                                                     \
+  do {                                                                                                    \
+    _Pragma("unroll") for (int s = 0; s < 8; ++s) {                                                       \
+      _Pragma("unroll") for (int h = 0; h < 2; ++h) {                                                     \
+        const int rg = (s & 1) * 2 + h, cg = (s >> 1) & 1;                                                \
+        c[rg][cg] = mfma16(wf[s >> 1], xf[(s >> 2) * 4 + rg], c[rg][cg]);                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                \
+      }                                                                                                   \
+      rd(s);                                                                                              \
+      dm(s);                                                                                              \
+      __builtin_amdgcn_sched_barrier(0);                                                                  \
+    }                                                                                                     \
+  } while (0)
+#define GM_PHASE(xf, wf, qm, qn, rd, dm)                                  \
+  do {                                                                    \
+    if constexpr (MS == 16) GM_PHASE16(xf, wf, acc4[qm][qn], rd, dm);     \
+    else GM_PHASE32(xf, wf, acc[qm][qn], rd, dm);                         \
   } while (0)
   GM_BAR(12, (aud_slot(GM_CHK_OPEN_X0, S_X0, 0), aud_slot(GM_CHK_OPEN_W0, S_W0, 0)));      // X0 and W0 of block 0 have landed
   read_x(S_X0, xA);
@@ -719,11 +876,11 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
     constexpr int A0 = decltype(a0_)::value, A1 = decltype(a1_)::value;
     const uint8_t* sb = smem + par * SLOT;
     const uint8_t* sbn = smem + (par ^ 4) * SLOT;
-    auto rd_w1 = [&](int k) { if (k < 4) wB[k] = *reinterpret_cast<const uint4*>(sb + S_W1 * SLOT + wa[k]); };
-    auto rd_x1 = [&](int k) { xB[k] = *reinterpret_cast<const uint4*>(sb + S_X1 * SLOT + xa[k & 3] + (k >> 2) * 4096); };
-    auto rd_x0 = [&](int k) { xA[k] = *reinterpret_cast<const uint4*>(sbn + S_X0 * SLOT + xa[k & 3] + (k >> 2) * 4096); };
+    auto rd_w1 = [&](int k) { if (k < 4) wB[k] = *reinterpret_cast<const uint4*>(sb + S_W1 * SLOT + w_off(k)); };
+    auto rd_x1 = [&](int k) { xB[k] = *reinterpret_cast<const uint4*>(sb + S_X1 * SLOT + x_off(k)); };
+    auto rd_x0 = [&](int k) { xA[k] = *reinterpret_cast<const uint4*>(sbn + S_X0 * SLOT + x_off(k)); };
     // W0 of the next block: fragment kk is free once both MFMAs of step kk have been issued (k = 2*kk + 1)
-    auto rd_w0 = [&](int k) { if (k & 1) wA[k >> 1] = *reinterpret_cast<const uint4*>(sbn + S_W0 * SLOT + wa[k >> 1]); };
+    auto rd_w0 = [&](int k) { if (k & 1) wA[k >> 1] = *reinterpret_cast<const uint4*>(sbn + S_W0 * SLOT + w_off(k >> 1)); };
     auto dm_none = [&](int) {};
     auto dm_x0w0 = [&](int k) {
       if (k == 0) issue_fill(S_X0, par, 0);
@@ -740,13 +897,13 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
       if (k == 4) issue_fill(S_X1, par, 1);
     };
     GM_BAR(10 + A0, aud_slot(GM_CHK_P0_W1, S_W1, par));
-    GM_PHASE(xA, wA, acc[0][0], rd_w1, dm_none);
+    GM_PHASE(xA, wA, 0, 0, rd_w1, dm_none);
     GM_BAR(8 + A0, aud_slot(GM_CHK_P1_X1, S_X1, par));
-    GM_PHASE(xA, wB, acc[0][1], rd_x1, dm_x0w0);
+    GM_PHASE(xA, wB, 0, 1, rd_x1, dm_x0w0);
     GM_BAR(10 + A1, aud_slot(GM_CHK_P2_X0, S_X0, par ^ 4));
-    GM_PHASE(xB, wB, acc[1][1], rd_x0, dm_w1);
+    GM_PHASE(xB, wB, 1, 1, rd_x0, dm_w1);
     GM_BAR(10 + A1, aud_slot(GM_CHK_P3_W0, S_W0, par ^ 4));
-    GM_PHASE(xB, wA, acc[1][0], rd_w0, dm_x1);
+    GM_PHASE(xB, wA, 1, 0, rd_w0, dm_x1);
     fetch_advance();
     par ^= 4;
   };
@@ -825,6 +982,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   }
 #undef GM_BAR
 #undef GM_PHASE
+#undef GM_PHASE16
+#undef GM_PHASE32
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // drain the run-ahead fills before this workgroup's LDS is freed
 #ifdef GM_AUDIT
   if (lane == 0) {
@@ -847,13 +1006,35 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const uint16_t* __restrict
   }
 }
 
+// The two kernels over the one body. The 16x16x32 instantiations carry a name of their own (and exist for the bf16 results of
+// epilogues 0-5 only: gemm_tn_mfma.hip's dispatch); the f32-class mode and the exact-GELU unit stay on 32x32x16.
+#define GM_KERNEL_ARGS                                                                                              \
+  const uint16_t *__restrict__ X, const uint16_t *__restrict__ W, const float *__restrict__ bias, void *__restrict__ Yv, \
+      void *__restrict__ aux_out_v, const void *__restrict__ aux_in_v, float *__restrict__ colpart, int64_t M, int N, int K, \
+      int tiles_n, int ntiles, unsigned *__restrict__ sched, int late_mod
+template <int EPI, bool F32O>
+__global__ __launch_bounds__(512) void gemm_tn_kernel(GM_KERNEL_ARGS) {
+  gemm_tn_body<EPI, F32O, 32>(X, W, bias, Yv, aux_out_v, aux_in_v, colpart, M, N, K, tiles_n, ntiles, sched, late_mod);
+}
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_tn_mfma16(GM_KERNEL_ARGS) {
+  gemm_tn_body<EPI, false, 16>(X, W, bias, Yv, aux_out_v, aux_in_v, colpart, M, N, K, tiles_n, ntiles, sched, late_mod);
+}
+#undef GM_KERNEL_ARGS
+template <int EPI, bool F32O, int MS>
+constexpr auto tn_kernel() {
+  if constexpr (MS == 16) return &gemm_tn_mfma16<EPI>;
+  else return &gemm_tn_kernel<EPI, F32O>;
+}
+
 int num_cus() { return lvl_persistent_cus(); }      // one persistent workgroup per compute unit
 
-template <int EPI, bool F32O = false>
+template <int EPI, bool F32O = false, int MS = 32>
 int launch_tn(const void* x, const void* w, const float* bias, void* y, void* aux_out, const void* aux_in,
               float* colpart, int64_t M, int N, int K, unsigned* sched, hipStream_t st) {
   constexpr int shmem = SMEM_B;
-  const int rc = lvl_allow_lds<gemm_tn_kernel<EPI, F32O>>();
+  constexpr auto kernel = tn_kernel<EPI, F32O, MS>();
+  const int rc = lvl_allow_lds<kernel>();
   if (rc != LVL_OK) return rc;
   const int tiles_n = N / TN;
   const int64_t tiles_m = (M + TM - 1) / TM;
@@ -862,7 +1043,7 @@ int launch_tn(const void* x, const void* w, const float* bias, void* y, void* au
   int grid = (int)(ntiles < num_cus() ? ntiles : num_cus());
   if (grid >= 8) grid -= grid % 8;          // whole XCD rounds (the kernel maps workgroup b to XCD b % 8)
   if (K / BK < DYN_MIN_NB) sched = nullptr; // too few K blocks per tile for the counter hand-off: static schedule
-  hipLaunchKernelGGL((gemm_tn_kernel<EPI, F32O>), dim3((unsigned)grid), dim3(512), shmem, st, (const uint16_t*)x,
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(512), shmem, st, (const uint16_t*)x,
                      (const uint16_t*)w, bias, y, aux_out, aux_in, colpart, M,
                      N, K, tiles_n, (int)ntiles, sched, sched ? lvl_debug_late_mod() : 0);
   LVL_CHECK_LAUNCH("linear_tn");

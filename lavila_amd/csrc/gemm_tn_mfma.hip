@@ -50,6 +50,13 @@
 //   * v_mfma_f32_32x32x16_bf16 with SWAPPED operands (A = weight rows, B = activation rows): the accumulator then
 //     holds, per lane, 4 consecutive output columns of one row, so bias / activation / aux tensors are read and
 //     written as 8- and 16-byte vectors without an LDS transpose of the tile;
+//   * MFMA SHAPE. The bf16 epilogues 0-5 also exist on v_mfma_f32_16x16x32_bf16 (gemm_tn_mfma16<EPI>, the same body with
+//     MS = 16): the same 128x64 block per wave as 8 x 4 accumulators of 16 x 16, twice the MFMAs at half the cycles, the
+//     same 24 fragment reads, fills, barriers and waits per K block, the same operand swap (a lane holds 4 consecutive
+//     columns of row lane & 15; the four 16-lane groups hold adjacent 8-byte pieces of a row and permlane16_swap widens
+//     them to the same 16 16-byte stores per wave). The loop is bound by the clock the chip holds under MFMA load, and it
+//     holds a higher one on this shape (profiles/gemm_mfma_shape.txt); which shape a launch takes: mfma_shape() below,
+//     lvl_set_gemm_mfma_shape. The f32-class mode and the exact-GELU unit stay on 32x32x16;
 //   * K is walked in blocks of 64 (one 128-byte line per operand row). The 128 KiB of LDS are a ring of 8 SLOTS of
 //     128 rows x 128 B: a K block is four slots (X rows 0-127 | X rows 128-255 | W half 0 | W half 1), two blocks are
 //     resident. LDS is only a transit buffer: a wave's share of a slot is read ONCE into registers (X: 64 rows = 8
@@ -85,6 +92,30 @@
 // no column mask and gets none: it sits at 248-252 VGPRs, and its K-loop waits COUNT the epilogue's stores (NS below),
 // which a sometimes-skipped store would break.
 #include "gemm_tn_kernel.h"
+
+// ---- MFMA shape of the bf16 launches (epilogues 0-5) -------------------------------------------------------------------
+// 0 = the table below; 16 / 32 force a shape (lvl_set_gemm_mfma_shape: the tests run every check under both, the probes
+// time both). The GM_AUDIT build compiles this file alone and so carries the same setter and the same table.
+static std::atomic<int> g_mfma_shape{0};
+extern "C" int lvl_set_gemm_mfma_shape(int shape) {
+  if (shape != 0 && shape != 16 && shape != 32)
+    return lvl_fail(LVL_EINVAL, "set_gemm_mfma_shape: %d is not 0 (default), 16 or 32", shape);
+  g_mfma_shape.store(shape, std::memory_order_relaxed);
+  return LVL_OK;
+}
+// The default, from interleaved timings of both shapes on random data at the step's shapes (profiles/gemm_mfma_shape.txt):
+// v_mfma_f32_16x16x32_bf16 for every (N, K, epilogue) -- the table is this one line.
+static int mfma_shape(int /*epilogue*/, int /*N*/, int /*K*/) {
+  const int forced = g_mfma_shape.load(std::memory_order_relaxed);
+  return forced ? forced : 16;
+}
+template <int EPI>
+static int launch_bf16(const void* x, const void* w, const float* bias, void* y, void* aux_out, const void* aux_in,
+                       float* colpart, int64_t M, int N, int K, unsigned* sched, hipStream_t st) {
+  if (mfma_shape(EPI, N, K) == 16)
+    return launch_tn<EPI, false, 16>(x, w, bias, y, aux_out, aux_in, colpart, M, N, K, sched, st);
+  return launch_tn<EPI>(x, w, bias, y, aux_out, aux_in, colpart, M, N, K, sched, st);
+}
 
 int64_t lvl_linear_tn_workspace_floats(int64_t M, int64_t N) {
   return (2 * ((M + TM - 1) / TM) + lvl_colsum_mid_rows()) * N;      // column partials + the reducer's intermediate rows
@@ -130,12 +161,12 @@ extern "C" int lvl_linear_tn_audit(const void* x, const void* w, const float* bi
     return -1;
   }
   switch (epilogue) {
-    case 0: return launch_tn<0>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
-    case 1: return launch_tn<1>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
-    case 2: return launch_tn<2>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
-    case 3: return launch_tn<3>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
-    case 4: return launch_tn<4>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
-    case 5: return launch_tn<5>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
+    case 0: return launch_bf16<0>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
+    case 1: return launch_bf16<1>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
+    case 2: return launch_bf16<2>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
+    case 3: return launch_bf16<3>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
+    case 4: return launch_bf16<4>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
+    case 5: return launch_bf16<5>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
   }
   return -1;
 }
@@ -197,28 +228,28 @@ extern "C" int lvl_linear_tn(const void* x, const void* w, const float* bias, vo
   }
   switch (epilogue) {
     case LVL_EPI_BIAS:
-      return launch_tn<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
+      return launch_bf16<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
     case LVL_EPI_BIAS_QUICKGELU:
       LVL_REQUIRE(aux_out != nullptr, "linear_tn: the QuickGELU epilogue writes the pre-activation to aux_out");
-      return launch_tn<1>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
+      return launch_bf16<1>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
     case LVL_EPI_BIAS_RESIDUAL:
       LVL_REQUIRE(aux_in != nullptr, "linear_tn: the residual epilogue reads the residual rows from aux_in");
-      return launch_tn<3>(x, w, bias, y, nullptr, aux_in, nullptr, M, N, K, sched, st);
+      return launch_bf16<3>(x, w, bias, y, nullptr, aux_in, nullptr, M, N, K, sched, st);
     case LVL_EPI_QUICKGELU_BWD: {
       LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
                   "linear_tn: the QuickGELU-backward epilogue needs aux_in, colsum and a workspace");
-      const int rc = launch_tn<2>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
+      const int rc = launch_bf16<2>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
       if (rc != LVL_OK) return rc;
       const int P = (int)(2 * ((M + TM - 1) / TM));
       return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
     }
     case LVL_EPI_BIAS_QUICKGELU_DERIV:
       LVL_REQUIRE(aux_out != nullptr, "linear_tn: the QuickGELU + derivative epilogue writes quickgelu'(u) to aux_out");
-      return launch_tn<4>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
+      return launch_bf16<4>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
     case LVL_EPI_MUL_AUX_COLSUM: {
       LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
                   "linear_tn: the multiply-by-aux epilogue needs aux_in, colsum and a workspace");
-      const int rc = launch_tn<5>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
+      const int rc = launch_bf16<5>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
       if (rc != LVL_OK) return rc;
       const int P = (int)(2 * ((M + TM - 1) / TM));
       return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
@@ -265,7 +296,7 @@ extern "C" int lvl_linear_tn_ragged(const void* x, const void* w, const float* b
   hipStream_t st = (hipStream_t)stream;
   const int N0 = N / TN * TN;
   if (N0 > 0) {
-    const int rc = launch_tn<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
+    const int rc = launch_bf16<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
     if (rc != LVL_OK) return rc;
   }
   if (N0 < N) return lvl_launch_tn_edge(x, w, bias, y, M, N, K, N0, st);

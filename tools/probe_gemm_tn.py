@@ -64,6 +64,41 @@ def check(M, N, K, seed=0):
     return not bad
 
 
+def mfma_shapes(M, rounds):
+    """`probe_gemm_tn.py M --mfma-shapes [rounds]`: the two MFMA shapes of the K loop (lvl_set_gemm_mfma_shape 32 / 16) on
+    the step's GEMMs with the epilogue each runs with, random operands, interleaved rounds in this one process; median and
+    min of the per-launch HIP-event time per arm (the record behind the default table of csrc/gemm_tn_mfma.hip)."""
+    step = [('qkv', 2304, 768, C.EPI_BIAS, True), ('proj+res', 768, 768, C.EPI_BIAS_RESIDUAL, True),
+            ('fc1+qgelu\'', 3072, 768, C.EPI_BIAS_QUICKGELU_DERIV, True), ('fc2+res', 768, 3072, C.EPI_BIAS_RESIDUAL, True),
+            ('dqkv', 768, 2304, C.EPI_BIAS, False), ('dproj', 768, 768, C.EPI_BIAS, False),
+            ('dfc1', 768, 3072, C.EPI_BIAS, False), ('dfc2*aux+colsum', 3072, 768, C.EPI_MUL_AUX_COLSUM, False)]
+    lib = C.lib()
+    print(f'M={M}, {rounds} interleaved rounds, ms per launch: median (min) per MFMA shape', flush=True)
+    try:
+        for name, N, K, epi, with_bias in step:
+            x = torch.randn(M, K, device='cuda').bfloat16()
+            w = (torch.randn(N, K, device='cuda') * K ** -0.5).bfloat16()
+            b = torch.randn(N, device='cuda') if with_bias else None
+            aux = torch.randn(M, N, device='cuda').bfloat16() if epi in (C.EPI_BIAS_RESIDUAL, C.EPI_MUL_AUX_COLSUM) else None
+            t = {32: [], 16: []}
+            for _ in range(rounds):
+                for shape in (32, 16):
+                    C.check(lib.lvl_set_gemm_mfma_shape(shape), 'set_gemm_mfma_shape')
+                    t[shape].append(timeit(lambda: ops.linear_tn_raw(x, w, b, epi, aux_in=aux), n=4))
+            med = {s: sorted(v)[len(v) // 2] for s, v in t.items()}
+            fl = 2.0 * M * N * K
+            print(f'{name:16s} N={N:4d} K={K:4d} epi {epi}: 32x32x16 {med[32]:.3f} ({min(t[32]):.3f}) ms {fl / med[32] / 1e9:5.0f} TF/s | '
+                  f'16x16x32 {med[16]:.3f} ({min(t[16]):.3f}) ms {fl / med[16] / 1e9:5.0f} TF/s | 16/32 {med[16] / med[32]:.3f} '
+                  f'spread16 {max(t[16]) - min(t[16]):.3f}', flush=True)
+    finally:
+        lib.lvl_set_gemm_mfma_shape(0)
+
+
+if '--mfma-shapes' in sys.argv:
+    i = sys.argv.index('--mfma-shapes')
+    mfma_shapes(M_BIG, int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 7)
+    sys.exit(0)
+
 ok = True
 for (M, N, K) in [(256, 256, 64), (1000, 512, 128), (777, 256, 192), (4096, 768, 768), (2049, 2304, 768), (513, 768, 3072), (70001, 768, 768), (33000, 256, 128), (1800, 256, 64)]:
     ok &= check(M, N, K)
