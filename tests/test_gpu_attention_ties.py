@@ -11,6 +11,10 @@ different keys: out, dq, dk and dv are nonzero and exactly representable, so
   * lse = ln m to 1e-6 where a raw entry returns it; d(qkv bias): k third exactly 0, v third exactly sum(dout), q third
     sum(dq) under the same rule.
 
+Every family runs in three bias modes: with a trainable qkv bias (the backward call carries the bias-gradient rider), with
+none and with a frozen one (the plain entry, every dq_part pointer null: what a freeze_space or frozen-tower step runs in every
+block). The bias-free runs meet the same bars, and their out and dqkv equal the trainable run's bit for bit.
+
 The second part holds the bf16 instantiations to a float64 reference on random inputs at the benched geometries, with a
 bound derived from the bf16 unit roundoff instead of the loose elementwise band of the older tests.
 """
@@ -96,28 +100,55 @@ def _assert_lse(lse, p, rows=None):
     assert err <= 1e-6, f'lse differs from ln(m) by {err}'
 
 
-def _run_divided(kind, shape, dt, generic=0):
-    """Forward + backward through ops.divided_attention with a qkv bias, a second forward for lse, then every check.
-    generic: how many of those three calls must land on the shape-generic kernels."""
+BIAS_MODES = ('trainable', 'none', 'frozen')
+NO_BIAS_GRAD = [m for m in BIAS_MODES if m != 'trainable']
+
+
+def _qkv_bias(D, mode):
+    """The qkv bias handed to the attention op: trainable (its gradient is the rider of the backward call), absent, or
+    present with requires_grad=False (a frozen qkv Linear)."""
+    return None if mode == 'none' else torch.zeros(3 * D, device=DEV, requires_grad=mode == 'trainable')
+
+
+def _divided_once(kind, shape, dt, generic, bias_mode):
     from lavila_amd import ops
     B, F, N, H = shape
     D = 64 * H
     p = _problem(kind, shape)
     _generic_calls()
     x = p.qkv.to(DEV, dt).requires_grad_(True)
-    bias = torch.zeros(3 * D, device=DEV, requires_grad=True)
+    bias = _qkv_bias(D, bias_mode)
     out = ops.divided_attention(x, F, N, H, kind, bias=bias)
     out.backward(p.dout.to(DEV, dt))
     _, lse = ops.divided_attn_fwd_raw(x.detach(), F, N, H, {'space': 0, 'time': 1}[kind])
     torch.cuda.synchronize()
     calls = _generic_calls()
-    assert calls == generic, f'{calls} calls on the generic kernels, {generic} expected'
+    assert calls == generic, f'{calls} calls on the generic kernels, {generic} expected (bias {bias_mode})'
     _assert_exact('out', out, p.out, dt)
     _assert_exact('dq', x.grad[..., :D], p.dqkv[..., :D], dt)
     _assert_exact('dk', x.grad[..., D:2 * D], p.dqkv[..., D:2 * D], dt)
     _assert_exact('dv', x.grad[..., 2 * D:], p.dqkv[..., 2 * D:], dt)
     _assert_lse(lse, p)
-    _assert_bias(bias.grad, p, D)
+    if bias_mode == 'trainable':
+        _assert_bias(bias.grad, p, D)
+    elif bias is not None:
+        assert bias.grad is None, 'a frozen qkv bias received a gradient'
+    return out.detach(), x.grad
+
+
+def _run_divided(kind, shape, dt, generic=0, bias='trainable'):
+    """Forward + backward through ops.divided_attention with a qkv bias, a second forward for lse, then every check.
+    generic: how many of those three calls must land on the shape-generic kernels.
+    bias: 'trainable' -- the backward call carries the bias-gradient rider (lvl_divided_attn_bwd_bias); 'none' / 'frozen' --
+    no bias, or one with requires_grad=False: the plain entry (lvl_divided_attn_bwd, every dq_part pointer null). Those two
+    meet the same exact bars, use the generic kernels as often, and their out and dqkv equal the trainable run's (made
+    here, under the same library switches) bit for bit."""
+    assert bias in BIAS_MODES
+    out, dqkv = _divided_once(kind, shape, dt, generic, bias)
+    if bias != 'trainable':
+        out_t, dqkv_t = _divided_once(kind, shape, dt, generic, 'trainable')
+        assert torch.equal(out, out_t), f'out differs from the run with a trainable bias (bias {bias})'
+        assert torch.equal(dqkv, dqkv_t), f'dqkv differs from the run with a trainable bias (bias {bias})'
 
 
 # ---- space -----------------------------------------------------------------------------------------------------------
@@ -215,17 +246,13 @@ def _causal_lse(x, B, L, H):
     return lse
 
 
-@pytest.mark.parametrize('dt', [BF, F32])
-@pytest.mark.parametrize('shape', AP.CAUSAL)
-def test_causal_ties_exact(shape, dt):
-    """Causal text: MFMA kernels up to 256 tokens; at 272 the forward stays on the MFMA kernel and the backward goes to
-    the generic one."""
+def _causal_once(shape, dt, bias_mode):
     from lavila_amd import ops
     B, L, H = shape
     D = 64 * H
     p = _problem('causal', shape)
     x = p.qkv.to(DEV, dt).requires_grad_(True)
-    bias = torch.zeros(3 * D, device=DEV, requires_grad=True)
+    bias = _qkv_bias(D, bias_mode)
     _generic_calls()
     out = ops.causal_attention(x, H, bias=bias)
     torch.cuda.synchronize()
@@ -239,13 +266,32 @@ def test_causal_ties_exact(shape, dt):
     _assert_exact('dk', x.grad[..., D:2 * D], p.dqkv[..., D:2 * D], dt)
     _assert_exact('dv', x.grad[..., 2 * D:], p.dqkv[..., 2 * D:], dt)
     _assert_lse(lse, p)
-    _assert_bias(bias.grad, p, D)
+    if bias_mode == 'trainable':
+        _assert_bias(bias.grad, p, D)
+    elif bias is not None:
+        assert bias.grad is None, 'a frozen in_proj bias received a gradient'
+    return out.detach(), x.grad
 
 
 @pytest.mark.parametrize('dt', [BF, F32])
-@pytest.mark.parametrize('shape', AP.CLS)
-def test_cls_only_ties_exact(shape, dt):
-    """The cls-only kernels of the last block (cls query over all T tokens, location-chunk partials combined)."""
+@pytest.mark.parametrize('shape', AP.CAUSAL)
+def test_causal_ties_exact(shape, dt):
+    """Causal text: MFMA kernels up to 256 tokens; at 272 the forward stays on the MFMA kernel and the backward goes to
+    the generic one."""
+    _causal_once(shape, dt, 'trainable')
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.CAUSAL)
+def test_causal_ties_exact_without_bias_gradient(shape, dt, bias):
+    """No in_proj bias, or a frozen one: no lvl_qkv_bias_grad pass; out and dqkv as with a trainable bias, to the bit."""
+    out, dqkv = _causal_once(shape, dt, bias)
+    out_t, dqkv_t = _causal_once(shape, dt, 'trainable')
+    assert torch.equal(out, out_t) and torch.equal(dqkv, dqkv_t)
+
+
+def _cls_once(shape, dt, bias_mode):
     from lavila_amd import _cabi as C
     from lavila_amd import ops
     B, T, H = shape
@@ -254,7 +300,7 @@ def test_cls_only_ties_exact(shape, dt):
     q_ref, kv_ref, out_ref, dq_ref, dkv_ref = p.as_cls()
     q = q_ref.to(DEV, dt).contiguous().requires_grad_(True)
     kv = kv_ref.to(DEV, dt).contiguous().requires_grad_(True)
-    bias = torch.zeros(3 * D, device=DEV, requires_grad=True)
+    bias = _qkv_bias(D, bias_mode)
     out = ops.cls_attention(q, kv, H, bias=bias)
     out.backward(p.dout[:, 0].to(DEV, dt))
     o2 = torch.empty(B, D, dtype=dt, device=DEV)
@@ -267,10 +313,124 @@ def test_cls_only_ties_exact(shape, dt):
     _assert_exact('dk', kv.grad[..., :D], dkv_ref[..., :D], dt)
     _assert_exact('dv', kv.grad[..., D:], dkv_ref[..., D:], dt)
     _assert_lse(lse, p, rows=[0])
-    db = bias.grad.detach().double().cpu()
-    assert torch.count_nonzero(db[D:2 * D]) == 0
-    assert torch.equal(db[2 * D:], p.dout[:, 0].sum(0))
-    _assert_exact('d(bias) q third', db[:D], dq_ref.sum(0), F32)      # a float32 sum of the float32 dq
+    if bias_mode == 'trainable':
+        db = bias.grad.detach().double().cpu()
+        assert torch.count_nonzero(db[D:2 * D]) == 0
+        assert torch.equal(db[2 * D:], p.dout[:, 0].sum(0))
+        _assert_exact('d(bias) q third', db[:D], dq_ref.sum(0), F32)      # a float32 sum of the float32 dq
+    elif bias is not None:
+        assert bias.grad is None, 'a frozen qkv bias received a gradient'
+    return out.detach(), q.grad, kv.grad
+
+
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.CLS)
+def test_cls_only_ties_exact(shape, dt):
+    """The cls-only kernels of the last block (cls query over all T tokens, location-chunk partials combined)."""
+    _cls_once(shape, dt, 'trainable')
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.CLS)
+def test_cls_only_ties_exact_without_bias_gradient(shape, dt, bias):
+    got = _cls_once(shape, dt, bias)
+    want = _cls_once(shape, dt, 'trainable')
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+# ---- the divided entry points without a bias gradient: lvl_divided_attn_bwd, every dq_part pointer null ---------------------
+# Every shape list above that ops.divided_attention serves, with no qkv bias and with a frozen one. A trainable bias sends
+# the backward to lvl_divided_attn_bwd_bias, whose kernels also leave column sums of dq (the fused space backward below 289
+# keys always, the time kernels by lvl_debug_time_bwd_rider); every freeze_space / frozen-tower step runs the other branch.
+def _fast(kind, dt, shape):
+    B, F, N, H = shape
+    fp = _lib().lvl_attention_fast_path if dt == BF else _lib().lvl_attention_fast_path_f32
+    return fp({'space': 0, 'time': 1}[kind], F, N, H)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.SPACE_RESIDENT)
+def test_space_resident_ties_exact_without_bias_gradient(shape, dt, bias):
+    assert _fast('space', dt, shape) == 1
+    _run_divided('space', shape, dt, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('shape', AP.SPACE_RESIDENT_273)
+def test_space_resident_forward_273_to_288_keys_ties_exact_without_bias_gradient(shape, bias):
+    _run_divided('space', shape, BF, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.SPACE_STREAM)
+def test_space_streaming_ties_exact_without_bias_gradient(shape, dt, bias):
+    _run_divided('space', shape, dt, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('shape', AP.SPACE_LARGE_RESIDENT)
+def test_space_large_group_resident_ties_exact_without_bias_gradient(shape, bias):
+    B, F, N, H = shape
+    with _switch('lvl_debug_space_stream', -1, 0):
+        assert _lib().lvl_attention_fast_path(0, F, N, H) == int(N + 1 <= 577)
+        _run_divided('space', shape, BF, generic=int(N + 1 > 577), bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', AP.TIME_REGISTER)
+def test_time_register_ties_exact_without_bias_gradient(shape, dt, bias):
+    assert _fast('time', dt, shape) == 1
+    _run_divided('time', shape, dt, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('shape', AP.TIME_MFMA)
+def test_time_mfma_ties_exact_without_bias_gradient(shape, bias):
+    assert _fast('time', BF, shape) == 1
+    _run_divided('time', shape, BF, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('shape', AP.TIME_GENERIC)
+def test_time_generic_ties_exact_without_bias_gradient(shape, bias):
+    assert _fast('time', BF, shape) == 0
+    _run_divided('time', shape, BF, generic=3, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('kind,shape', AP.F32_GENERIC)
+def test_f32_generic_ties_exact_without_bias_gradient(kind, shape, bias):
+    with _switch('lvl_debug_f32_generic', 1, 0):
+        assert _fast(kind, F32, shape) == 0
+        _run_divided(kind, shape, F32, generic=3, bias=bias)
+
+
+@pytest.mark.parametrize('bias', NO_BIAS_GRAD)
+@pytest.mark.parametrize('dt', [BF, F32])
+@pytest.mark.parametrize('shape', [(2, 4, 196, 12), (2, 3, 5, 2)])
+def test_space_backward_without_bias_gradient_is_bitwise_reproducible(shape, dt, bias):
+    """Ten backward passes of the fused space kernel on its rider-free branch (TSF-B geometry, a tiny group) agree to the bit,
+    as test_divided_attention_backward_is_bitwise_reproducible requires of the branch with a bias; random data."""
+    from lavila_amd import ops
+    B, F, N, H = shape
+    D = 64 * H
+    g = torch.Generator().manual_seed(5)
+    x = (torch.randn(B, 1 + F * N, 3 * D, generator=g) * 1.5).to(DEV, dt).requires_grad_(True)
+    go = torch.randn(B, 1 + F * N, D, generator=g).to(DEV, dt)
+    b = _qkv_bias(D, bias)
+    first = None
+    for _ in range(10):
+        x.grad = None
+        ops.divided_attention(x, F, N, H, 'space', bias=b).backward(go)
+        if first is None:
+            first = x.grad.clone()
+        assert torch.equal(x.grad, first)
+    assert b is None or b.grad is None
+    assert bool(torch.isfinite(first.float()).all())
 
 
 # ----------------------------------------------------------------------------------------------------------------------
