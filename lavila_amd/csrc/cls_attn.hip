@@ -6,6 +6,8 @@
 // qkv weight writes them. One workgroup per (b, h): 32 key slots x 8 lanes (8 channels each, one 128-byte row per slot),
 // one pass over K and V with a flash-style running (max, sum, acc) per slot, merged through LDS. HBM-bound: the kernel
 // reads kv once (forward) and reads kv + writes dkv once (backward); f32 arithmetic for both element types.
+// lvl_cross_attn_rows_fwd lives here for its VALU kernels (one query row per context, float32, more than 256 keys); bf16
+// with several rows and <= 256 keys it hands its RowsAttn (internal.h) to the MFMA launcher of cross_attn_mfma.hip.
 #include "internal.h"
 
 namespace {
@@ -246,15 +248,18 @@ extern "C" int lvl_cls_attn_fwd(const void* q, const void* kv, void* out, float*
 extern "C" int lvl_cross_attn_rows_fwd(const void* q, const void* kv, void* out, int rows, int qrep, int Tk, int H,
                                        int dtype, void* stream) {
   LVL_REQUIRE(rows == 0 || (q && kv && out), "cross_attn_rows_fwd: null pointer");
-  LVL_REQUIRE(rows >= 0 && qrep > 0 && rows % qrep == 0 && Tk > 0 && H > 0,
-              "cross_attn_rows_fwd: bad shape rows=%d qrep=%d T=%d H=%d", rows, qrep, Tk, H);
-  LVL_REQUIRE((int64_t)rows * H < (1ll << 31), "cross_attn_rows_fwd: rows * heads must stay below 2^31");
+  LVL_REQUIRE(rows >= 0 && qrep > 0 && rows % qrep == 0, "cross_attn_rows_fwd: bad shape rows=%d qrep=%d T=%d H=%d", rows,
+              qrep, Tk, H);
+  const int64_t Dk = (int64_t)H * 64;            // the image layout kv [ctx, Tk, 2D] = k | v as strides
+  const RowsAttn r{q, kv, (const uint16_t*)kv + Dk, rows / qrep, qrep, Tk, H, Dk, 2 * Dk, (int64_t)Tk * 2 * Dk,
+                   /*keymasked, mask, mask_ctx_stride*/ false, nullptr, 0, /*causal*/ false, /*seed, site, p*/ 0, 0, 0.f,
+                   /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("cross_attn_rows_fwd", r)) return rc;
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(kv) && lvl_aligned16(out),
               "cross_attn_rows_fwd: pointers must be 16-byte aligned");
   if (rows == 0) return LVL_OK;
   // bf16, several rows per context, <= 256 keys: the MFMA kernel
-  if (dtype == LVL_BF16 && qrep >= 2 && Tk <= 256)
-    return lvl_launch_cross_attn_mfma(q, kv, out, rows / qrep, qrep, Tk, H, (hipStream_t)stream);
+  if (dtype == LVL_BF16 && qrep >= 2 && Tk <= 256) return lvl_launch_rows_attn_mfma_fwd(r, out, (hipStream_t)stream);
   const size_t lds = (size_t)Tk * 128 * (dtype == LVL_F32 ? 4 : 2);
   if (qrep >= 2 && lds <= 150 * 1024) {           // the context's keys / values fit LDS: read them once per (context, head)
     const unsigned grid = (unsigned)(rows / qrep * H);

@@ -20,6 +20,9 @@
 // 64 bits per lane (16 fragments x 4 keys; the kernel already holds 4 x 64 accumulator registers per lane):
 //   dPd = dO . V^T,  dP = keep ? dPd / (1 - p) : 0,  delta = sum_j P dP (= dO . O),  dS = P o (dP - delta),
 //   dV += Pd^T . dO with Pd = keep ? P / (1 - p) : 0 (the P^T image holds Pd);  dQ, dK from dS as before.
+//
+// Host side: lvl_launch_rows_attn_mfma_bwd is the one launch site, behind the backward entries of all four rows-attention
+// pairs; they describe their call as a RowsAttn and share lvl_rows_attn_check (internal.h, cross_attn_mfma.hip).
 #include "attn_mfma_common.h"
 #include "dropout.h"
 #include "internal.h"
@@ -238,59 +241,52 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_bwd_mfma_kernel(const uint
   }
 }
 
-}  // namespace
-
-// called by lvl_keymask_attn_bwd (keymask_attn.hip) for bf16, Tk <= 256
-int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
-                                     void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride,
-                                     int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st) {
+template <bool DROP, bool CAUSAL, bool KEYMASK>
+int launch_bwd(const RowsAttn& r, const void* dout, void* dq, void* dk, void* dv, hipStream_t st) {
   const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<false, false, true>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<false, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
-                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
-                     (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, Tk, H, qrep,
-                     AttnDrop{}, mask, (size_t)mask_ctx_stride);
-  LVL_CHECK_LAUNCH("keymask_attn_bwd (mfma)");
+  const AttnDrop drop = DROP ? AttnDrop{r.seed, r.site, lvl_drop::threshold(r.p), lvl_drop::scale_of(r.p), r.idx_qrep}
+                             : AttnDrop{};
+  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<DROP, CAUSAL, KEYMASK>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<DROP, CAUSAL, KEYMASK>), dim3((unsigned)(r.contexts * r.H)), dim3(64 * XW),
+                     lds, st, (const uint16_t*)r.q, (size_t)r.q_stride, (const uint16_t*)r.k, (const uint16_t*)r.v,
+                     (size_t)r.kv_stride, (size_t)r.kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk,
+                     (uint16_t*)dv, r.Tk, r.H, r.qrep, drop, r.mask, (size_t)r.mask_ctx_stride);
+  LVL_CHECK_LAUNCH("rows attention backward (mfma)");
   return LVL_OK;
 }
 
-// called by lvl_keymask_attn_drop_bwd (keymask_attn.hip) for bf16, Tk <= 256, p > 0
-int lvl_launch_keymask_attn_mfma_drop_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
-                                          void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H,
-                                          int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
-                                          int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p,
-                                          hipStream_t st) {
-  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), idx_qrep};
-  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<true, false, true>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<true, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
-                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
-                     (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, Tk, H, qrep,
-                     drop, mask, (size_t)mask_ctx_stride);
-  LVL_CHECK_LAUNCH("keymask_attn_drop_bwd (mfma)");
-  return LVL_OK;
+}  // namespace
+
+// The one launch site of cross_attn_bwd_mfma_kernel: the six instantiations the entries reach.
+int lvl_launch_rows_attn_mfma_bwd(const RowsAttn& r, const void* dout, void* dq, void* dk, void* dv, hipStream_t st) {
+  if (r.Tk > NKT * 16 || (r.causal && r.keymasked))
+    return lvl_fail(LVL_EINVAL, "rows attention backward (mfma): Tk = %d beyond %d keys, or causal with a key mask", r.Tk,
+                    NKT * 16);
+  const bool drop = r.p > 0.f;
+  if (r.keymasked)
+    return drop ? launch_bwd<true, false, true>(r, dout, dq, dk, dv, st) : launch_bwd<false, false, true>(r, dout, dq, dk, dv, st);
+  if (r.causal)
+    return drop ? launch_bwd<true, true, false>(r, dout, dq, dk, dv, st) : launch_bwd<false, true, false>(r, dout, dq, dk, dv, st);
+  return drop ? launch_bwd<true, false, false>(r, dout, dq, dk, dv, st) : launch_bwd<false, false, false>(r, dout, dq, dk, dv, st);
 }
 
 extern "C" int lvl_cross_attn_rows_bwd(const void* q, const void* kv, const void* dout, void* dq, void* dkv, int rows,
                                        int qrep, int Tk, int H, int dtype, void* stream) {
   LVL_REQUIRE(rows == 0 || (q && kv && dout && dq && dkv), "cross_attn_rows_bwd: null pointer");
-  LVL_REQUIRE(rows >= 0 && qrep > 0 && rows % qrep == 0 && Tk > 0 && H > 0,
-              "cross_attn_rows_bwd: bad shape rows=%d qrep=%d Tk=%d H=%d", rows, qrep, Tk, H);
+  LVL_REQUIRE(rows >= 0 && qrep > 0 && rows % qrep == 0, "cross_attn_rows_bwd: bad shape rows=%d qrep=%d Tk=%d H=%d", rows,
+              qrep, Tk, H);
+  const int64_t D = (int64_t)H * 64;             // the image layout kv [ctx, Tk, 2D] = k | v as strides
+  const RowsAttn r{q, kv, (const uint16_t*)kv + D, rows / qrep, qrep, Tk, H, D, 2 * D, (int64_t)Tk * 2 * D,
+                   /*keymasked, mask, mask_ctx_stride*/ false, nullptr, 0, /*causal*/ false, /*seed, site, p*/ 0, 0, 0.f,
+                   /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("cross_attn_rows_bwd", r)) return rc;
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(kv) && lvl_aligned16(dout) && lvl_aligned16(dq) && lvl_aligned16(dkv),
               "cross_attn_rows_bwd: pointers must be 16-byte aligned");
   if (dtype != LVL_BF16 || Tk > NKT * 16)
     return lvl_fail(LVL_ENOSYS, "cross_attn_rows_bwd: built for bf16 and 1 <= Tk <= %d keys per context (got dtype %d, Tk=%d)",
                     NKT * 16, dtype, Tk);
   if (rows == 0) return LVL_OK;
-  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const size_t D = (size_t)H * 64;
-  if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<false, false>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<false, false>), dim3((unsigned)((rows / qrep) * H)), dim3(64 * XW), lds,
-                     (hipStream_t)stream, (const uint16_t*)q, D, (const uint16_t*)kv, (const uint16_t*)kv + D, 2 * D,
-                     (size_t)Tk * 2 * D, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dkv, (uint16_t*)dkv + D, Tk, H,
-                     qrep, AttnDrop{});
-  LVL_CHECK_LAUNCH("cross_attn_rows_bwd");
-  return LVL_OK;
+  return lvl_launch_rows_attn_mfma_bwd(r, dout, dq, dkv, (uint16_t*)dkv + D, (hipStream_t)stream);
 }
 
 // backward of lvl_attn_rows_drop_fwd: dq laid out as q, dk and dv as k and v (same strides); dout [rows, H*64]
@@ -299,36 +295,14 @@ extern "C" int lvl_attn_rows_drop_bwd(const void* q, const void* k, const void* 
                                       int64_t kv_ctx_stride, int causal, uint64_t seed, uint32_t site, float p, int dtype,
                                       void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && dout && dq && dk && dv), "attn_rows_drop_bwd: null pointer");
-  LVL_REQUIRE(contexts >= 0 && qrep > 0 && Tk > 0 && H > 0, "attn_rows_drop_bwd: bad shape contexts=%d qrep=%d Tk=%d H=%d",
-              contexts, qrep, Tk, H);
-  const int64_t D = (int64_t)H * 64;
-  LVL_REQUIRE(q_stride >= D && kv_stride >= D && q_stride % 8 == 0 && kv_stride % 8 == 0 && kv_ctx_stride % 8 == 0 &&
-                  kv_ctx_stride >= 0, "attn_rows_drop_bwd: strides must be multiples of 8 elements, rows at least H*64 apart");
-  LVL_REQUIRE(!causal || qrep == Tk, "attn_rows_drop_bwd: the causal form needs qrep == Tk (got %d, %d)", qrep, Tk);
-  LVL_REQUIRE(p >= 0.f && p < 1.f, "attn_rows_drop_bwd: p = %g must be in [0, 1)", (double)p);
-  LVL_REQUIRE((int64_t)contexts * qrep * H < (1ll << 31), "attn_rows_drop_bwd: rows * heads must stay below 2^31");
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked, mask, mask_ctx_stride*/ false, nullptr, 0, causal != 0, seed, site, p, /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("attn_rows_drop_bwd", r)) return rc;
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(dout) && lvl_aligned16(dq) &&
                   lvl_aligned16(dk) && lvl_aligned16(dv), "attn_rows_drop_bwd: pointers must be 16-byte aligned");
   if (dtype != LVL_BF16 || Tk > NKT * 16)
     return lvl_fail(LVL_ENOSYS, "attn_rows_drop_bwd: built for bf16 and 1 <= Tk <= %d keys per context (got dtype %d, Tk=%d)",
                     NKT * 16, dtype, Tk);
   if (contexts == 0) return LVL_OK;
-  const size_t lds = ((size_t)4 * NKT * 16 * RS + (size_t)2 * QR * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), qrep};
-#define LVL_AR(DR, CA)                                                                                                 \
-  do {                                                                                                                 \
-    if (int rc = lvl_allow_lds<cross_attn_bwd_mfma_kernel<DR, CA>>()) return rc;                                       \
-    hipLaunchKernelGGL((cross_attn_bwd_mfma_kernel<DR, CA>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds,       \
-                       (hipStream_t)stream, (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, \
-                       (size_t)kv_stride, (size_t)kv_ctx_stride, (const uint16_t*)dout, (uint16_t*)dq, (uint16_t*)dk,  \
-                       (uint16_t*)dv, Tk, H, qrep, drop);                                                              \
-  } while (0)
-  if (p > 0.f) {
-    if (causal) LVL_AR(true, true); else LVL_AR(true, false);
-  } else {
-    if (causal) LVL_AR(false, true); else LVL_AR(false, false);
-  }
-#undef LVL_AR
-  LVL_CHECK_LAUNCH("attn_rows_drop_bwd");
-  return LVL_OK;
+  return lvl_launch_rows_attn_mfma_bwd(r, dout, dq, dk, dv, (hipStream_t)stream);
 }

@@ -18,6 +18,11 @@
 //         fragment (j = k*16 + g*4 + r) share one Philox call, generated where the fragment is packed; nothing is stored.
 //         (The index takes drop.idx_qrep for qrep: the same number, except when a key-masked call computes a subset of
 //         the query rows of a larger one.)
+//
+// Host side: every entry point of the rows attention (lvl_cross_attn_rows_*, lvl_attn_rows_drop_*, lvl_keymask_attn_*,
+// lvl_keymask_attn_drop_*) describes its call as a RowsAttn (internal.h), runs lvl_rows_attn_check below and comes to
+// lvl_launch_rows_attn_mfma_fwd, the one launch site of the kernel: it picks among the six instantiations that exist
+// (<DROP> x <plain, CAUSAL, KEYMASK>). The backward has the same pair in cross_attn_bwd_mfma.hip.
 #include "attn_mfma_common.h"
 #include "dropout.h"
 #include "internal.h"
@@ -151,47 +156,48 @@ __global__ __launch_bounds__(64 * XW) void cross_attn_mfma_kernel(const uint16_t
   }
 }
 
+template <bool DROP, bool CAUSAL, bool KEYMASK>
+int launch_fwd(const RowsAttn& r, void* out, hipStream_t st) {
+  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
+  const AttnDrop drop = DROP ? AttnDrop{r.seed, r.site, lvl_drop::threshold(r.p), lvl_drop::scale_of(r.p), r.idx_qrep}
+                             : AttnDrop{};
+  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<DROP, CAUSAL, KEYMASK>>()) return rc;
+  hipLaunchKernelGGL((cross_attn_mfma_kernel<DROP, CAUSAL, KEYMASK>), dim3((unsigned)(r.contexts * r.H)), dim3(64 * XW), lds,
+                     st, (const uint16_t*)r.q, (size_t)r.q_stride, (const uint16_t*)r.k, (const uint16_t*)r.v,
+                     (size_t)r.kv_stride, (size_t)r.kv_ctx_stride, (uint16_t*)out, r.Tk, r.H, r.qrep, drop, r.mask,
+                     (size_t)r.mask_ctx_stride);
+  LVL_CHECK_LAUNCH("rows attention forward (mfma)");
+  return LVL_OK;
+}
+
 }  // namespace
 
-// called by lvl_cross_attn_rows_fwd (cls_attn.hip) for bf16, qrep >= 2, Tk <= 256
-int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
-                               hipStream_t st) {
-  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const size_t D = (size_t)H * 64;
-  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<false, false>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_mfma_kernel<false, false>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
-                     (const uint16_t*)q, D, (const uint16_t*)kv, (const uint16_t*)kv + D, 2 * D, (size_t)Tk * 2 * D,
-                     (uint16_t*)out, Tk, H, qrep, AttnDrop{});
-  LVL_CHECK_LAUNCH("cross_attn_rows_fwd (mfma)");
+int lvl_rows_attn_check(const char* who, const RowsAttn& r) {
+  LVL_REQUIRE(r.contexts >= 0 && r.qrep > 0 && r.Tk > 0 && r.H > 0, "%s: bad shape contexts=%d qrep=%d Tk=%d H=%d", who,
+              r.contexts, r.qrep, r.Tk, r.H);
+  const int64_t D = (int64_t)r.H * 64;
+  LVL_REQUIRE(r.q_stride >= D && r.kv_stride >= D && r.q_stride % 8 == 0 && r.kv_stride % 8 == 0 &&
+                  r.kv_ctx_stride % 8 == 0 && r.kv_ctx_stride >= 0,
+              "%s: strides must be multiples of 8 elements, rows at least H*64 apart", who);
+  LVL_REQUIRE(r.mask == nullptr || r.mask_ctx_stride >= r.Tk, "%s: the mask's context stride must be at least Tk bytes", who);
+  LVL_REQUIRE((int64_t)r.contexts * r.qrep * r.H < (1ll << 31), "%s: rows * heads must stay below 2^31", who);
+  // the shape-generic key-masked kernels also size a grid by the keys
+  LVL_REQUIRE(!r.keymasked || (int64_t)r.contexts * r.Tk * r.H < (1ll << 31), "%s: keys * heads must stay below 2^31", who);
+  LVL_REQUIRE(!r.causal || r.qrep == r.Tk, "%s: the causal form needs qrep == Tk (got %d, %d)", who, r.qrep, r.Tk);
+  LVL_REQUIRE(r.p >= 0.f && r.p < 1.f, "%s: p = %g must be in [0, 1)", who, (double)r.p);
+  LVL_REQUIRE(r.idx_qrep >= r.qrep, "%s: idx_qrep = %d must be at least qrep = %d", who, r.idx_qrep, r.qrep);
   return LVL_OK;
 }
 
-// called by lvl_keymask_attn_fwd (keymask_attn.hip) for bf16, Tk <= 256
-int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
-                                     int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
-                                     int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st) {
-  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<false, false, true>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_mfma_kernel<false, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
-                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
-                     (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, AttnDrop{}, mask, (size_t)mask_ctx_stride);
-  LVL_CHECK_LAUNCH("keymask_attn_fwd (mfma)");
-  return LVL_OK;
-}
-
-// called by lvl_keymask_attn_drop_fwd (keymask_attn.hip) for bf16, Tk <= 256, p > 0
-int lvl_launch_keymask_attn_mfma_drop_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
-                                          int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
-                                          int64_t kv_ctx_stride, int64_t mask_ctx_stride, int idx_qrep, uint64_t seed,
-                                          uint32_t site, float p, hipStream_t st) {
-  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), idx_qrep};
-  if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<true, false, true>>()) return rc;
-  hipLaunchKernelGGL((cross_attn_mfma_kernel<true, false, true>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds, st,
-                     (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, (size_t)kv_stride,
-                     (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, drop, mask, (size_t)mask_ctx_stride);
-  LVL_CHECK_LAUNCH("keymask_attn_drop_fwd (mfma)");
-  return LVL_OK;
+// The one launch site of cross_attn_mfma_kernel: the six instantiations the entries reach.
+int lvl_launch_rows_attn_mfma_fwd(const RowsAttn& r, void* out, hipStream_t st) {
+  if (r.Tk > NKT * 16 || (r.causal && r.keymasked))
+    return lvl_fail(LVL_EINVAL, "rows attention forward (mfma): Tk = %d beyond %d keys, or causal with a key mask", r.Tk,
+                    NKT * 16);
+  const bool drop = r.p > 0.f;
+  if (r.keymasked) return drop ? launch_fwd<true, false, true>(r, out, st) : launch_fwd<false, false, true>(r, out, st);
+  if (r.causal) return drop ? launch_fwd<true, true, false>(r, out, st) : launch_fwd<false, true, false>(r, out, st);
+  return drop ? launch_fwd<true, false, false>(r, out, st) : launch_fwd<false, false, false>(r, out, st);
 }
 
 // The dropout-capable rows attention of the training decoder: q [contexts * qrep rows, stride q_stride], keys k and values
@@ -200,14 +206,9 @@ extern "C" int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* 
                                       int H, int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride, int causal,
                                       uint64_t seed, uint32_t site, float p, int dtype, void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && out), "attn_rows_drop_fwd: null pointer");
-  LVL_REQUIRE(contexts >= 0 && qrep > 0 && Tk > 0 && H > 0, "attn_rows_drop_fwd: bad shape contexts=%d qrep=%d Tk=%d H=%d",
-              contexts, qrep, Tk, H);
-  const int64_t D = (int64_t)H * 64;
-  LVL_REQUIRE(q_stride >= D && kv_stride >= D && q_stride % 8 == 0 && kv_stride % 8 == 0 && kv_ctx_stride % 8 == 0 &&
-                  kv_ctx_stride >= 0, "attn_rows_drop_fwd: strides must be multiples of 8 elements, rows at least H*64 apart");
-  LVL_REQUIRE(!causal || qrep == Tk, "attn_rows_drop_fwd: the causal form needs qrep == Tk (got %d, %d)", qrep, Tk);
-  LVL_REQUIRE(p >= 0.f && p < 1.f, "attn_rows_drop_fwd: p = %g must be in [0, 1)", (double)p);
-  LVL_REQUIRE((int64_t)contexts * qrep * H < (1ll << 31), "attn_rows_drop_fwd: rows * heads must stay below 2^31");
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked, mask, mask_ctx_stride*/ false, nullptr, 0, causal != 0, seed, site, p, /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("attn_rows_drop_fwd", r)) return rc;
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(out),
               "attn_rows_drop_fwd: pointers must be 16-byte aligned");
   if (dtype != LVL_BF16 || Tk > NKT * 16)
@@ -215,24 +216,9 @@ extern "C" int lvl_attn_rows_drop_fwd(const void* q, const void* k, const void* 
                     NKT * 16, dtype, Tk);
   if (contexts == 0) return LVL_OK;
   // no dropout, no mask, the image layout: exactly today's call (which has a kernel of its own for qrep == 1)
+  const int64_t D = (int64_t)H * 64;
   if (!causal && p == 0.f && q_stride == D && kv_stride == 2 * D && kv_ctx_stride == (int64_t)Tk * 2 * D &&
       (const uint16_t*)v == (const uint16_t*)k + D)
     return lvl_cross_attn_rows_fwd(q, k, out, contexts * qrep, qrep, Tk, H, dtype, stream);
-  const size_t lds = ((size_t)2 * NKT * 16 * RS + (size_t)XW * 16 * OS) * sizeof(uint16_t);
-  const AttnDrop drop{seed, site, lvl_drop::threshold(p), lvl_drop::scale_of(p), qrep};
-#define LVL_AR(DR, CA)                                                                                                 \
-  do {                                                                                                                 \
-    if (int rc = lvl_allow_lds<cross_attn_mfma_kernel<DR, CA>>()) return rc;                                           \
-    hipLaunchKernelGGL((cross_attn_mfma_kernel<DR, CA>), dim3((unsigned)(contexts * H)), dim3(64 * XW), lds,           \
-                       (hipStream_t)stream, (const uint16_t*)q, (size_t)q_stride, (const uint16_t*)k, (const uint16_t*)v, \
-                       (size_t)kv_stride, (size_t)kv_ctx_stride, (uint16_t*)out, Tk, H, qrep, drop);                   \
-  } while (0)
-  if (p > 0.f) {
-    if (causal) LVL_AR(true, true); else LVL_AR(true, false);
-  } else {
-    if (causal) LVL_AR(false, true); else LVL_AR(false, false);
-  }
-#undef LVL_AR
-  LVL_CHECK_LAUNCH("attn_rows_drop_fwd");
-  return LVL_OK;
+  return lvl_launch_rows_attn_mfma_fwd(r, out, (hipStream_t)stream);
 }

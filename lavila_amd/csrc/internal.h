@@ -37,25 +37,29 @@ int lvl_launch_wgrad_160(int cfg, int tiles_k, int ntiles, int S, const void* dy
 bool lvl_clip_mfma_supported(int E);
 int lvl_clip_fwd_mfma(const void* img_all, const void* txt_all, const float* scale, int B, int G, int E, int row0,
                       float* stats, int32_t* argmax, float* logits, int dtype, hipStream_t st);
-// cross_attn_mfma.hip
-int lvl_launch_cross_attn_mfma(const void* q, const void* kv, void* out, int contexts, int qrep, int Tk, int H,
-                               hipStream_t st);
-// cross_attn_mfma.hip / cross_attn_bwd_mfma.hip: the key-masked instantiations behind lvl_keymask_attn_fwd / _bwd (bf16,
-// Tk <= 256; keymask_attn.hip holds the entry points and the shape-generic kernels)
-int lvl_launch_keymask_attn_mfma_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
-                                     int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
-                                     int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st);
-int lvl_launch_keymask_attn_mfma_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
-                                     void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H, int64_t q_stride,
-                                     int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride, hipStream_t st);
-// their <DROP, KEYMASK> twins behind lvl_keymask_attn_drop_fwd / _bwd (p > 0): the mask of dropout.h over
-// e = ((((ctx * H + h) * idx_qrep + i) << 8) | j
-int lvl_launch_keymask_attn_mfma_drop_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
-                                          int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
-                                          int64_t kv_ctx_stride, int64_t mask_ctx_stride, int idx_qrep, uint64_t seed,
-                                          uint32_t site, float p, hipStream_t st);
-int lvl_launch_keymask_attn_mfma_drop_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* dout,
-                                          void* dq, void* dk, void* dv, int contexts, int qrep, int Tk, int H,
-                                          int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride,
-                                          int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p,
-                                          hipStream_t st);
+// The rows attention (one workgroup per (context, head), bf16, Tk <= 256) as its eight entry points describe a call:
+// lvl_cross_attn_rows_fwd / _bwd, lvl_attn_rows_drop_fwd / _bwd, lvl_keymask_attn_fwd / _bwd, lvl_keymask_attn_drop_fwd /
+// _bwd. q rows q_stride apart, keys k and values v rows kv_stride apart and contexts kv_ctx_stride apart (elements); the
+// image layout kv [ctx, Tk, 2D] is q_stride = D, kv_stride = 2D, kv_ctx_stride = Tk * 2D, v = k + D.
+struct RowsAttn {
+  const void *q, *k, *v;
+  int contexts, qrep, Tk, H;
+  int64_t q_stride, kv_stride, kv_ctx_stride;
+  bool keymasked;               // the key-masked kernels (the lvl_keymask_attn_* entries), also when mask is NULL
+  const uint8_t* mask;          // [contexts] rows of Tk bytes, mask_ctx_stride apart, non-zero = visible; NULL: none hidden
+  int64_t mask_ctx_stride;
+  bool causal;                  // key j <= query i; needs qrep == Tk
+  // the dropout site on the probabilities, p == 0: none. The mask of dropout.h over
+  // e = ((((ctx * H + h) * idx_qrep + i) << 8) | j; idx_qrep is qrep, or the full call's when this one computes a subset
+  // of its query rows
+  uint64_t seed;
+  uint32_t site;
+  float p;
+  int idx_qrep;
+};
+// cross_attn_mfma.hip: the shape, stride, < 2^31, causal, p and idx_qrep requirements of every entry; `who` names the entry
+int lvl_rows_attn_check(const char* who, const RowsAttn& r);
+// cross_attn_mfma.hip / cross_attn_bwd_mfma.hip: the one launch site of each direction; out / dout [rows, H*64], dq laid
+// out as q, dk and dv as k and v. The caller has run the check and refused what is not bf16 with Tk <= 256.
+int lvl_launch_rows_attn_mfma_fwd(const RowsAttn& r, void* out, hipStream_t st);
+int lvl_launch_rows_attn_mfma_bwd(const RowsAttn& r, const void* dout, void* dq, void* dk, void* dv, hipStream_t st);

@@ -1,7 +1,8 @@
 // Key-masked bidirectional attention (forward + backward): the entry points, and the shape-generic kernels (f32 arithmetic,
 // any element type, any key count) that serve float32 and bf16 beyond 256 keys; bf16 with Tk <= 256 goes to the KEYMASK
 // instantiations of the MFMA rows attention (cross_attn_mfma.hip, cross_attn_bwd_mfma.hip: one workgroup per (context,
-// head), exact single-pass softmax). The self-attention of a padded text batch (DistilBERT's MultiHeadSelfAttention under an attention_mask; transformers fills
+// head), exact single-pass softmax) through the rows attention's own check and launchers (RowsAttn, internal.h): an entry
+// here keeps its null-pointer, dtype and alignment lines and the launches of the generic kernels. The self-attention of a padded text batch (DistilBERT's MultiHeadSelfAttention under an attention_mask; transformers fills
 // the scores of hidden keys with the most negative finite value before the softmax). Operands as lvl_attn_rows_drop_fwd:
 // q rows q_stride apart, per-context keys / values kv_stride apart, contexts kv_ctx_stride apart; keymask [contexts, Tk]
 // bytes, non-zero = visible, NULL = all visible.
@@ -365,35 +366,21 @@ __global__ __launch_bounds__(256) void keymask_bwd_dkv_drop_kernel(const T* __re
   }
 }
 
-int km_check(const char* who, int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
-             int64_t kv_ctx_stride, int64_t mask_ctx_stride, const void* keymask, int dtype) {
-  LVL_REQUIRE(contexts >= 0 && qrep > 0 && Tk > 0 && H > 0, "%s: bad shape contexts=%d qrep=%d Tk=%d H=%d", who, contexts,
-              qrep, Tk, H);
-  const int64_t D = (int64_t)H * 64;
-  LVL_REQUIRE(q_stride >= D && kv_stride >= D && q_stride % 8 == 0 && kv_stride % 8 == 0 && kv_ctx_stride % 8 == 0 &&
-                  kv_ctx_stride >= 0, "%s: strides must be multiples of 8 elements, rows at least H*64 apart", who);
-  LVL_REQUIRE(keymask == nullptr || mask_ctx_stride >= Tk, "%s: the mask's context stride must be at least Tk bytes", who);
-  LVL_REQUIRE((int64_t)contexts * qrep * H < (1ll << 31) && (int64_t)contexts * Tk * H < (1ll << 31),
-              "%s: rows * heads and keys * heads must stay below 2^31", who);
-  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "%s: unknown dtype %d", who, dtype);
-  return LVL_OK;
-}
-
 }  // namespace
 
 extern "C" int lvl_keymask_attn_fwd(const void* q, const void* k, const void* v, const uint8_t* keymask, void* out,
                                     int contexts, int qrep, int Tk, int H, int64_t q_stride, int64_t kv_stride,
                                     int64_t kv_ctx_stride, int64_t mask_ctx_stride, int dtype, void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && out), "keymask_attn_fwd: null pointer");
-  if (int rc = km_check("keymask_attn_fwd", contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride,
-                        keymask, dtype))
-    return rc;
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked*/ true, keymask, mask_ctx_stride, /*causal*/ false, /*seed, site, p*/ 0, 0, 0.f,
+                   /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("keymask_attn_fwd", r)) return rc;
+  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "keymask_attn_fwd: unknown dtype %d", dtype);
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(out),
               "keymask_attn_fwd: pointers must be 16-byte aligned");
   if (contexts == 0) return LVL_OK;
-  if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys)
-    return lvl_launch_keymask_attn_mfma_fwd(q, k, v, keymask, out, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
-                                            mask_ctx_stride, (hipStream_t)stream);
+  if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys) return lvl_launch_rows_attn_mfma_fwd(r, out, (hipStream_t)stream);
   const KmOperands d{q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride, Tk, H, qrep};
   const int64_t total = (int64_t)contexts * qrep * H;
   LVL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((keymask_fwd_kernel<T, false>), dim3((unsigned)((total + 3) / 4)), dim3(256),
@@ -408,16 +395,17 @@ extern "C" int lvl_keymask_attn_bwd(const void* q, const void* k, const void* v,
                                     int64_t q_stride, int64_t kv_stride, int64_t kv_ctx_stride, int64_t mask_ctx_stride,
                                     int dtype, void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && dout && dq && dk && dv && ws), "keymask_attn_bwd: null pointer");
-  if (int rc = km_check("keymask_attn_bwd", contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride,
-                        keymask, dtype))
-    return rc;
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked*/ true, keymask, mask_ctx_stride, /*causal*/ false, /*seed, site, p*/ 0, 0, 0.f,
+                   /*idx_qrep*/ qrep};
+  if (int rc = lvl_rows_attn_check("keymask_attn_bwd", r)) return rc;
+  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "keymask_attn_bwd: unknown dtype %d", dtype);
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(dout) && lvl_aligned16(dq) &&
                   lvl_aligned16(dk) && lvl_aligned16(dv) && lvl_aligned16(ws),
               "keymask_attn_bwd: pointers must be 16-byte aligned");
   if (contexts == 0) return LVL_OK;
   if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys)
-    return lvl_launch_keymask_attn_mfma_bwd(q, k, v, keymask, dout, dq, dk, dv, contexts, qrep, Tk, H, q_stride, kv_stride,
-                                            kv_ctx_stride, mask_ctx_stride, (hipStream_t)stream);
+    return lvl_launch_rows_attn_mfma_bwd(r, dout, dq, dk, dv, (hipStream_t)stream);
   const KmOperands d{q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride, Tk, H, qrep};
   const int64_t total_q = (int64_t)contexts * qrep * H, total_k = (int64_t)contexts * Tk * H;
   LVL_DISPATCH_DTYPE(dtype, {
@@ -433,12 +421,6 @@ extern "C" int lvl_keymask_attn_bwd(const void* q, const void* k, const void* v,
 }
 
 // ---- dropout on the key-masked probabilities -------------------------------------------------------------------------
-static int km_drop_check(const char* who, int qrep, int idx_qrep, float p) {
-  LVL_REQUIRE(p >= 0.f && p < 1.f, "%s: p = %g must be in [0, 1)", who, (double)p);
-  LVL_REQUIRE(idx_qrep >= qrep, "%s: idx_qrep = %d must be at least qrep = %d", who, idx_qrep, qrep);
-  return LVL_OK;
-}
-
 static KmDrop km_drop_args(int Tk, int idx_qrep, uint64_t seed, uint32_t site, float p) {
   int s = 8;
   while ((1ll << s) < Tk) ++s;
@@ -450,19 +432,17 @@ extern "C" int lvl_keymask_attn_drop_fwd(const void* q, const void* k, const voi
                                          int64_t kv_ctx_stride, int64_t mask_ctx_stride, int idx_qrep, uint64_t seed,
                                          uint32_t site, float p, int dtype, void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && out), "keymask_attn_drop_fwd: null pointer");
-  if (int rc = km_check("keymask_attn_drop_fwd", contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride,
-                        keymask, dtype))
-    return rc;
-  if (int rc = km_drop_check("keymask_attn_drop_fwd", qrep, idx_qrep, p)) return rc;
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked*/ true, keymask, mask_ctx_stride, /*causal*/ false, seed, site, p, idx_qrep};
+  if (int rc = lvl_rows_attn_check("keymask_attn_drop_fwd", r)) return rc;
+  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "keymask_attn_drop_fwd: unknown dtype %d", dtype);
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(out),
               "keymask_attn_drop_fwd: pointers must be 16-byte aligned");
   if (contexts == 0) return LVL_OK;
   if (p == 0.f)                                               // today's kernels, today's bits
     return lvl_keymask_attn_fwd(q, k, v, keymask, out, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
                                 mask_ctx_stride, dtype, stream);
-  if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys)
-    return lvl_launch_keymask_attn_mfma_drop_fwd(q, k, v, keymask, out, contexts, qrep, Tk, H, q_stride, kv_stride,
-                                                 kv_ctx_stride, mask_ctx_stride, idx_qrep, seed, site, p, (hipStream_t)stream);
+  if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys) return lvl_launch_rows_attn_mfma_fwd(r, out, (hipStream_t)stream);
   const KmOperands d{q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride, Tk, H, qrep};
   const KmDrop dr = km_drop_args(Tk, idx_qrep, seed, site, p);
   const int64_t total = (int64_t)contexts * qrep * H;
@@ -479,10 +459,10 @@ extern "C" int lvl_keymask_attn_drop_bwd(const void* q, const void* k, const voi
                                          int64_t mask_ctx_stride, int idx_qrep, uint64_t seed, uint32_t site, float p,
                                          int dtype, void* stream) {
   LVL_REQUIRE(contexts == 0 || (q && k && v && dout && dq && dk && dv && ws), "keymask_attn_drop_bwd: null pointer");
-  if (int rc = km_check("keymask_attn_drop_bwd", contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride,
-                        keymask, dtype))
-    return rc;
-  if (int rc = km_drop_check("keymask_attn_drop_bwd", qrep, idx_qrep, p)) return rc;
+  const RowsAttn r{q, k, v, contexts, qrep, Tk, H, q_stride, kv_stride, kv_ctx_stride,
+                   /*keymasked*/ true, keymask, mask_ctx_stride, /*causal*/ false, seed, site, p, idx_qrep};
+  if (int rc = lvl_rows_attn_check("keymask_attn_drop_bwd", r)) return rc;
+  LVL_REQUIRE(dtype == LVL_F32 || dtype == LVL_BF16, "keymask_attn_drop_bwd: unknown dtype %d", dtype);
   LVL_REQUIRE(lvl_aligned16(q) && lvl_aligned16(k) && lvl_aligned16(v) && lvl_aligned16(dout) && lvl_aligned16(dq) &&
                   lvl_aligned16(dk) && lvl_aligned16(dv) && lvl_aligned16(ws),
               "keymask_attn_drop_bwd: pointers must be 16-byte aligned");
@@ -491,9 +471,7 @@ extern "C" int lvl_keymask_attn_drop_bwd(const void* q, const void* k, const voi
     return lvl_keymask_attn_bwd(q, k, v, keymask, dout, dq, dk, dv, ws, contexts, qrep, Tk, H, q_stride, kv_stride,
                                 kv_ctx_stride, mask_ctx_stride, dtype, stream);
   if (dtype == LVL_BF16 && Tk <= kMfmaMaxKeys)
-    return lvl_launch_keymask_attn_mfma_drop_bwd(q, k, v, keymask, dout, dq, dk, dv, contexts, qrep, Tk, H, q_stride,
-                                                 kv_stride, kv_ctx_stride, mask_ctx_stride, idx_qrep, seed, site, p,
-                                                 (hipStream_t)stream);
+    return lvl_launch_rows_attn_mfma_bwd(r, dout, dq, dk, dv, (hipStream_t)stream);
   const KmOperands d{q_stride, kv_stride, kv_ctx_stride, mask_ctx_stride, Tk, H, qrep};
   const KmDrop dr = km_drop_args(Tk, idx_qrep, seed, site, p);
   const int64_t total_q = (int64_t)contexts * qrep * H;

@@ -584,26 +584,21 @@ class _GatedAddLnFn(torch.autograd.Function):
     """s = res + tanh(alpha) * y, h = LayerNorm(s): (s, h) -- or h alone when there is no y (the first norm of the stack).
     Forward lvl_gated_add_layernorm_train (the inference kernel, which also returns mean / rstd), backward
     lvl_gated_add_layernorm_bwd: lvl_layernorm_bwd on the kept sum with the residual stream's gradient as `dadd`, then one
-    pass for dy = gate * ds and the deterministic gate gradient."""
+    pass for dy = gate * ds and the deterministic gate gradient.
+    drop = (seed, site, p): dropout on y, s = res + (keep ? tanh(alpha) / (1 - p) : 0) * y, through
+    lvl_gated_add_layernorm_train_drop / _bwd_drop; the backward regenerates the mask from ctx.drop."""
 
     @staticmethod
-    def forward(ctx, res, y, alpha, gamma, beta, eps):
+    def forward(ctx, res, y, alpha, gamma, beta, eps, drop=None):
         res = res if res.is_contiguous() else res.contiguous()
-        rows, D = res.shape
         g, b = ops._f32(gamma), ops._f32(beta)
         gate = _tanh_gate(alpha)
         if y is not None:
             y = y if y.is_contiguous() else y.contiguous()
-        s = torch.empty_like(res) if y is not None else None
-        h = torch.empty_like(res)
-        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
-        C.require_device(res, y, g, b)
-        C.check(C.lib().lvl_gated_add_layernorm_train(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(b), float(eps),
-                                                      C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows, D,
-                                                      C.dtype_code(res), C.stream_ptr()), 'lvl_gated_add_layernorm_train')
+        s, h, mean, rstd = ops.add_ln_fwd_raw(res, y, gate, g, b, eps, drop)
         ctx.save_for_backward(res if s is None else s, y if gate is not None else None, gate, g, mean, rstd)
         ctx.meta = (y is not None, None if alpha is None else alpha.dtype, gamma.dtype, beta.dtype)
+        ctx.drop = drop
         return h if s is None else (s, h)
 
     @staticmethod
@@ -611,26 +606,17 @@ class _GatedAddLnFn(torch.autograd.Function):
         s, y, gate, g, mean, rstd = ctx.saved_tensors
         has_y, adt, gdt, bdt = ctx.meta
         dadd, dh = (grads if has_y else (None, grads[0]))
-        rows, D = s.shape
         if dh is None:
             dh = torch.zeros_like(s)
         dh = dh if dh.is_contiguous() else dh.contiguous()
         if dadd is not None and not dadd.is_contiguous():
             dadd = dadd.contiguous()
-        ds = torch.empty_like(s)
-        dy = torch.empty_like(s) if gate is not None else None
-        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
-        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
-        dgate = torch.empty(1, dtype=torch.float32, device=s.device) if gate is not None else None
-        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
-        C.check(C.lib().lvl_gated_add_layernorm_bwd(C.ptr(dh), C.ptr(s), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(mean),
-                                                    C.ptr(rstd), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma),
-                                                    C.ptr(dbeta), C.ptr(dgate), C.ptr(ws), rows, D, C.dtype_code(s),
-                                                    C.stream_ptr()), 'lvl_gated_add_layernorm_bwd')
+        ds, dy, dgamma, dbeta, dgate = ops.add_ln_bwd_raw(dh, s, y, gate, g, mean, rstd, dadd, ctx.drop)
         dalpha = None
         if gate is not None:
             dalpha = (dgate * (1.0 - gate * gate)).reshape(()).to(adt)
-        return ds, ((dy if gate is not None else ds) if has_y else None), dalpha, dgamma.to(gdt), dbeta.to(bdt), None
+        # an ungated add without dropout has no dy of its own: it is ds
+        return ds, ((ds if dy is None else dy) if has_y else None), dalpha, dgamma.to(gdt), dbeta.to(bdt), None, None
 
 
 class _ActFn(torch.autograd.Function):
@@ -658,34 +644,6 @@ class _ActFn(torch.autograd.Function):
 CROSS_ATTN_BWD_MAX_KEYS = 256
 
 
-class _CrossAttnRowsFn(torch.autograd.Function):
-    """lvl_cross_attn_rows_fwd / lvl_cross_attn_rows_bwd: q [rows, D] over kv [rows / qrep, Tk, 2 D]."""
-
-    @staticmethod
-    def forward(ctx, q, kv, qrep, heads):
-        if q.dtype != torch.bfloat16 or kv.shape[1] > CROSS_ATTN_BWD_MAX_KEYS:
-            raise C.HipExtensionError(f'decoder cross-attention backward is built for bf16 and at most '
-                                      f'{CROSS_ATTN_BWD_MAX_KEYS} image tokens per clip (got {q.dtype}, {kv.shape[1]})')
-        q = q if q.is_contiguous() else q.contiguous()
-        kv = kv if kv.is_contiguous() else kv.contiguous()
-        C.require_device(q, kv)
-        out = cross_attn_rows_raw(q, kv, qrep, heads)
-        ctx.save_for_backward(q, kv)
-        ctx.cfg = (qrep, heads)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, kv = ctx.saved_tensors
-        qrep, heads = ctx.cfg
-        dout = dout if dout.is_contiguous() else dout.contiguous()
-        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        C.check(C.lib().lvl_cross_attn_rows_bwd(C.ptr(q), C.ptr(kv), C.ptr(dout), C.ptr(dq), C.ptr(dkv), q.shape[0], qrep,
-                                                kv.shape[1], heads, C.dtype_code(q), C.stream_ptr()),
-                'lvl_cross_attn_rows_bwd')
-        return dq, dkv, None, None
-
-
 class _DropoutFn(torch.autograd.Function):
     """out = keep ? x / (1 - p) : 0 (lvl_dropout_apply; the embedding site); the backward is the same call on the gradient."""
 
@@ -709,64 +667,16 @@ class _DropoutFn(torch.autograd.Function):
         return _DropoutFn._apply(dout, ctx.drop), None, None, None
 
 
-class _GatedAddLnDropFn(torch.autograd.Function):
-    """_GatedAddLnFn with dropout on y: s = res + (keep ? tanh(alpha) / (1 - p) : 0) * y, h = LayerNorm(s) -> (s, h).
-    lvl_gated_add_layernorm_train_drop / _bwd_drop; the mask is regenerated from ctx.drop = (seed, site, p)."""
-
-    @staticmethod
-    def forward(ctx, res, y, alpha, gamma, beta, eps, seed, site, p):
-        res = res if res.is_contiguous() else res.contiguous()
-        y = y if y.is_contiguous() else y.contiguous()
-        rows, D = res.shape
-        g, b = ops._f32(gamma), ops._f32(beta)
-        gate = _tanh_gate(alpha)
-        s, h = torch.empty_like(res), torch.empty_like(res)
-        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
-        C.require_device(res, y, g, b)
-        C.check(C.lib().lvl_gated_add_layernorm_train_drop(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(b), float(eps),
-                                                           C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows, D, seed, site, p,
-                                                           C.dtype_code(res), C.stream_ptr()),
-                'lvl_gated_add_layernorm_train_drop')
-        ctx.save_for_backward(s, y if gate is not None else None, gate, g, mean, rstd)
-        ctx.meta = (None if alpha is None else alpha.dtype, gamma.dtype, beta.dtype)
-        ctx.drop = (seed, site, p)
-        return s, h
-
-    @staticmethod
-    def backward(ctx, dadd, dh):
-        s, y, gate, g, mean, rstd = ctx.saved_tensors
-        adt, gdt, bdt = ctx.meta
-        seed, site, p = ctx.drop
-        rows, D = s.shape
-        if dh is None:
-            dh = torch.zeros_like(s)
-        dh = dh if dh.is_contiguous() else dh.contiguous()
-        if dadd is not None and not dadd.is_contiguous():
-            dadd = dadd.contiguous()
-        ds, dy = torch.empty_like(s), torch.empty_like(s)
-        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
-        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
-        dgate = torch.empty(1, dtype=torch.float32, device=s.device) if gate is not None else None
-        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
-        C.check(C.lib().lvl_gated_add_layernorm_bwd_drop(C.ptr(dh), C.ptr(s), C.ptr(y), C.ptr(gate), C.ptr(g), C.ptr(mean),
-                                                         C.ptr(rstd), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma),
-                                                         C.ptr(dbeta), C.ptr(dgate), C.ptr(ws), rows, D, seed, site, p,
-                                                         C.dtype_code(s), C.stream_ptr()), 'lvl_gated_add_layernorm_bwd_drop')
-        dalpha = None
-        if gate is not None:
-            dalpha = (dgate * (1.0 - gate * gate)).reshape(()).to(adt)
-        return ds, dy, dalpha, dgamma.to(gdt), dbeta.to(bdt), None, None, None, None
-
-
 def _off_ptr(t, elements):
     return C._c.c_void_p(t.data_ptr() + elements * t.element_size())
 
 
-class _AttnRowsDropFn(torch.autograd.Function):
-    """lvl_attn_rows_drop_fwd / _bwd, dropout on the attention probabilities. kv given: the cross-attention, q [rows, D] over
-    kv [rows / qrep, Tk, 2 D]. kv None: the causal self-attention on q = qkv [B L, 3 D] with qrep = L positions per caption
-    (keys and values are its own thirds; the gradient comes back as dqkv)."""
+class _RowsAttnFn(torch.autograd.Function):
+    """The decoder's rows attention. kv given: the cross-attention, q [rows, D] over kv [rows / qrep, Tk, 2 D]. kv None: the
+    causal self-attention on q = qkv [B L, 3 D] with qrep = L positions per caption (keys and values are its own thirds;
+    the gradient comes back as dqkv); built only with dropout.
+    drop None: lvl_cross_attn_rows_fwd / _bwd. drop = (seed, site, p): dropout on the attention probabilities,
+    lvl_attn_rows_drop_fwd / _bwd on the same operands as strides."""
 
     @staticmethod
     def _layout(q, kv, qrep, heads):
@@ -776,9 +686,15 @@ class _AttnRowsDropFn(torch.autograd.Function):
         return C.ptr(kv), _off_ptr(kv, D), kv.shape[0], kv.shape[1], D, 2 * D, kv.shape[1] * 2 * D, 0
 
     @staticmethod
-    def forward(ctx, q, kv, qrep, heads, seed, site, p):
+    def forward(ctx, q, kv, qrep, heads, drop=None):
         keys = qrep if kv is None else kv.shape[1]
-        if q.dtype != torch.bfloat16 or keys > ATTN_DROP_MAX_KEYS:
+        if drop is None:
+            if kv is None:
+                raise C.HipExtensionError('decoder rows attention: the causal form (kv None) is built with dropout only')
+            if q.dtype != torch.bfloat16 or keys > CROSS_ATTN_BWD_MAX_KEYS:
+                raise C.HipExtensionError(f'decoder cross-attention backward is built for bf16 and at most '
+                                          f'{CROSS_ATTN_BWD_MAX_KEYS} image tokens per clip (got {q.dtype}, {keys})')
+        elif q.dtype != torch.bfloat16 or keys > ATTN_DROP_MAX_KEYS:
             raise C.HipExtensionError(f'decoder attention with attn_pdrop > 0 is built for bf16 and at most '
                                       f'{ATTN_DROP_MAX_KEYS} keys (caption positions / image tokens per clip); got '
                                       f'{q.dtype}, {keys}')
@@ -786,28 +702,36 @@ class _AttnRowsDropFn(torch.autograd.Function):
         if kv is not None:
             kv = kv if kv.is_contiguous() else kv.contiguous()
         C.require_device(q, kv)
-        k, v, contexts, Tk, qs, kvs, kvc, causal = _AttnRowsDropFn._layout(q, kv, qrep, heads)
-        out = torch.empty(q.shape[0], heads * 64, dtype=q.dtype, device=q.device)
-        C.check(C.lib().lvl_attn_rows_drop_fwd(C.ptr(q), k, v, C.ptr(out), contexts, qrep, Tk, heads, qs, kvs, kvc, causal,
-                                               seed, site, p, C.dtype_code(q), C.stream_ptr()), 'lvl_attn_rows_drop_fwd')
+        if drop is None:
+            out = cross_attn_rows_raw(q, kv, qrep, heads)
+        else:
+            k, v, contexts, Tk, qs, kvs, kvc, causal = _RowsAttnFn._layout(q, kv, qrep, heads)
+            out = torch.empty(q.shape[0], heads * 64, dtype=q.dtype, device=q.device)
+            C.check(C.lib().lvl_attn_rows_drop_fwd(C.ptr(q), k, v, C.ptr(out), contexts, qrep, Tk, heads, qs, kvs, kvc, causal,
+                                                   *drop, C.dtype_code(q), C.stream_ptr()), 'lvl_attn_rows_drop_fwd')
         ctx.save_for_backward(q, kv)
-        ctx.cfg = (qrep, heads, seed, site, p)
+        ctx.cfg = (qrep, heads, drop)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, kv = ctx.saved_tensors
-        qrep, heads, seed, site, p = ctx.cfg
+        qrep, heads, drop = ctx.cfg
         D = heads * 64
         dout = dout if dout.is_contiguous() else dout.contiguous()
-        k, v, contexts, Tk, qs, kvs, kvc, causal = _AttnRowsDropFn._layout(q, kv, qrep, heads)
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv) if kv is not None else None
-        dk, dv = (_off_ptr(dq, D), _off_ptr(dq, 2 * D)) if kv is None else (C.ptr(dkv), _off_ptr(dkv, D))
-        C.check(C.lib().lvl_attn_rows_drop_bwd(C.ptr(q), k, v, C.ptr(dout), C.ptr(dq), dk, dv, contexts, qrep, Tk, heads, qs,
-                                               kvs, kvc, causal, seed, site, p, C.dtype_code(q), C.stream_ptr()),
-                'lvl_attn_rows_drop_bwd')
-        return dq, dkv, None, None, None, None, None
+        if drop is None:
+            C.check(C.lib().lvl_cross_attn_rows_bwd(C.ptr(q), C.ptr(kv), C.ptr(dout), C.ptr(dq), C.ptr(dkv), q.shape[0], qrep,
+                                                    kv.shape[1], heads, C.dtype_code(q), C.stream_ptr()),
+                    'lvl_cross_attn_rows_bwd')
+        else:
+            k, v, contexts, Tk, qs, kvs, kvc, causal = _RowsAttnFn._layout(q, kv, qrep, heads)
+            dk, dv = (_off_ptr(dq, D), _off_ptr(dq, 2 * D)) if kv is None else (C.ptr(dkv), _off_ptr(dkv, D))
+            C.check(C.lib().lvl_attn_rows_drop_bwd(C.ptr(q), k, v, C.ptr(dout), C.ptr(dq), dk, dv, contexts, qrep, Tk, heads,
+                                                   qs, kvs, kvc, causal, *drop, C.dtype_code(q), C.stream_ptr()),
+                    'lvl_attn_rows_drop_bwd')
+        return dq, dkv, None, None, None
 
 
 class _LmHeadFn(torch.autograd.Function):
@@ -878,7 +802,7 @@ class _TrainOps:
     def self_attn(self, i, qkv, L):
         """The causal self-attention of block i on qkv [B L, 3D]: ops.causal_attention, or with attn_pdrop the rows kernel."""
         if self.p_attn:
-            return _AttnRowsDropFn.apply(qkv, None, L, self.heads, self.seed, 1 + 6 * i + 3, self.p_attn)
+            return _RowsAttnFn.apply(qkv, None, L, self.heads, (self.seed, 1 + 6 * i + 3, self.p_attn))
         return ops.causal_attention(qkv.reshape(-1, L, 3 * self.D), self.heads).reshape(-1, self.D)
 
     def gemm(self, x2, m, act=None):
@@ -887,7 +811,7 @@ class _TrainOps:
 
     def add_ln(self, res, y, alpha, ln):
         if y is not None and self.p_resid:
-            return _GatedAddLnDropFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps, self.seed, self.site, self.p_resid)
+            return _GatedAddLnFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps, (self.seed, self.site, self.p_resid))
         out = _GatedAddLnFn.apply(res, y, alpha, ln.weight, ln.bias, self.eps)
         return out if y is not None else (res, out)
 
@@ -899,8 +823,8 @@ class _TrainOps:
         if isinstance(qrep, PackedRows):              # the rectangle's (ctx, h, i, j) index serves the dropout site
             return qrep.around(lambda rect: self.cross_attn(rect, kv, qrep.longest), q)
         if self.p_attn:
-            return _AttnRowsDropFn.apply(q, kv, qrep, self.heads, self.seed, self.site, self.p_attn)
-        return _CrossAttnRowsFn.apply(q, kv, qrep, self.heads)
+            return _RowsAttnFn.apply(q, kv, qrep, self.heads, (self.seed, self.site, self.p_attn))
+        return _RowsAttnFn.apply(q, kv, qrep, self.heads)
 
     def logits(self, h2, rows=None):
         if rows is None:

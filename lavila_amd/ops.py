@@ -1740,10 +1740,13 @@ def causal_attention(qkv, heads, bias=None):
 
 class _KeymaskAttnFn(torch.autograd.Function):
     """lvl_keymask_attn_fwd / _bwd on three separate tensors: q [B, Lq, D] (Lq query rows per sample; Lq = 1 is the row-0
-    form), k / v [B, Tk, D], keymask uint8 [B, Tk] (non-zero = visible) or None."""
+    form), k / v [B, Tk, D], keymask uint8 [B, Tk] (non-zero = visible) or None.
+    drop = (idx_qrep, seed, site, p): dropout on the probabilities (lvl_keymask_attn_drop_fwd / _bwd). No mask is saved: the
+    backward regenerates it from ctx.drop; idx_qrep = query rows per sample of the FULL call, so that the row-0 form (Lq = 1,
+    idx_qrep = L) draws the mask elements of row 0 of the full call."""
 
     @staticmethod
-    def forward(ctx, q, k, v, keymask, heads):
+    def forward(ctx, q, k, v, keymask, heads, drop=None):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         C.require_device(q, k, v, keymask)
         B, Tk, D = k.shape
@@ -1756,8 +1759,13 @@ class _KeymaskAttnFn(torch.autograd.Function):
             raise C.HipExtensionError(f'key-masked attention: the mask must be uint8 [{B}, {Tk}]')
         qrep = q.numel() // (B * D) if B else 1
         out = torch.empty_like(q)
-        C.check(C.lib().lvl_keymask_attn_fwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(keymask), C.ptr(out), B, qrep, Tk, heads, D, D,
-                                             Tk * D, Tk, C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_fwd')
+        ctx.fwd, ctx.bwd, ctx.drop = 'lvl_keymask_attn_fwd', 'lvl_keymask_attn_bwd', ()
+        if drop is not None:
+            idx_qrep, seed, site, p = drop
+            ctx.fwd, ctx.bwd = 'lvl_keymask_attn_drop_fwd', 'lvl_keymask_attn_drop_bwd'
+            ctx.drop = (int(idx_qrep), int(seed), int(site), float(p))
+        C.check(getattr(C.lib(), ctx.fwd)(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(keymask), C.ptr(out), B, qrep, Tk, heads, D, D,
+                                          Tk * D, Tk, *ctx.drop, C.dtype_code(q), C.stream_ptr()), ctx.fwd)
         ctx.save_for_backward(q, k, v)
         ctx.keymask = keymask                  # a byte mask (no gradient, not an output): kept as a plain attribute
         ctx.cfg = (B, qrep, Tk, heads, D)
@@ -1770,63 +1778,63 @@ class _KeymaskAttnFn(torch.autograd.Function):
         dout = dout.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         ws = C.workspace('keymask_attn_bwd', B * qrep * H, Tk, q.device)
-        C.check(C.lib().lvl_keymask_attn_bwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(ctx.keymask), C.ptr(dout), C.ptr(dq),
-                                             C.ptr(dk), C.ptr(dv), C.ptr(ws), B, qrep, Tk, H, D, D, Tk * D, Tk,
-                                             C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_bwd')
-        return dq, dk, dv, None, None
+        C.check(getattr(C.lib(), ctx.bwd)(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(ctx.keymask), C.ptr(dout), C.ptr(dq), C.ptr(dk),
+                                          C.ptr(dv), C.ptr(ws), B, qrep, Tk, H, D, D, Tk * D, Tk, *ctx.drop, C.dtype_code(q),
+                                          C.stream_ptr()), ctx.bwd)
+        return dq, dk, dv, None, None, None
 
 
-def keymask_attention(q, k, v, keymask, heads):
+def keymask_attention(q, k, v, keymask, heads, drop=None):
     """Bidirectional attention whose keys are hidden per sample (DistilBERT under an attention_mask): softmax over the
-    visible keys of each sample, exact zeros for hidden ones; keymask uint8 [B, Tk], non-zero = visible, None = all."""
-    return _KeymaskAttnFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads)
+    visible keys of each sample, exact zeros for hidden ones; keymask uint8 [B, Tk], non-zero = visible, None = all.
+    drop = (idx_qrep, seed, site, p): dropout p on the probabilities, mask element ((((b * heads + h) * idx_qrep + i) << s) | j
+    of (seed, site) -- include/lavila_hip.h, the text tower's mask contract."""
+    return _KeymaskAttnFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads, drop)
 
 
-class _KeymaskAttnDropFn(torch.autograd.Function):
-    """_KeymaskAttnFn with dropout on the probabilities (lvl_keymask_attn_drop_fwd / _bwd). No mask is saved: the backward
-    regenerates it from ctx.drop = (idx_qrep, seed, site, p); idx_qrep = query rows per sample of the FULL call, so that the
-    row-0 form (Lq = 1, idx_qrep = L) draws the mask elements of row 0 of the full call."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, keymask, heads, idx_qrep, seed, site, p):
-        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        C.require_device(q, k, v, keymask)
-        B, Tk, D = k.shape
-        if D != heads * 64:
-            raise C.HipExtensionError(f'key-masked attention: width {D} != heads*64 ({heads} heads)')
-        if q.shape[0] != B or q.shape[-1] != D or v.shape != k.shape or q.dtype != k.dtype or v.dtype != k.dtype:
-            raise C.HipExtensionError(f'key-masked attention: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, '
-                                      f'v {tuple(v.shape)} {v.dtype} do not belong together')
-        if keymask is not None and (keymask.dtype != torch.uint8 or tuple(keymask.shape) != (B, Tk)):
-            raise C.HipExtensionError(f'key-masked attention: the mask must be uint8 [{B}, {Tk}]')
-        qrep = q.numel() // (B * D) if B else 1
-        out = torch.empty_like(q)
-        ctx.drop = (int(idx_qrep), int(seed), int(site), float(p))
-        C.check(C.lib().lvl_keymask_attn_drop_fwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(keymask), C.ptr(out), B, qrep, Tk, heads,
-                                                  D, D, Tk * D, Tk, *ctx.drop, C.dtype_code(q), C.stream_ptr()),
-                'lvl_keymask_attn_drop_fwd')
-        ctx.save_for_backward(q, k, v)
-        ctx.keymask = keymask
-        ctx.cfg = (B, qrep, Tk, heads, D)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v = ctx.saved_tensors
-        B, qrep, Tk, H, D = ctx.cfg
-        dout = dout.contiguous()
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        ws = C.workspace('keymask_attn_bwd', B * qrep * H, Tk, q.device)
-        C.check(C.lib().lvl_keymask_attn_drop_bwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(ctx.keymask), C.ptr(dout), C.ptr(dq),
-                                                  C.ptr(dk), C.ptr(dv), C.ptr(ws), B, qrep, Tk, H, D, D, Tk * D, Tk, *ctx.drop,
-                                                  C.dtype_code(q), C.stream_ptr()), 'lvl_keymask_attn_drop_bwd')
-        return dq, dk, dv, None, None, None, None, None, None
+def add_ln_fwd_raw(res, y, gate, gamma, beta, eps, drop=None, row_index_stride=None):
+    """One add + LayerNorm forward on contiguous rows: s = res + gate * y (gate: one f32 on the device, None = 1; y None =
+    no add), h = LayerNorm(s) -> (s or None without y, h, mean, rstd). drop None: lvl_gated_add_layernorm_train.
+    drop = (seed, site, p): dropout on y, lvl_gated_add_layernorm_train_drop, or with a row_index_stride (and no gate)
+    lvl_dropout_add_layernorm_fwd."""
+    C.require_device(res, y, gamma, beta)
+    rows, D = _rows_cols(res)
+    s = torch.empty_like(res) if y is not None else None
+    h = torch.empty_like(res)
+    mean = torch.empty(rows, dtype=torch.float32, device=res.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+    mid = (C.ptr(gamma), C.ptr(beta), float(eps), C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd), rows, D)
+    end = (C.dtype_code(res), C.stream_ptr())
+    if drop is None:
+        name, args = 'lvl_gated_add_layernorm_train', (C.ptr(gate), *mid, *end)
+    elif row_index_stride is None:
+        name, args = 'lvl_gated_add_layernorm_train_drop', (C.ptr(gate), *mid, *drop, *end)
+    else:
+        name, args = 'lvl_dropout_add_layernorm_fwd', (*mid, row_index_stride, *drop, *end)
+    C.check(getattr(C.lib(), name)(C.ptr(res), C.ptr(y), *args), name)
+    return s, h, mean, rstd
 
 
-def keymask_attention_drop(q, k, v, keymask, heads, idx_qrep, seed, site, p):
-    """keymask_attention with dropout p on the probabilities: mask element ((((b * heads + h) * idx_qrep + i) << s) | j of
-    (seed, site) -- include/lavila_hip.h, the text tower's mask contract."""
-    return _KeymaskAttnDropFn.apply(lowp(q), lowp(k), lowp(v), keymask, heads, idx_qrep, seed, site, p)
+def add_ln_bwd_raw(dh, s, y, gate, gamma, mean, rstd, dadd, drop=None, row_index_stride=None):
+    """The backward of add_ln_fwd_raw from its kept sum and statistics -> (ds, dy, dgamma, dbeta, dgate): lvl_gated_add_
+    layernorm_bwd, _bwd_drop or lvl_dropout_add_layernorm_bwd. dgate is None without a gate; dy is None for an ungated add
+    without dropout (it is ds)."""
+    rows, D = _rows_cols(s)
+    ds = torch.empty_like(s)
+    dy =torch.empty_like(s) if (gate is not None or drop is not None) else None
+    dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
+    dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
+    dgate = torch.empty(1, dtype=torch.float32, device=s.device) if gate is not None else None
+    ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
+    stats = (C.ptr(gamma), C.ptr(mean), C.ptr(rstd), C.ptr(dadd), C.ptr(ds), C.ptr(dy), C.ptr(dgamma), C.ptr(dbeta))
+    end = (C.dtype_code(s), C.stream_ptr())
+    if row_index_stride is not None:
+        name, args = 'lvl_dropout_add_layernorm_bwd', (*stats, C.ptr(ws), rows, D, row_index_stride, *drop, *end)
+    else:
+        name = 'lvl_gated_add_layernorm_bwd' if drop is None else 'lvl_gated_add_layernorm_bwd_drop'
+        args = (C.ptr(y), C.ptr(gate), *stats, C.ptr(dgate), C.ptr(ws), rows, D, *(drop or ()), *end)
+    C.check(getattr(C.lib(), name)(C.ptr(dh), C.ptr(s), *args), name)
+    return ds, dy, dgamma, dbeta, dgate
 
 
 class _DropoutAddLnFn(torch.autograd.Function):
@@ -1836,16 +1844,9 @@ class _DropoutAddLnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, res, y, gamma, beta, eps, row_index_stride, seed, site, p):
         res, y = res.contiguous(), y.contiguous()
-        rows, D = _rows_cols(res)
-        g, b = _f32(gamma), _f32(beta)
-        C.require_device(res, y, g, b)
-        s, h = torch.empty_like(res), torch.empty_like(res)
-        mean = torch.empty(rows, dtype=torch.float32, device=res.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=res.device)
+        g = _f32(gamma)
         ctx.drop = (int(row_index_stride), int(seed), int(site), float(p))
-        C.check(C.lib().lvl_dropout_add_layernorm_fwd(C.ptr(res), C.ptr(y), C.ptr(g), C.ptr(b), float(eps), C.ptr(s), C.ptr(h),
-                                                      C.ptr(mean), C.ptr(rstd), rows, D, *ctx.drop, C.dtype_code(res),
-                                                      C.stream_ptr()), 'lvl_dropout_add_layernorm_fwd')
+        s, h, mean, rstd = add_ln_fwd_raw(res, y, None, g, _f32(beta), eps, ctx.drop[1:], ctx.drop[0])
         ctx.save_for_backward(s, g, mean, rstd)
         ctx.pdt = (gamma.dtype, beta.dtype)
         return h
@@ -1853,15 +1854,7 @@ class _DropoutAddLnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh):
         s, g, mean, rstd = ctx.saved_tensors
-        rows, D = _rows_cols(s)
-        dh = dh.contiguous()
-        ds, dy = torch.empty_like(s), torch.empty_like(s)
-        dgamma = torch.empty(D, dtype=torch.float32, device=s.device)
-        dbeta = torch.empty(D, dtype=torch.float32, device=s.device)
-        ws = C.workspace('gated_add_layernorm_bwd', rows, D, s.device)
-        C.check(C.lib().lvl_dropout_add_layernorm_bwd(C.ptr(dh), C.ptr(s), C.ptr(g), C.ptr(mean), C.ptr(rstd), None, C.ptr(ds),
-                                                      C.ptr(dy), C.ptr(dgamma), C.ptr(dbeta), C.ptr(ws), rows, D, *ctx.drop,
-                                                      C.dtype_code(s), C.stream_ptr()), 'lvl_dropout_add_layernorm_bwd')
+        ds, dy, dgamma, dbeta, _ = add_ln_bwd_raw(dh.contiguous(), s, None, None, g, mean, rstd, None, ctx.drop[1:], ctx.drop[0])
         return ds, dy, dgamma.to(ctx.pdt[0]), dbeta.to(ctx.pdt[1]), None, None, None, None, None
 
 

@@ -38,6 +38,43 @@ def test_cabi_exports_every_declared_symbol():
         assert not [e for e in exported if e.startswith('_Z') and 'lvl' in e], 'mangled internals exported'
 
 
+def test_cabi_signatures_match_the_header_prototypes():
+    """_cabi.SIGNATURES is written by hand: every entry has the argument count of its prototype in include/lavila_hip.h and
+    the same class per argument and for the result (pointer, int, int64_t, float, uint32_t, uint64_t). A wrong class is not
+    an error at the call: ctypes would truncate an int64_t stride to 32 bits, or shift every later argument."""
+    from lavila_amd import _cabi
+    hdr = open(os.path.join(ROOT, 'include', 'lavila_hip.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    hdr = re.sub(r'//[^\n]*', '', hdr)
+    scalars = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'uint32_t': ctypes.c_uint32,
+               'uint64_t': ctypes.c_uint64}
+
+    def c_class(decl, named):
+        """'const float* gamma' -> 'pointer', 'int64_t rows' -> 'int64_t'; `named`: the last word is the argument's name."""
+        if '*' in decl:
+            return 'pointer'
+        words = [w for w in decl.split() if w != 'const']
+        words = words[:-1] if named else words
+        assert len(words) == 1 and words[0] in scalars, f'a type this test does not know: {decl!r}'
+        return words[0]
+
+    def ctypes_class(t):
+        if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+            return 'pointer'
+        (name,) = [k for k, v in scalars.items() if v is t]
+        return name
+
+    protos = re.findall(r'([A-Za-z_][\w\s\*]*?)\b(lvl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', hdr)
+    assert {p[1] for p in protos} == set(_cabi.SIGNATURES) and len(protos) == len(_cabi.SIGNATURES)
+    for ret, name, args in protos:
+        args = [a.strip() for a in args.split(',')] if args.strip() not in ('', 'void') else []
+        restype, argtypes = _cabi.SIGNATURES[name]
+        assert ctypes_class(restype) == c_class(ret, named=False), f'{name}: result'
+        assert len(argtypes) == len(args), f'{name}: {len(args)} arguments in the header, {len(argtypes)} in SIGNATURES'
+        for i, (a, t) in enumerate(zip(args, argtypes)):
+            assert ctypes_class(t) == c_class(a, named=True), f'{name}: argument {i} ({a})'
+
+
 def test_workspace_queries_are_host_only_and_shape_aware():
     """lvl_workspace_floats is pure host code: every op the header names answers without a GPU, unknown ops and
     shapes the weight-gradient kernel cannot tile answer -1 (the caller then keeps the library GEMM)."""

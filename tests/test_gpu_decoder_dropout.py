@@ -5,6 +5,8 @@
   * lvl_dropout_apply, the gated add + LayerNorm pair and the rows attention pair with dropout: p = 0 against the entry
     points without dropout (torch.equal), p > 0 against float64 torch with the explicit mask at the bounds of
     tests/test_gpu_narrator_train.py (2^-7 of the largest magnitude), exact cases, run-to-run bit identity
+  * the autograd Functions (_GatedAddLnFn, _RowsAttnFn), with and without `drop`, against the raw calls they stand for
+    (torch.equal, forward and backward)
   * one training step of the narrator against the unmodified reference under the same masks (tests/golden/narrator_dropout.pt)
   * the switch: nothing changes with it off, with all probabilities 0, in .eval() or under no_grad
 
@@ -326,12 +328,115 @@ def test_attn_rows_drop_single_key_is_exact():
     assert torch.equal(dqkv[:, 2 * D:].reshape(B, H, 64), torch.where(keep, 2 * do.reshape(B, H, 64), zero))
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# 4b. the autograd Functions make the raw calls: one Function per family, with and without `drop`
+# ----------------------------------------------------------------------------------------------------------------------
+DROP = (SEED, 8, 0.5)
+
+
+@pytest.mark.parametrize('form,drop', [('gated', None), ('gated', DROP), ('ungated', None), ('ungated', DROP), ('no_y', None)])
+def test_gated_add_ln_function_makes_the_raw_calls(form, drop):
+    """_GatedAddLnFn, forward and backward, gives the bits of lvl_gated_add_layernorm_train / _bwd without `drop` and of
+    _train_drop / _bwd_drop with it, on the same operands; no_y is the first norm of the stack (h alone, no sum kept)."""
+    from lavila_amd import gpt2_gated as G
+    C = _C()
+    lib = C.lib()
+    rows, D, eps = 5, 192, 1e-5
+    g = torch.Generator().manual_seed(4100)
+    res, y, dh, dadd = (_bf((rows, D), g)[0] for _ in range(4))
+    y = None if form == 'no_y' else y
+    gamma = (1.0 + 0.2 * torch.randn(D, generator=g)).to(DEV)
+    beta = (0.1 * torch.randn(D, generator=g)).to(DEV)
+    alpha = torch.tensor(0.7, device=DEV) if form == 'gated' else None
+    gate = None if alpha is None else torch.tanh(alpha).reshape(1)
+    code, tail = C.dtype_code(res), () if drop is None else drop
+    s, h = torch.full_like(res, NAN) if y is not None else None, torch.full_like(res, NAN)
+    mean, rstd = torch.full((rows,), NAN, device=DEV), torch.full((rows,), NAN, device=DEV)
+    fwd = lib.lvl_gated_add_layernorm_train if drop is None else lib.lvl_gated_add_layernorm_train_drop
+    C.check(fwd(C.ptr(res), C.ptr(y), C.ptr(gate), C.ptr(gamma), C.ptr(beta), eps, C.ptr(s), C.ptr(h), C.ptr(mean), C.ptr(rstd),
+                rows, D, *tail, code, C.stream_ptr()), 'forward')
+    kept = res if s is None else s
+    ds = torch.full_like(res, NAN)
+    dy = torch.full_like(res, NAN) if (gate is not None or drop is not None) else None
+    dg, db = torch.full((D,), NAN, device=DEV), torch.full((D,), NAN, device=DEV)
+    dgate = torch.full((1,), NAN, device=DEV) if gate is not None else None
+    ws = torch.full((lib.lvl_workspace_floats(b'gated_add_layernorm_bwd', rows, D),), NAN, device=DEV)
+    bwd = lib.lvl_gated_add_layernorm_bwd if drop is None else lib.lvl_gated_add_layernorm_bwd_drop
+    C.check(bwd(C.ptr(dh), C.ptr(kept), C.ptr(y if gate is not None else None), C.ptr(gate), C.ptr(gamma), C.ptr(mean),
+                C.ptr(rstd), C.ptr(dadd if y is not None else None), C.ptr(ds), C.ptr(dy), C.ptr(dg), C.ptr(db), C.ptr(dgate),
+                C.ptr(ws), rows, D, *tail, code, C.stream_ptr()), 'backward')
+    torch.cuda.synchronize()
+
+    ins = [t.clone().requires_grad_(True) if t is not None else None for t in (res, y, alpha, gamma, beta)]
+    out = G._GatedAddLnFn.apply(*ins, eps) if drop is None else G._GatedAddLnFn.apply(*ins, eps, drop)
+    if y is None:
+        assert torch.equal(out, h)
+        out.backward(dh)
+    else:
+        assert torch.equal(out[0], s) and torch.equal(out[1], h)
+        torch.autograd.backward(out, (dadd, dh))
+    assert not torch.isnan(h).any() and not torch.isnan(ds).any()
+    assert torch.equal(ins[0].grad, ds)
+    if y is not None:
+        assert torch.equal(ins[1].grad, ds if dy is None else dy)       # an ungated add without dropout: dy is ds
+    if alpha is not None:
+        assert torch.equal(ins[2].grad, (dgate * (1.0 - gate * gate)).reshape(()))
+    assert torch.equal(ins[3].grad, dg) and torch.equal(ins[4].grad, db)
+
+
+@pytest.mark.parametrize('drop', [None, (SEED, 13, 0.5)], ids=['plain', 'p0.5'])
+def test_rows_attn_function_makes_the_raw_calls_cross(drop):
+    """_RowsAttnFn on the image layout: lvl_cross_attn_rows_fwd / _bwd without `drop`, lvl_attn_rows_drop_fwd / _bwd with it."""
+    from lavila_amd import gpt2_gated as G
+    C = _C()
+    contexts, qrep, H, Tk = 2, 5, 2, 37
+    D, rows = H * 64, contexts * qrep
+    g = torch.Generator().manual_seed(4200)
+    q, kv, do = _bf((rows, D), g)[0], _bf((contexts, Tk, 2 * D), g)[0], _bf((rows, D), g)[0]
+    dq, dkv = torch.full_like(q, NAN), torch.full_like(kv, NAN)
+    if drop is None:
+        out = torch.full((rows, D), NAN, dtype=BF, device=DEV)
+        C.check(C.lib().lvl_cross_attn_rows_fwd(C.ptr(q), C.ptr(kv), C.ptr(out), rows, qrep, Tk, H, C.dtype_code(q),
+                                                C.stream_ptr()), 'lvl_cross_attn_rows_fwd')
+        C.check(C.lib().lvl_cross_attn_rows_bwd(C.ptr(q), C.ptr(kv), C.ptr(do), C.ptr(dq), C.ptr(dkv), rows, qrep, Tk, H,
+                                                C.dtype_code(q), C.stream_ptr()), 'lvl_cross_attn_rows_bwd')
+        torch.cuda.synchronize()
+    else:
+        out = _run_attn(q, C.ptr(kv), _off(kv, D), do, dq, C.ptr(dkv), _off(dkv, D), contexts, qrep, Tk, H, D, 2 * D,
+                        Tk * 2 * D, 0, drop[1], drop[2], (rows, D))
+    qa, kva = q.clone().requires_grad_(True), kv.clone().requires_grad_(True)
+    got = G._RowsAttnFn.apply(qa, kva, qrep, H) if drop is None else G._RowsAttnFn.apply(qa, kva, qrep, H, drop)
+    got.backward(do)
+    assert not torch.isnan(out).any() and not torch.isnan(dq).any() and not torch.isnan(dkv).any()
+    assert torch.equal(got, out) and torch.equal(qa.grad, dq) and torch.equal(kva.grad, dkv)
+
+
+def test_rows_attn_function_makes_the_raw_calls_causal():
+    """_RowsAttnFn without kv: the causal self-attention on qkv through lvl_attn_rows_drop_fwd / _bwd; it needs `drop`."""
+    from lavila_amd import gpt2_gated as G
+    C = _C()
+    B, L, H, site, p = 2, 5, 2, 4, 0.5
+    D, rows = H * 64, B * L
+    g = torch.Generator().manual_seed(4300)
+    qkv, do = _bf((rows, 3 * D), g, 1.5)[0], _bf((rows, D), g)[0]
+    dqkv = torch.full_like(qkv, NAN)
+    out = _run_attn(qkv, _off(qkv, D), _off(qkv, 2 * D), do, dqkv, _off(dqkv, D), _off(dqkv, 2 * D), B, L, L, H, 3 * D, 3 * D,
+                    L * 3 * D, 1, site, p, (rows, D))
+    xa = qkv.clone().requires_grad_(True)
+    got = G._RowsAttnFn.apply(xa, None, L, H, (SEED, site, p))
+    got.backward(do)
+    assert not torch.isnan(out).any() and not torch.isnan(dqkv).any()
+    assert torch.equal(got, out) and torch.equal(xa.grad, dqkv)
+    with pytest.raises(C.HipExtensionError, match='dropout'):
+        G._RowsAttnFn.apply(xa, None, L, H)
+
+
 def test_attn_rows_drop_refuses_more_than_256_keys():
     from lavila_amd import gpt2_gated as G
     C = _C()
     qkv = torch.zeros(257, 192, dtype=BF, device=DEV, requires_grad=True)
     with pytest.raises(C.HipExtensionError, match='256'):
-        G._AttnRowsDropFn.apply(qkv, None, 257, 1, SEED, 4, 0.1)
+        G._RowsAttnFn.apply(qkv, None, 257, 1, (SEED, 4, 0.1))
     out = torch.zeros(257, 64, dtype=BF, device=DEV)
     with pytest.raises(C.HipExtensionError, match='256'):
         C.check(C.lib().lvl_attn_rows_drop_fwd(C.ptr(qkv), _off(qkv, 64), _off(qkv, 128), C.ptr(out), 1, 257, 257, 1, 192, 192,

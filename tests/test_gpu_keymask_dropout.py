@@ -361,6 +361,46 @@ def test_dropout_add_layernorm_p0_is_the_undropped_train_pair(rows, D, dt):
         assert torch.equal(a, b.cpu()), name
 
 
+@pytest.mark.parametrize('p', [None, 0.5], ids=['plain', 'p0.5'])
+@pytest.mark.parametrize('form', ['full', 'row0'])
+@pytest.mark.parametrize('dt', [BF, torch.float32], ids=['bf16', 'f32'])
+def test_keymask_function_makes_the_raw_calls(dt, form, p):
+    """ops._KeymaskAttnFn, forward and backward, gives the bits of lvl_keymask_attn_fwd / _bwd without `drop` and of
+    lvl_keymask_attn_drop_fwd / _bwd with it, on the same operands: the full form and the row-0 form (Lq = 1, idx_qrep = L),
+    the last two keys of sample 1 hidden."""
+    from lavila_amd import ops
+    C = _C()
+    L = C.lib()
+    B, Lk, H, site = 2, 5, 2, 3
+    D, Lq = H * 64, (1 if form == 'row0' else 5)
+    g = torch.Generator().manual_seed(5100)
+    q, k, v, do = (torch.randn(*s, generator=g).to(dt).to(DEV) for s in ((B, Lq, D), (B, Lk, D), (B, Lk, D), (B, Lq, D)))
+    mask = torch.ones(B, Lk, dtype=torch.uint8)
+    mask[1, -2:] = 0
+    mask = mask.to(DEV)
+    drop = None if p is None else (Lk, SEED, site, p)
+    tail = () if drop is None else drop
+    code = C.LVL_BF16 if dt == BF else C.LVL_F32
+    out, dq, dk, dv = (torch.full_like(t, NAN) for t in (q, q, k, v))
+    ws = torch.full((L.lvl_workspace_floats(b'keymask_attn_bwd', B * Lq * H, Lk) + 64,), NAN, device=DEV)
+    fwd, bwd = (L.lvl_keymask_attn_fwd, L.lvl_keymask_attn_bwd) if drop is None else (L.lvl_keymask_attn_drop_fwd,
+                                                                                     L.lvl_keymask_attn_drop_bwd)
+    C.check(fwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(mask), C.ptr(out), B, Lq, Lk, H, D, D, Lk * D, Lk, *tail, code,
+                C.stream_ptr()), 'forward')
+    C.check(bwd(C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(mask), C.ptr(do), C.ptr(dq), C.ptr(dk), C.ptr(dv), C.ptr(ws), B, Lq, Lk, H,
+                D, D, Lk * D, Lk, *tail, code, C.stream_ptr()), 'backward')
+    torch.cuda.synchronize()
+    for t in (out, dq, dk, dv):
+        assert not torch.isnan(t).any(), 'an addressed element was not written'
+    qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))
+    got = ops._KeymaskAttnFn.apply(qa, ka, va, mask, H) if drop is None else ops._KeymaskAttnFn.apply(qa, ka, va, mask, H, drop)
+    got.backward(do)
+    assert torch.equal(got, out) and torch.equal(qa.grad, dq) and torch.equal(ka.grad, dk) and torch.equal(va.grad, dv)
+    assert not dk[1, -2:].any() and not dv[1, -2:].any(), 'dk / dv rows of hidden keys must be exact zeros'
+    # the one public function is that Function
+    assert torch.equal(ops.keymask_attention(q, k, v, mask, H, drop), out)
+
+
 def test_error_codes():
     """p outside [0, 1), misaligned pointers, idx_qrep < qrep and a bad row index stride return LVL_EINVAL without a launch."""
     C = _C()

@@ -159,7 +159,7 @@ def test_training_primitives_walk_the_same_plan(variant, monkeypatch):
     monkeypatch.setattr(G, '_Conv1DFn', fn(lambda x2, w, b: x2 @ w + b))
     monkeypatch.setattr(G, '_GatedAddLnFn', fn(gated_add_ln))
     monkeypatch.setattr(G, '_ActFn', fn(lambda u, which: O.gelu_new(u) if which == C.ACT_GELU_NEW else O.sq_relu(u)))
-    monkeypatch.setattr(G, '_CrossAttnRowsFn', fn(cross_attn))
+    monkeypatch.setattr(G, '_RowsAttnFn', fn(cross_attn))
     monkeypatch.setattr(G, '_LmHeadFn', fn(lambda h2, w: h2 @ w.t()))
     monkeypatch.setattr(G._TrainOps, 'dtype', torch.float32)
     monkeypatch.setattr(ops, 'text_embed', lambda *a: None)

@@ -80,7 +80,7 @@ def child_kernels(B, steps, warmup):
 
     def attn(p):
         def run():
-            o = (ops.keymask_attention_drop(q, k, v, mask, H, L, seed, 1, p) if p else ops.keymask_attention(q, k, v, mask, H))
+            o = ops.keymask_attention(q, k, v, mask, H, (L, seed, 1, p) if p else None)
             o.backward(do)
         return run
 

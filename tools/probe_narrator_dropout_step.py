@@ -105,16 +105,16 @@ def time_kernels(batch=32, length=77, heads=12, keys=256, p=0.1, reps=50):
 
     pair('gated add + LayerNorm, without dropout', lambda: G._GatedAddLnFn.apply(res, y, alpha, gamma, beta, 1e-5),
          (res, y), (dadd, dh))
-    pair(f'gated add + LayerNorm, p = {p}', lambda: G._GatedAddLnDropFn.apply(res, y, alpha, gamma, beta, 1e-5, seed, 8, p),
+    pair(f'gated add + LayerNorm, p = {p}', lambda: G._GatedAddLnFn.apply(res, y, alpha, gamma, beta, 1e-5, (seed, 8, p)),
          (res, y), (dadd, dh))
-    pair(f'cross-attention ({length} x {keys}), without dropout', lambda: G._CrossAttnRowsFn.apply(q, kv, length, heads),
+    pair(f'cross-attention ({length} x {keys}), without dropout', lambda: G._RowsAttnFn.apply(q, kv, length, heads),
          (q, kv), (do,))
-    pair(f'cross-attention ({length} x {keys}), p = {p}', lambda: G._AttnRowsDropFn.apply(q, kv, length, heads, seed, 7, p),
+    pair(f'cross-attention ({length} x {keys}), p = {p}', lambda: G._RowsAttnFn.apply(q, kv, length, heads, (seed, 7, p)),
          (q, kv), (do,))
     pair(f'causal self-attention (L = {length}), without dropout: ops.causal_attention',
          lambda: ops.causal_attention(qkv.reshape(batch, length, 3 * D), heads).reshape(rows, D), (qkv,), (do,))
     pair(f'causal self-attention (L = {length}), p = {p}: rows kernel, causal',
-         lambda: G._AttnRowsDropFn.apply(qkv, None, length, heads, seed, 4, p), (qkv,), (do,))
+         lambda: G._RowsAttnFn.apply(qkv, None, length, heads, (seed, 4, p)), (qkv,), (do,))
     x = res.detach()
     cases.append((f'lvl_dropout_apply (embedding site), p = {p}', lambda: G._DropoutFn._apply(x, (seed, 0, p))))
     out = []
