@@ -14,8 +14,21 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'liblavila_hip.so')
 
 LVL_F32, LVL_BF16 = 0, 1
 ATTN_SPACE, ATTN_TIME = 0, 1
-EPI_BIAS, EPI_BIAS_QUICKGELU, EPI_QUICKGELU_BWD, EPI_BIAS_RESIDUAL, EPI_BIAS_QUICKGELU_DERIV, EPI_MUL_AUX_COLSUM = 0, 1, 2, 3, 4, 5
-EPI_BIAS_GELU, EPI_GELU_BWD, EPI_BIAS_GELU_DERIV = 6, 7, 8      # the exact (erf) GELU twins of epilogues 1, 2, 4
+# The epilogues of lvl_linear_tn (LVL_EPI_* of the header; csrc/gemm_tn_kernel.h holds the library's table):
+# name -> (code, two_out: writes aux_out, colsum: reads aux_in and leaves column sums, f32: exists in the f32-class mode).
+# 6-8 are the exact (erf) GELU twins of 1, 2, 4. Every name is a module constant too (C.EPI_BIAS, ...).
+TN_EPILOGUES = {
+    'EPI_BIAS': (0, False, False, True),
+    'EPI_BIAS_QUICKGELU': (1, True, False, True),
+    'EPI_QUICKGELU_BWD': (2, False, True, True),
+    'EPI_BIAS_RESIDUAL': (3, False, False, True),
+    'EPI_BIAS_QUICKGELU_DERIV': (4, True, False, False),
+    'EPI_MUL_AUX_COLSUM': (5, False, True, False),
+    'EPI_BIAS_GELU': (6, True, False, True),
+    'EPI_GELU_BWD': (7, False, True, True),
+    'EPI_BIAS_GELU_DERIV': (8, True, False, False),
+}
+globals().update({_name: _row[0] for _name, _row in TN_EPILOGUES.items()})
 LN_PLAIN, LN_GENERAL = 1, 2          # flags of lvl_layernorm_*_mixed
 ACT_GELU_NEW, ACT_SQRELU, ACT_GELU_ERF = 0, 1, 2
 

@@ -1050,4 +1050,81 @@ int launch_tn(const void* x, const void* w, const float* bias, void* y, void* au
   return LVL_OK;
 }
 
+// ---- The epilogues as data: one row per LVL_EPI_* value --------------------------------------------------------------------
+// What lvl_linear_tn requires of a call, what its debug twins (GM_AUDIT / GM_TRACE) launch and which kernels a unit
+// instantiates all follow from a row; an epilogue is added here and as one case of its unit's tn_launch.
+enum { TN_UNIT_MFMA, TN_UNIT_GELU };      // gemm_tn_mfma.hip | gemm_tn_gelu.hip
+struct TnEpilogue {
+  bool bias, aux_out, aux_in;             // takes a bias | writes aux_out | reads aux_in (an operand it does not take is passed as null)
+  bool colpart;                           // leaves [2 * tiles_m][N] column partials to reduce: needs colsum and ws
+  bool f32;                               // exists in the f32-class mode (the others keep act'(u) in bf16: bf16 only)
+  int unit;                               // the translation unit that instantiates its kernels
+  const char* name;                       // in refusal texts
+};
+constexpr TnEpilogue kTnEpilogues[] = {
+    /* 0 LVL_EPI_BIAS                 */ {true, false, false, false, true, TN_UNIT_MFMA, "plain"},
+    /* 1 LVL_EPI_BIAS_QUICKGELU       */ {true, true, false, false, true, TN_UNIT_MFMA, "QuickGELU"},
+    /* 2 LVL_EPI_QUICKGELU_BWD        */ {false, false, true, true, true, TN_UNIT_MFMA, "QuickGELU-backward"},
+    /* 3 LVL_EPI_BIAS_RESIDUAL        */ {true, false, true, false, true, TN_UNIT_MFMA, "residual"},
+    /* 4 LVL_EPI_BIAS_QUICKGELU_DERIV */ {true, true, false, false, false, TN_UNIT_MFMA, "QuickGELU + derivative"},
+    /* 5 LVL_EPI_MUL_AUX_COLSUM       */ {false, false, true, true, false, TN_UNIT_MFMA, "multiply-by-aux"},
+    /* 6 LVL_EPI_BIAS_GELU            */ {true, true, false, false, true, TN_UNIT_GELU, "GELU"},
+    /* 7 LVL_EPI_GELU_BWD             */ {false, false, true, true, true, TN_UNIT_GELU, "GELU-backward"},
+    /* 8 LVL_EPI_BIAS_GELU_DERIV      */ {true, true, false, false, false, TN_UNIT_GELU, "GELU + derivative"},
+};
+static_assert(sizeof(kTnEpilogues) / sizeof(kTnEpilogues[0]) == LVL_EPI_BIAS_GELU_DERIV + 1, "one row per LVL_EPI_* value");
+constexpr bool tn_epilogue_known(int e) { return e >= LVL_EPI_BIAS && e <= LVL_EPI_BIAS_GELU_DERIV; }
+
+struct TnCall {      // the arguments of launch_tn
+  const void *x, *w;
+  const float* bias;
+  void *y, *aux_out;
+  const void* aux_in;
+  float* colpart;
+  int64_t M;
+  int N, K;
+  unsigned* sched;
+  hipStream_t st;
+};
+
+// (EPI, f32, ms) -> the launch_tn instantiation, for the cases of a unit's tn_launch. MS16: the unit carries the 16x16x32
+// kernels. A mode the table does not give the epilogue is not instantiated: -1, as for an epilogue of the other unit.
+template <int EPI, bool MS16>
+int launch_tn_mode(bool f32, int ms, const TnCall& c) {
+  constexpr TnEpilogue e = kTnEpilogues[EPI];
+  const float* bias = e.bias ? c.bias : nullptr;
+  void* aux_out = e.aux_out ? c.aux_out : nullptr;
+  const void* aux_in = e.aux_in ? c.aux_in : nullptr;
+  if (f32) {
+    if constexpr (e.f32) return launch_tn<EPI, true>(c.x, c.w, bias, c.y, aux_out, aux_in, c.colpart, c.M, c.N, c.K, c.sched, c.st);
+    else return -1;
+  }
+  if constexpr (MS16)
+    if (ms == 16) return launch_tn<EPI, false, 16>(c.x, c.w, bias, c.y, aux_out, aux_in, c.colpart, c.M, c.N, c.K, c.sched, c.st);
+  return launch_tn<EPI>(c.x, c.w, bias, c.y, aux_out, aux_in, c.colpart, c.M, c.N, c.K, c.sched, c.st);
+}
+
+// The argument checks lvl_linear_tn and lvl_linear_tn_ragged share, in one order: null pointers, dtype, (bias_only, the ragged
+// entry: bf16 and LVL_EPI_BIAS), empty problem, tiling (N in n_mod's, K in 64s), 4 GiB, alignment.
+inline int tn_check_args(const char* who, const TnCall& c, int n_mod, int epilogue, int dtype, bool bias_only) {
+  LVL_REQUIRE(c.x && c.w && c.y, "%s: null pointer", who);
+  LVL_REQUIRE(dtype == LVL_BF16 || dtype == LVL_F32, "%s: unknown dtype %d", who, dtype);
+  if (bias_only) {
+    if (dtype != LVL_BF16)
+      return lvl_fail(LVL_ENOSYS, "%s: bf16 only (float32 rows at these widths: lvl_linear_skinny_f32c)", who);
+    LVL_REQUIRE(tn_epilogue_known(epilogue), "%s: unknown epilogue %d", who, epilogue);
+    if (epilogue != LVL_EPI_BIAS)
+      return lvl_fail(LVL_ENOSYS, "%s: epilogue %d is not available on ragged widths (LVL_EPI_BIAS only)", who, epilogue);
+  }
+  LVL_REQUIRE(c.M > 0 && c.N > 0 && c.K > 0, "%s: empty problem", who);
+  if (c.N % n_mod != 0 || c.K % BK != 0)
+    return lvl_fail(LVL_ENOSYS, "%s: no tiling for N=%d K=%d (N %% %d == 0 and K %% 64 == 0 needed)", who, c.N, c.K, n_mod);
+  if ((uint64_t)c.M * c.K * 2 >= (1ull << 32) || (uint64_t)c.N * c.K * 2 >= (1ull << 32))
+    return lvl_fail(LVL_ENOSYS, "%s: operand larger than 4 GiB (32-bit DMA offsets)", who);
+  LVL_REQUIRE(lvl_aligned16(c.x) && lvl_aligned16(c.w) && lvl_aligned16(c.y) && lvl_aligned16(c.bias) &&
+                  lvl_aligned16(c.aux_out) && lvl_aligned16(c.aux_in),
+              "%s: pointers must be 16-byte aligned", who);
+  return LVL_OK;
+}
+
 }  // namespace

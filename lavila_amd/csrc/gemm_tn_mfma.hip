@@ -109,12 +109,20 @@ static int mfma_shape(int /*epilogue*/, int /*N*/, int /*K*/) {
   const int forced = g_mfma_shape.load(std::memory_order_relaxed);
   return forced ? forced : 16;
 }
-template <int EPI>
-static int launch_bf16(const void* x, const void* w, const float* bias, void* y, void* aux_out, const void* aux_in,
-                       float* colpart, int64_t M, int N, int K, unsigned* sched, hipStream_t st) {
-  if (mfma_shape(EPI, N, K) == 16)
-    return launch_tn<EPI, false, 16>(x, w, bias, y, aux_out, aux_in, colpart, M, N, K, sched, st);
-  return launch_tn<EPI>(x, w, bias, y, aux_out, aux_in, colpart, M, N, K, sched, st);
+
+// This unit's kernels: epilogues 0-5 of the table (gemm_tn_kernel.h: kTnEpilogues) in the modes it gives them, on MFMA shape
+// `ms` in bf16 (the f32-class mode runs 32x32x16). The one switch over epilogue codes of this file: lvl_linear_tn, the audit
+// and the trace entries launch through it. -1: not instantiated here.
+static int tn_launch(int epilogue, bool f32, int ms, const TnCall& c) {
+  switch (epilogue) {
+    case LVL_EPI_BIAS: return launch_tn_mode<0, true>(f32, ms, c);
+    case LVL_EPI_BIAS_QUICKGELU: return launch_tn_mode<1, true>(f32, ms, c);
+    case LVL_EPI_QUICKGELU_BWD: return launch_tn_mode<2, true>(f32, ms, c);
+    case LVL_EPI_BIAS_RESIDUAL: return launch_tn_mode<3, true>(f32, ms, c);
+    case LVL_EPI_BIAS_QUICKGELU_DERIV: return launch_tn_mode<4, true>(f32, ms, c);
+    case LVL_EPI_MUL_AUX_COLSUM: return launch_tn_mode<5, true>(f32, ms, c);
+  }
+  return -1;
 }
 
 int64_t lvl_linear_tn_workspace_floats(int64_t M, int64_t N) {
@@ -126,18 +134,11 @@ extern "C" int lvl_linear_tn_trace(const void* x, const void* w, const float* bi
                                    int N, int K, void* stream) {
   return launch_tn<0>(x, w, bias, y, nullptr, nullptr, (float*)trace, M, N, K, nullptr, (hipStream_t)stream);
 }
-// the same with an epilogue (0, 1, 3, 4, 5); epilogue 5: `trace` starts with room for the column partials
+// the same with an epilogue (0, 1, 3, 4, 5), on 32x32x16; epilogue 5: `trace` starts with room for the column partials
 extern "C" int lvl_linear_tn_trace_epi(const void* x, const void* w, const float* bias, void* y, void* aux_out,
                                        const void* aux_in, void* trace, int64_t M, int N, int K, int epilogue, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case 0: return launch_tn<0>(x, w, bias, y, nullptr, nullptr, (float*)trace, M, N, K, nullptr, st);
-    case 1: return launch_tn<1>(x, w, bias, y, aux_out, nullptr, (float*)trace, M, N, K, nullptr, st);
-    case 3: return launch_tn<3>(x, w, bias, y, nullptr, aux_in, (float*)trace, M, N, K, nullptr, st);
-    case 4: return launch_tn<4>(x, w, bias, y, aux_out, nullptr, (float*)trace, M, N, K, nullptr, st);
-    case 5: return launch_tn<5>(x, w, nullptr, y, nullptr, aux_in, (float*)trace, M, N, K, nullptr, st);
-  }
-  return -1;
+  if (epilogue == LVL_EPI_QUICKGELU_BWD) return -1;
+  return tn_launch(epilogue, false, 32, {x, w, bias, y, aux_out, aux_in, (float*)trace, M, N, K, nullptr, (hipStream_t)stream});
 }
 #endif
 
@@ -149,128 +150,36 @@ extern "C" int lvl_linear_tn_audit_cap() { return GM_AUDIT_CAP; }
 extern "C" int lvl_linear_tn_audit(const void* x, const void* w, const float* bias, void* y, void* aux_out,
                                    const void* aux_in, void* audit, uint32_t* sched, int64_t M, int N, int K, int epilogue,
                                    int dtype, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  float* a = (float*)audit;
-  if (dtype == LVL_F32) {
-    switch (epilogue) {
-      case 0: return launch_tn<0, true>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
-      case 1: return launch_tn<1, true>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
-      case 2: return launch_tn<2, true>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
-      case 3: return launch_tn<3, true>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
-    }
-    return -1;
-  }
-  switch (epilogue) {
-    case 0: return launch_bf16<0>(x, w, bias, y, nullptr, nullptr, a, M, N, K, sched, st);
-    case 1: return launch_bf16<1>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
-    case 2: return launch_bf16<2>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
-    case 3: return launch_bf16<3>(x, w, bias, y, nullptr, aux_in, a, M, N, K, sched, st);
-    case 4: return launch_bf16<4>(x, w, bias, y, aux_out, nullptr, a, M, N, K, sched, st);
-    case 5: return launch_bf16<5>(x, w, nullptr, y, nullptr, aux_in, a, M, N, K, sched, st);
-  }
-  return -1;
+  return tn_launch(epilogue, dtype == LVL_F32, mfma_shape(epilogue, N, K),
+                   {x, w, bias, y, aux_out, aux_in, (float*)audit, M, N, K, sched, (hipStream_t)stream});
 }
 #endif
 
 extern "C" int lvl_linear_tn(const void* x, const void* w, const float* bias, void* y, void* aux_out,
                              const void* aux_in, float* colsum, float* ws, uint32_t* sched, int64_t M, int N, int K,
                              int epilogue, int dtype, void* stream) {
-  LVL_REQUIRE(x && w && y, "linear_tn: null pointer");
-  LVL_REQUIRE(dtype == LVL_BF16 || dtype == LVL_F32, "linear_tn: unknown dtype %d", dtype);
-  LVL_REQUIRE(M > 0 && N > 0 && K > 0, "linear_tn: empty problem");
-  if (N % TN != 0 || K % BK != 0)
-    return lvl_fail(LVL_ENOSYS, "linear_tn: no tiling for N=%d K=%d (N %% 256 == 0 and K %% 64 == 0 needed)", N, K);
-  if ((uint64_t)M * K * 2 >= (1ull << 32) || (uint64_t)N * K * 2 >= (1ull << 32))
-    return lvl_fail(LVL_ENOSYS, "linear_tn: operand larger than 4 GiB (32-bit DMA offsets)");
-  LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(w) && lvl_aligned16(y) && lvl_aligned16(bias) &&
-                  lvl_aligned16(aux_out) && lvl_aligned16(aux_in),
-              "linear_tn: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == LVL_F32) {      // f32-class mode: bf16 term images in (K = 3 x the layer's width), float32 out
-    LVL_REQUIRE(K % (3 * BK) == 0, "linear_tn (f32 class): K = %d is not 3 x a multiple of 64", K);
-    switch (epilogue) {
-      case LVL_EPI_BIAS:
-        return launch_tn<0, true>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
-      case LVL_EPI_BIAS_QUICKGELU:
-        LVL_REQUIRE(aux_out != nullptr, "linear_tn: the QuickGELU epilogue writes the pre-activation to aux_out");
-        return launch_tn<1, true>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
-      case LVL_EPI_BIAS_RESIDUAL:
-        LVL_REQUIRE(aux_in != nullptr, "linear_tn: the residual epilogue reads the residual rows from aux_in");
-        return launch_tn<3, true>(x, w, bias, y, nullptr, aux_in, nullptr, M, N, K, sched, st);
-      case LVL_EPI_QUICKGELU_BWD: {
-        LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
-                    "linear_tn: the QuickGELU-backward epilogue needs aux_in, colsum and a workspace");
-        const int rc = launch_tn<2, true>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
-        if (rc != LVL_OK) return rc;
-        const int P = (int)(2 * ((M + TM - 1) / TM));
-        return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
-      }
-      case LVL_EPI_BIAS_GELU:
-        LVL_REQUIRE(aux_out != nullptr, "linear_tn: the GELU epilogue writes the pre-activation to aux_out");
-        return lvl_launch_tn_gelu(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, LVL_EPI_BIAS_GELU, 1, st);
-      case LVL_EPI_GELU_BWD: {
-        LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
-                    "linear_tn: the GELU-backward epilogue needs aux_in, colsum and a workspace");
-        const int rc = lvl_launch_tn_gelu(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, LVL_EPI_GELU_BWD, 1, st);
-        if (rc != LVL_OK) return rc;
-        const int P = (int)(2 * ((M + TM - 1) / TM));
-        return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
-      }
-      case LVL_EPI_BIAS_QUICKGELU_DERIV:
-      case LVL_EPI_MUL_AUX_COLSUM:
-      case LVL_EPI_BIAS_GELU_DERIV:
-        return lvl_fail(LVL_ENOSYS, "linear_tn: epilogue %d is a bf16 epilogue (the f32-class mode keeps the pre-activation: "
-                                    "LVL_EPI_BIAS_QUICKGELU / LVL_EPI_QUICKGELU_BWD, LVL_EPI_BIAS_GELU / LVL_EPI_GELU_BWD)",
-                        epilogue);
-      default:
-        return lvl_fail(LVL_EINVAL, "linear_tn: unknown epilogue %d", epilogue);
-    }
-  }
-  switch (epilogue) {
-    case LVL_EPI_BIAS:
-      return launch_bf16<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
-    case LVL_EPI_BIAS_QUICKGELU:
-      LVL_REQUIRE(aux_out != nullptr, "linear_tn: the QuickGELU epilogue writes the pre-activation to aux_out");
-      return launch_bf16<1>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
-    case LVL_EPI_BIAS_RESIDUAL:
-      LVL_REQUIRE(aux_in != nullptr, "linear_tn: the residual epilogue reads the residual rows from aux_in");
-      return launch_bf16<3>(x, w, bias, y, nullptr, aux_in, nullptr, M, N, K, sched, st);
-    case LVL_EPI_QUICKGELU_BWD: {
-      LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
-                  "linear_tn: the QuickGELU-backward epilogue needs aux_in, colsum and a workspace");
-      const int rc = launch_bf16<2>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
-      if (rc != LVL_OK) return rc;
-      const int P = (int)(2 * ((M + TM - 1) / TM));
-      return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
-    }
-    case LVL_EPI_BIAS_QUICKGELU_DERIV:
-      LVL_REQUIRE(aux_out != nullptr, "linear_tn: the QuickGELU + derivative epilogue writes quickgelu'(u) to aux_out");
-      return launch_bf16<4>(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, st);
-    case LVL_EPI_MUL_AUX_COLSUM: {
-      LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
-                  "linear_tn: the multiply-by-aux epilogue needs aux_in, colsum and a workspace");
-      const int rc = launch_bf16<5>(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, st);
-      if (rc != LVL_OK) return rc;
-      const int P = (int)(2 * ((M + TM - 1) / TM));
-      return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
-    }
-    case LVL_EPI_BIAS_GELU:
-      LVL_REQUIRE(aux_out != nullptr, "linear_tn: the GELU epilogue writes the pre-activation to aux_out");
-      return lvl_launch_tn_gelu(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, LVL_EPI_BIAS_GELU, 0, st);
-    case LVL_EPI_GELU_BWD: {
-      LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
-                  "linear_tn: the GELU-backward epilogue needs aux_in, colsum and a workspace");
-      const int rc = lvl_launch_tn_gelu(x, w, nullptr, y, nullptr, aux_in, ws, M, N, K, sched, LVL_EPI_GELU_BWD, 0, st);
-      if (rc != LVL_OK) return rc;
-      const int P = (int)(2 * ((M + TM - 1) / TM));
-      return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, st);
-    }
-    case LVL_EPI_BIAS_GELU_DERIV:
-      LVL_REQUIRE(aux_out != nullptr, "linear_tn: the GELU + derivative epilogue writes gelu'(u) to aux_out");
-      return lvl_launch_tn_gelu(x, w, bias, y, aux_out, nullptr, nullptr, M, N, K, sched, LVL_EPI_BIAS_GELU_DERIV, 0, st);
-    default:
-      return lvl_fail(LVL_EINVAL, "linear_tn: unknown epilogue %d", epilogue);
-  }
+  TnCall c{x, w, bias, y, aux_out, aux_in, nullptr, M, N, K, sched, (hipStream_t)stream};
+  const int bad = tn_check_args("linear_tn", c, TN, epilogue, dtype, false);
+  if (bad != LVL_OK) return bad;
+  const bool f32 = dtype == LVL_F32;      // f32-class mode: bf16 term images in (K = 3 x the layer's width), float32 out
+  LVL_REQUIRE(!f32 || K % (3 * BK) == 0, "linear_tn (f32 class): K = %d is not 3 x a multiple of 64", K);
+  LVL_REQUIRE(tn_epilogue_known(epilogue), "linear_tn: unknown epilogue %d", epilogue);
+  const TnEpilogue& e = kTnEpilogues[epilogue];
+  if (f32 && !e.f32)
+    return lvl_fail(LVL_ENOSYS, "linear_tn: epilogue %d is a bf16 epilogue (the f32-class mode keeps the pre-activation: "
+                                "LVL_EPI_BIAS_QUICKGELU / LVL_EPI_QUICKGELU_BWD, LVL_EPI_BIAS_GELU / LVL_EPI_GELU_BWD)",
+                    epilogue);
+  LVL_REQUIRE(!e.aux_out || aux_out != nullptr, "linear_tn: the %s epilogue writes to aux_out", e.name);
+  if (e.colpart)
+    LVL_REQUIRE(aux_in != nullptr && colsum != nullptr && ws != nullptr && lvl_aligned16(ws),
+                "linear_tn: the %s epilogue needs aux_in, colsum and a workspace", e.name);
+  LVL_REQUIRE(!e.aux_in || aux_in != nullptr, "linear_tn: the %s epilogue reads aux_in", e.name);
+  if (e.colpart) c.colpart = ws;
+  const int rc = e.unit == TN_UNIT_GELU ? lvl_launch_tn_gelu(x, w, bias, y, aux_out, aux_in, c.colpart, M, N, K, sched, epilogue, f32, c.st)
+                                        : tn_launch(epilogue, f32, mfma_shape(epilogue, N, K), c);
+  if (rc != LVL_OK || !e.colpart) return rc;
+  const int P = (int)(2 * ((M + TM - 1) / TM));      // the column partials -> colsum
+  return lvl_launch_column_reduce(ws, P, N, N, ws + (size_t)P * N, colsum, nullptr, nullptr, c.st);
 }
 
 // Plain GEMM (+ bias) for any N % 64 == 0 (the decoder widths of the GPT-2 XL narrators: 1600, 3200, 4800): the full
@@ -279,26 +188,14 @@ extern "C" int lvl_linear_tn(const void* x, const void* w, const float* bias, vo
 // (gemm_tn_edge.hip) on the same stream. The two launches write disjoint columns of y.
 extern "C" int lvl_linear_tn_ragged(const void* x, const void* w, const float* bias, void* y, uint32_t* sched, int64_t M,
                                     int N, int K, int epilogue, int dtype, void* stream) {
-  LVL_REQUIRE(x && w && y, "linear_tn_ragged: null pointer");
-  LVL_REQUIRE(dtype == LVL_BF16 || dtype == LVL_F32, "linear_tn_ragged: unknown dtype %d", dtype);
-  if (dtype != LVL_BF16)
-    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: bf16 only (float32 rows at these widths: lvl_linear_skinny_f32c)");
-  LVL_REQUIRE(epilogue >= LVL_EPI_BIAS && epilogue <= LVL_EPI_BIAS_GELU_DERIV, "linear_tn_ragged: unknown epilogue %d", epilogue);
-  if (epilogue != LVL_EPI_BIAS)
-    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: epilogue %d is not available on ragged widths (LVL_EPI_BIAS only)", epilogue);
-  LVL_REQUIRE(M > 0 && N > 0 && K > 0, "linear_tn_ragged: empty problem");
-  if (N % 64 != 0 || K % BK != 0)
-    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: no tiling for N=%d K=%d (N %% 64 == 0 and K %% 64 == 0 needed)", N, K);
-  if ((uint64_t)M * K * 2 >= (1ull << 32) || (uint64_t)N * K * 2 >= (1ull << 32))
-    return lvl_fail(LVL_ENOSYS, "linear_tn_ragged: operand larger than 4 GiB (32-bit DMA offsets)");
-  LVL_REQUIRE(lvl_aligned16(x) && lvl_aligned16(w) && lvl_aligned16(y) && lvl_aligned16(bias),
-              "linear_tn_ragged: pointers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
+  const TnCall c{x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, (hipStream_t)stream};
+  const int bad = tn_check_args("linear_tn_ragged", c, 64, epilogue, dtype, true);
+  if (bad != LVL_OK) return bad;
   const int N0 = N / TN * TN;
   if (N0 > 0) {
-    const int rc = launch_bf16<0>(x, w, bias, y, nullptr, nullptr, nullptr, M, N, K, sched, st);
+    const int rc = tn_launch(LVL_EPI_BIAS, false, mfma_shape(LVL_EPI_BIAS, N, K), c);
     if (rc != LVL_OK) return rc;
   }
-  if (N0 < N) return lvl_launch_tn_edge(x, w, bias, y, M, N, K, N0, st);
+  if (N0 < N) return lvl_launch_tn_edge(x, w, bias, y, M, N, K, N0, c.st);
   return LVL_OK;
 }

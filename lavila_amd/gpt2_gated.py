@@ -553,12 +553,12 @@ class _Conv1DFn(torch.autograd.Function):
         w_in_out, w_out_in = ops.weight_copies(weight)
         # forward and input gradient each pick lvl_linear_tn or lvl_linear_tn_ragged by their own shape (c_fc [1600 -> 6400]
         # tiles lvl_linear_tn forward and needs the ragged entry backward); the layer is on the own kernels when both are served
-        ctx.own = ops._tn_rows_ok(rows, n_out, n_in) and (not ctx.needs_input_grad[0] or ops._tn_rows_ok(rows, n_in, n_out))
+        ctx.mode = ops._route(x2, rows, n_out, n_in, ctx.needs_input_grad[0], ragged=(True, True))
         ctx.meta = (weight.dtype, bias.dtype)
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         ctx.save_for_backward(x2, w_in_out)
-        if ctx.own:
-            return ops.linear_tn_rows(x2, w_out_in, ops._f32(bias))
+        if ctx.mode:
+            return ops._gemm(ctx.mode, x2, w_out_in, ops._f32(bias), ragged=True)
         ops.warn_once(('conv1d', n_out, n_in), f'decoder Conv1D [{n_in}->{n_out}] on {rows} rows runs on the '
                       'library GEMM (in % 64 == 0 and out % 256 == 0, or out % 64 == 0 with both >= 256, needed)')
         with torch.autocast('cuda', enabled=False):
@@ -569,15 +569,8 @@ class _Conv1DFn(torch.autograd.Function):
         x2, w_in_out = ctx.saved_tensors
         wdt, bdt = ctx.meta
         dy = dy if dy.is_contiguous() else dy.contiguous()
-        dx = dw = db = None
-        with torch.autocast('cuda', enabled=False):
-            if ctx.needs_input_grad[0]:
-                dx = ops.linear_tn_rows(dy, w_in_out) if ctx.own else dy @ w_in_out.t()
-            if ctx.needs_input_grad[1]:
-                dw = ops._wgrad(x2, dy, wdt)                  # x^T dy: [in, out], the Conv1D layout
-            if ctx.needs_input_grad[2]:
-                db = dy.sum(0, dtype=torch.float32).to(bdt)
-        return dx, dw, db
+        with torch.autocast('cuda', enabled=False):      # swap: dw = x^T dy, [in, out], the Conv1D layout
+            return ops._linear_backward(ctx.needs_input_grad, dy, x2, w_in_out, ctx.mode, wdt, bdt, ragged=True, swap=True)
 
 
 class _GatedAddLnFn(torch.autograd.Function):
@@ -747,12 +740,12 @@ class _LmHeadFn(torch.autograd.Function):
         rows = h2.shape[0]
         w = _pad_rows(weight.detach().to(torch.bfloat16), 256)
         Vp = w.shape[0]
-        ctx.own = ops._tn_ok(rows, Vp, D) and ops._tn_rows_ok(rows, D, Vp)       # the input gradient has N = D: ragged at 1600
+        ctx.mode = ops._route(h2, rows, Vp, D, ragged=(False, True))            # the input gradient has N = D: ragged at 1600
         h2 = h2 if h2.is_contiguous() else h2.contiguous()
         ctx.save_for_backward(h2, w)
         ctx.meta = (V, weight.dtype, padded)
-        if ctx.own:
-            full = ops.linear_tn_raw(h2, w, None, C.EPI_BIAS)
+        if ctx.mode:
+            full = ops._gemm(ctx.mode, h2, w)
         else:
             ops.warn_once(('lm_head', V, D), f'decoder lm_head [{D}->{V}] on {rows} rows runs on the library GEMM')
             with torch.autocast('cuda', enabled=False):
@@ -768,13 +761,11 @@ class _LmHeadFn(torch.autograd.Function):
         else:
             dl = torch.zeros(h2.shape[0], w.shape[0], dtype=torch.bfloat16, device=h2.device)
             dl[:, :V] = dlogits
-        dh = dw = None
+        need = ctx.needs_input_grad
         with torch.autocast('cuda', enabled=False):
-            if ctx.needs_input_grad[0]:
-                dh = ops.linear_tn_rows(dl, w.t().contiguous()) if ctx.own else dl @ w
-            if ctx.needs_input_grad[1]:
-                dw = ops._wgrad(dl, h2, wdt)[:V]
-        return dh, dw, None
+            wt = w.t().contiguous() if (ctx.mode and need[0]) else w.t()
+            dh, dw, _ = ops._linear_backward(need[:2], dl, h2, wt, ctx.mode, wdt, ragged=True)
+        return dh, None if dw is None else dw[:V], None
 
 
 class _TrainOps:

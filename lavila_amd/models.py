@@ -75,12 +75,13 @@ class _ClassifierHeadFn(torch.autograd.Function):
         w = _pad_to(weight.detach().to(torch.bfloat16), 0, _HEAD_TILE)
         wt = _pad_to(w.t(), 0, _HEAD_TILE).contiguous()                   # [D padded, classes padded]
         b = None if bias is None else _pad_to(bias.detach().float(), 0, _HEAD_TILE)
-        ctx.own = ops._tn_ok(rows, w.shape[0], D) and ops._tn_ok(rows, wt.shape[0], wt.shape[1])
+        # the input gradient is a GEMM of its own shape (both widths padded), not the forward's with N and K swapped
+        ctx.mode = ops._route(x, rows, w.shape[0], D, False) and ops._route(x, rows, *wt.shape, False)
         x = x if x.is_contiguous() else x.contiguous()
         ctx.save_for_backward(x, wt)
         ctx.meta = (n, D, weight.dtype, None if bias is None else bias.dtype)
-        if ctx.own:
-            return ops.linear_tn_raw(x, w, b, ops.C.EPI_BIAS)[:, :n]
+        if ctx.mode:
+            return ops._gemm(ctx.mode, x, w, b)[:, :n]
         ops.warn_once(('fc_cls', n, D), f'classifier head [{D}->{n}] on {rows} rows runs on the library GEMM')
         with torch.autocast('cuda', enabled=False):
             return F.linear(x, w[:n], None if b is None else b[:n].to(x.dtype))
@@ -91,15 +92,12 @@ class _ClassifierHeadFn(torch.autograd.Function):
         n, D, wdt, bdt = ctx.meta
         dl = torch.zeros(x.shape[0], wt.shape[1], dtype=torch.bfloat16, device=x.device)
         dl[:, :n] = dlogits
-        dx = dw = db = None
+        db = None
         with torch.autocast('cuda', enabled=False):
-            if ctx.needs_input_grad[0]:
-                dx = (ops.linear_tn_raw(dl, wt, None, ops.C.EPI_BIAS) if ctx.own else dl @ wt.t())[:, :D]
-            if ctx.needs_input_grad[1]:
-                dw = ops._wgrad(dl, x, wdt)[:n]
+            dx, dw, _ = ops._linear_backward(ctx.needs_input_grad[:2], dl, x, wt, ctx.mode, wdt)
             if bdt is not None and ctx.needs_input_grad[2]:
-                db = dlogits.sum(0, dtype=torch.float32).to(bdt)
-        return dx, dw, db
+                db = dlogits.sum(0, dtype=torch.float32).to(bdt)      # of the unpadded columns
+        return None if dx is None else dx[:, :D], None if dw is None else dw[:n], db
 
 
 def _classifier_head(x, fc):

@@ -363,6 +363,56 @@ def _ln_rebuild(saved, shape):
     return layernorm_apply_raw(x, x2, xbias, gamma, beta, mean, rstd).reshape(shape)
 
 
+# The Linear layers' routing rule, GEMM and backward, shared by _LinearFn, _LinearTokenFn, the fused MLP and LayerNorm forms
+# below, and the decoder's and the classifier's Functions (gpt2_gated.py, models.py).
+OWN_BF16, OWN_F32 = 'bf16', 'f32'       # what _route answers; None: the library GEMM
+
+
+def _route(x, rows, n_out, n_in, want_dx=True, ragged=(False, False)):
+    """Which GEMMs run a Linear [n_in -> n_out] on `rows` rows of the activation x: OWN_BF16 (lvl_linear_tn), OWN_F32 (its
+    f32-class mode) or None (the library). The forward must tile, and the input gradient -- N and K swapped -- too if it is
+    wanted. ragged = (forward, input gradient): lvl_linear_tn_ragged may serve that direction (the bf16 layers that say so
+    have no f32-class mode)."""
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        mode, (fwd, bwd) = OWN_BF16, ((_tn_rows_ok if r else _tn_ok) for r in ragged)
+    elif x.is_cuda and x.dtype == torch.float32 and not any(ragged):
+        mode, fwd, bwd = OWN_F32, _tn_ok_f32, _tn_ok_f32
+    else:
+        return None
+    return mode if fwd(rows, n_out, n_in) and (not want_dx or bwd(rows, n_in, n_out)) else None
+
+
+def _gemm(mode, x2, w, bias=None, epilogue=C.EPI_BIAS, aux_in=None, ragged=False):
+    """One own GEMM of a Linear in `mode` (_route) on contiguous rows x2: lvl_linear_tn, in OWN_F32 on the term images of x2
+    against the term images w (weight_copies(f32=True)); ragged: the entry linear_tn_rows picks by the shape."""
+    if mode == OWN_F32:
+        return linear_tn_raw(split3(x2, 0), w, bias, epilogue, aux_in=aux_in, f32=True)
+    if ragged:
+        return linear_tn_rows(x2, w, bias)
+    return linear_tn_raw(x2, w, bias, epilogue, aux_in=aux_in)
+
+
+def _linear_backward(need, dy2, x2, wt, mode, wdt, bdt=None, recipe=None, ragged=False, swap=False):
+    """(dx, dw, db) of y = x W^T (+ b) for the gradient dy2 [rows, out] (contiguous). need: needs_input_grad of (x, W, b).
+    dx = dy2 wt^T on the own GEMMs (`mode`, `ragged`: as _gemm) or, mode None, the library's; wt [in, out] is the transposed
+    weight copy. dw = dy2^T x2 on lvl_linear_wgrad (swap: x2^T dy2, the Conv1D layout) with x2 the kept rows or, recipe (the
+    saved tensors of an LnRecipe), rebuilt right before this GEMM, their only reader, and only if dw is wanted. db (bdt: the
+    bias dtype, None: no bias): float32 column sums of dy2."""
+    if mode == OWN_F32:
+        dy2 = dy2.float()
+    dx = dw = db = None
+    if need[0]:
+        dx = _gemm(mode, dy2, wt, ragged=ragged) if mode else dy2 @ wt.t()
+    if need[1]:
+        if recipe is not None:
+            x2 = _ln_rebuild(recipe, (-1, wt.shape[0]))
+        wgrad = _wgrad_f32 if x2.dtype == torch.float32 else _wgrad
+        dw = wgrad(x2, dy2, wdt) if swap else wgrad(dy2, x2, wdt)
+    if bdt is not None and need[2]:
+        db = dy2.sum(0, dtype=torch.float32).to(bdt)      # f32 accumulation AND f32 result
+    return dx, dw, db
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T (+ b) for token-major activations [rows, in].
 
@@ -377,25 +427,14 @@ class _LinearFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, ln=None):
         x2 = x.reshape(-1, x.shape[-1])
         rows, n_in, n_out = x2.shape[0], x2.shape[1], weight.shape[0]
-        own = (x.dtype == torch.bfloat16 and x.is_cuda and _tn_ok(rows, n_out, n_in)
-               and (not ctx.needs_input_grad[0] or _tn_ok(rows, n_in, n_out)))     # the input gradient swaps N and K
-        ctx.own = own
+        mode = ctx.mode = _route(x, rows, n_out, n_in, ctx.needs_input_grad[0])
         ctx.meta = (weight.dtype, None if bias is None else bias.dtype, x.shape)
-        ctx.f32own = (not own and x.dtype == torch.float32 and x.is_cuda and _tn_ok_f32(rows, n_out, n_in)
-                      and (not ctx.needs_input_grad[0] or _tn_ok_f32(rows, n_in, n_out)))
         ctx.ln = ln is not None
-        if ctx.f32own:          # f32-class mode of the same kernels (the parity configuration)
-            w3, wt3 = weight_copies(weight, f32=True)
-            x2 = x2 if x2.is_contiguous() else x2.contiguous()
-            ctx.save_for_backward(*(ln.saved() if ctx.ln else (x2,)), wt3)
-            y = linear_tn_raw(split3(x2, 0), w3, _f32(bias), C.EPI_BIAS, f32=True)
-            return y.reshape(*x.shape[:-1], n_out)
-        if own:
-            w, wt = weight_copies(weight)
+        if mode:
+            w, wt = weight_copies(weight, mode == OWN_F32)
             x2 = x2 if x2.is_contiguous() else x2.contiguous()
             ctx.save_for_backward(*(ln.saved() if ctx.ln else (x2,)), wt)
-            y = linear_tn_raw(x2, w, _f32(bias), C.EPI_BIAS)
-            return y.reshape(*x.shape[:-1], n_out)
+            return _gemm(mode, x2, w, _f32(bias)).reshape(*x.shape[:-1], n_out)
         if x.dtype == torch.bfloat16 and rows >= 4096:
             warn_once(('linear', n_out, n_in), f'Linear [{n_out},{n_in}] runs on the library GEMM (lvl_linear_tn needs '
                                                'out % 256 == 0 and in % 64 == 0)')
@@ -407,41 +446,23 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        *kept, w = ctx.saved_tensors              # own path: w is the TRANSPOSED copy [in, out]
+        *kept, w = ctx.saved_tensors              # own modes: w is the TRANSPOSED copy [in, out]
         wdt, bdt, xshape = ctx.meta
-        # the weight gradient's operand: kept, or (ln) rebuilt right before its only reader
-        x_rows = (lambda: _ln_rebuild(kept, (-1, xshape[-1]))) if ctx.ln else (lambda: kept[0])
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
-        dx = dw = db = None
         with torch.autocast('cuda', enabled=False):
-            if ctx.f32own:
-                dy2 = dy2.float()
-                if ctx.needs_input_grad[0]:
-                    dx = linear_tn_raw(split3(dy2, 0), w, None, C.EPI_BIAS, f32=True).reshape(xshape)
-                if ctx.needs_input_grad[1]:
-                    dw = _wgrad_f32(dy2, x_rows(), wdt)
-                if bdt is not None and ctx.needs_input_grad[2]:
-                    db = dy2.sum(0).to(bdt)
-                return dx, dw, db, None
-            if ctx.needs_input_grad[0]:
-                dx = (linear_tn_raw(dy2, w, None, C.EPI_BIAS) if ctx.own else dy2 @ w).reshape(xshape)
-            if ctx.needs_input_grad[1]:
-                x2 = x_rows()
-                dw = _wgrad(dy2, x2, wdt) if (ctx.own or x2.dtype != torch.float32) else _wgrad_f32(dy2, x2, wdt)
-                del x2
-            if bdt is not None and ctx.needs_input_grad[2]:
-                db = dy2.sum(0, dtype=torch.float32).to(bdt)      # f32 accumulation AND f32 result
-        return dx, dw, db, None
+            dx, dw, db = _linear_backward(ctx.needs_input_grad, dy2, None if ctx.ln else kept[0], w if ctx.mode else w.t(),
+                                          ctx.mode, wdt, bdt, recipe=kept if ctx.ln else None)
+        return None if dx is None else dx.reshape(xshape), dw, db, None
 
 
 # The activations of the fused MLP: the epilogues of lvl_linear_tn that apply them (keeping u / keeping act'(u) / the backward
 # on a kept u) and the kernel that rebuilds the hidden activation from a kept u (selective recompute). The bf16 backward on a
 # kept DERIVATIVE is LVL_EPI_MUL_AUX_COLSUM for both.
 ACT_QUICKGELU, ACT_GELU = 'quickgelu', 'gelu'
-_MLP_EPILOGUES = {ACT_QUICKGELU: (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV, C.EPI_QUICKGELU_BWD),
-                  ACT_GELU: (C.EPI_BIAS_GELU, C.EPI_BIAS_GELU_DERIV, C.EPI_GELU_BWD)}
+_MLP_EPILOGUES = {act: tuple(C.TN_EPILOGUES[name.format(act.upper())][0] for name in ('EPI_BIAS_{}', 'EPI_BIAS_{}_DERIV', 'EPI_{}_BWD'))
+                  for act in (ACT_QUICKGELU, ACT_GELU)}
 
 
 def _mlp_epilogues(act):
@@ -473,27 +494,13 @@ class _MlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, ln=None, act=ACT_QUICKGELU):
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        f32 = ctx.f32 = x.dtype == torch.float32        # f32-class mode: term images in, float32 u / a / y
-        sel = ctx.sel = ln is not None                  # selective recompute: keep u, neither x (a LayerNorm output) nor a
-        ctx.act = act
-        keep_u, keep_deriv, _ = _mlp_epilogues(act)
-        w1b, w1t = weight_copies(w1, f32)
-        w2b, w2t = weight_copies(w2, f32)
-        a, u = linear_tn_raw(split3(x2, 0) if f32 else x2, w1b, _f32(b1), keep_u if (f32 or sel) else keep_deriv, f32=f32)
-        y = linear_tn_raw(split3(a, 0) if f32 else a, w2b, None, C.EPI_BIAS, f32=f32)
-        if sel:
-            ctx.save_for_backward(*ln.saved(), u, w1t, w2t)
-        else:
-            ctx.save_for_backward(x2, u, a, w1t, w2t)
+        y, saved = _mlp_forward(ctx, x, w1, b1, w2, ln, act)
+        ctx.save_for_backward(*saved)
         ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, x.shape)
         return y.reshape(*x.shape[:-1], w2.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
-        w1dt, b1dt, w2dt, xshape = ctx.meta
         if ctx.sel:
             *kept, u, w1t, w2t = ctx.saved_tensors
             x2 = a = None
@@ -502,10 +509,29 @@ class _MlpFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
-        if ctx.f32:
+        if ctx.mode == OWN_F32:
             dy2 = dy2.float()
         dx, dw1, db1, dw2 = _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept if ctx.sel else None)
         return dx, dw1, db1, dw2, None, None
+
+
+def _mlp_forward(ctx, x, w1, b1, w2, ln, act, b2=None, res2=None):
+    """The two GEMMs of fc2(act(fc1(x) + b1)) shared by _MlpFn and _MlpResidualLayerNormFn (res2: the residual rows fc2 adds
+    in its epilogue, with its bias b2): (fc2's output, what backward keeps of them -- the head of save_for_backward).
+    ctx.mode: bf16, or the f32-class mode (term images in, float32 u / a / y); ctx.sel: selective recompute (ln, the
+    LnRecipe of x): keep u, neither x (a LayerNorm output) nor a."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    mode = ctx.mode = OWN_F32 if x.dtype == torch.float32 else OWN_BF16
+    sel = ctx.sel = ln is not None
+    ctx.act = act
+    keep_u, keep_deriv, _ = _mlp_epilogues(act)
+    w1b, w1t = weight_copies(w1, mode == OWN_F32)
+    w2b, w2t = weight_copies(w2, mode == OWN_F32)
+    a, u = _gemm(mode, x2, w1b, _f32(b1), keep_u if (mode == OWN_F32 or sel) else keep_deriv)
+    y = _gemm(mode, a, w2b, _f32(b2), C.EPI_BIAS if res2 is None else C.EPI_BIAS_RESIDUAL, aux_in=res2)
+    return y, ((*ln.saved(), u, w1t, w2t) if sel else (x2, u, a, w1t, w2t))
 
 
 def _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept, need=(0, 1, 2, 3)):
@@ -516,67 +542,48 @@ def _mlp_backward(ctx, dy2, x2, u, a, w1t, w2t, kept, need=(0, 1, 2, 3)):
     `kept` are rebuilt one after the other, each right before the weight-gradient GEMM that reads it and only if that
     gradient is wanted, so that at most one [rows, 4D] and one [rows, D] rebuilt tensor are alive at a time."""
     w1dt, b1dt, w2dt, xshape = ctx.meta[0], ctx.meta[1], ctx.meta[2], ctx.meta[-1]
-    f32, sel = ctx.f32, ctx.sel
+    mode, sel = ctx.mode, ctx.sel
     gx, gw1, gb1, gw2 = (ctx.needs_input_grad[i] for i in need)
-    wgrad = _wgrad_f32 if f32 else _wgrad
     bwd_on_u = _mlp_epilogues(ctx.act)[2]
-    if f32:
-        du, db1 = linear_tn_raw(split3(dy2, 0), w2t, None, bwd_on_u, aux_in=u, f32=True)
-    else:
-        du, db1 = linear_tn_raw(dy2, w2t, None, bwd_on_u if sel else C.EPI_MUL_AUX_COLSUM, aux_in=u)
+    du, db1 = _gemm(mode, dy2, w2t, None, bwd_on_u if (mode == OWN_F32 or sel) else C.EPI_MUL_AUX_COLSUM, aux_in=u)
     dw2 = None
     if gw2:
         if sel:
             a = quickgelu_apply_raw(u) if ctx.act == ACT_QUICKGELU else gelu_apply_raw(u)
-        dw2 = wgrad(dy2, a, w2dt)
+        dw2 = (_wgrad_f32 if mode == OWN_F32 else _wgrad)(dy2, a, w2dt)
     del a, u
-    if f32:
-        dx = linear_tn_raw(split3(du, 0), w1t, None, C.EPI_BIAS, f32=True).reshape(xshape) if gx else None
-    else:
-        dx = linear_tn_raw(du, w1t, None, C.EPI_BIAS).reshape(xshape) if gx else None
-    dw1 = None
-    if gw1:
-        if sel:
-            x2 = _ln_rebuild(kept, (-1, xshape[-1]))
-        dw1 = wgrad(du, x2, w1dt)
-    return dx, dw1, (db1.to(b1dt) if (b1dt is not None and gb1) else None), dw2
+    dx, dw1, _ = _linear_backward((gx, gw1, False), du, x2, w1t, mode, w1dt, recipe=kept)      # fc1: db1 left the epilogue above
+    return (None if dx is None else dx.reshape(xshape), dw1, (db1.to(b1dt) if (b1dt is not None and gb1) else None), dw2)
 
 
 def _mlp_fused_ok(x, w1, b1, w2):
-    """Whether _MlpFn takes the MLP: bf16 on the benched kernels, or float32 on their f32-class mode."""
+    """Whether _MlpFn takes the MLP: both Linears, forward and input gradient, on the own kernels (bf16, or float32 on their
+    f32-class mode)."""
     rows = x.numel() // x.shape[-1]
-    if (x.dtype == torch.bfloat16 and x.is_cuda and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1])
-            and _tn_ok(rows, w1.shape[1], w1.shape[0]) and _tn_ok(rows, w2.shape[0], w2.shape[1])
-            and _tn_ok(rows, w2.shape[1], w2.shape[0])):
-        return True
-    return (x.dtype == torch.float32 and x.is_cuda and b1 is not None and w1.dtype == torch.float32
-            and _tn_ok_f32(rows, w1.shape[0], w1.shape[1]) and _tn_ok_f32(rows, w1.shape[1], w1.shape[0])
-            and _tn_ok_f32(rows, w2.shape[0], w2.shape[1]) and _tn_ok_f32(rows, w2.shape[1], w2.shape[0]))
-
-
-def mlp_quickgelu(x, w1, b1, w2, ln=None):
-    """fc2(QuickGELU(fc1(x))) minus fc2's bias; fused GEMM epilogues in bf16, composed kernels otherwise.
-    ln: the LnRecipe of x (selective activation recompute: neither x nor the hidden activation is kept by the fused
-    function; the composed form keeps the hidden activation and rebuilds x only)."""
-    x = _act(x)
-    ln = _ln_for(ln, x)
-    if _mlp_fused_ok(x, w1, b1, w2):
-        return _MlpFn.apply(x, w1, b1, w2, ln, ACT_QUICKGELU)      # bf16, or the same fused epilogues in f32-class mode
-    return linear(bias_quick_gelu(linear(x, w1, ln=ln), b1), w2)
+    if b1 is None or (x.dtype == torch.float32 and w1.dtype != torch.float32):
+        return False
+    return _route(x, rows, *w1.shape) is not None and _route(x, rows, *w2.shape) is not None
 
 
 def mlp(x, w1, b1, w2, act, ln=None):
-    """fc2(act(fc1(x))) minus fc2's bias for act = ACT_QUICKGELU (mlp_quickgelu) or ACT_GELU, the exact erf GELU of nn.GELU():
-    the same fused GEMM epilogues (bf16 and f32-class), and where the fused form does not take the shapes or dtypes, the
-    composed form: Linear + bias, the activation as a torch op, Linear. ln: as in mlp_quickgelu."""
+    """fc2(act(fc1(x))) minus fc2's bias for act = ACT_QUICKGELU or ACT_GELU, the exact erf GELU of nn.GELU(): fused GEMM
+    epilogues (bf16 and f32-class), and where the fused form does not take the shapes or dtypes, the composed form: Linear,
+    the activation (bias_quick_gelu / a torch op), Linear.
+    ln: the LnRecipe of x (selective activation recompute: neither x nor the hidden activation is kept by the fused
+    function; the composed form keeps the hidden activation and rebuilds x only)."""
     _mlp_epilogues(act)
-    if act == ACT_QUICKGELU:
-        return mlp_quickgelu(x, w1, b1, w2, ln=ln)
     x = _act(x)
     ln = _ln_for(ln, x)
     if _mlp_fused_ok(x, w1, b1, w2):
-        return _MlpFn.apply(x, w1, b1, w2, ln, ACT_GELU)
+        return _MlpFn.apply(x, w1, b1, w2, ln, act)      # bf16, or the same fused epilogues in f32-class mode
+    if act == ACT_QUICKGELU:
+        return linear(bias_quick_gelu(linear(x, w1, ln=ln), b1), w2)
     return linear(torch.nn.functional.gelu(linear(x, w1, b1, ln=ln)), w2)
+
+
+def mlp_quickgelu(x, w1, b1, w2, ln=None):
+    """mlp with ACT_QUICKGELU (the models' call)."""
+    return mlp(x, w1, b1, w2, ACT_QUICKGELU, ln=ln)
 
 
 def linear_wgrad_raw(dy, x, want_dbias: bool, ws_floats: int = -1):
@@ -632,8 +639,8 @@ def sched_block(device, words=16):
     return pool[0][pool[1]]
 
 
-_TN_TWO_OUT = (C.EPI_BIAS_QUICKGELU, C.EPI_BIAS_QUICKGELU_DERIV, C.EPI_BIAS_GELU, C.EPI_BIAS_GELU_DERIV)      # write aux_out
-_TN_COLSUM = (C.EPI_QUICKGELU_BWD, C.EPI_MUL_AUX_COLSUM, C.EPI_GELU_BWD)      # read aux_in, leave column sums
+_TN_TWO_OUT = tuple(code for code, two_out, _, _ in C.TN_EPILOGUES.values() if two_out)      # write aux_out
+_TN_COLSUM = tuple(code for code, _, colsum, _ in C.TN_EPILOGUES.values() if colsum)        # read aux_in, leave column sums
 
 
 def linear_tn_raw(x, w, bias=None, epilogue=C.EPI_BIAS, aux_in=None, f32=False):
@@ -775,10 +782,9 @@ class _LinearTokenFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
         with torch.autocast('cuda', enabled=False):
-            dx = linear_tn_raw(dy2, wt, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
-            dw = _wgrad(dy2, x2, wdt) if ctx.needs_input_grad[1] else None
+            dx, dw, _ = _linear_backward(ctx.needs_input_grad[:2], dy2, x2, wt, OWN_BF16, wdt)
             dtok = vec_mat(dytoken, weight) if (dytoken is not None and ctx.needs_input_grad[2]) else None
-        return dx, dw, dtok
+        return None if dx is None else dx.reshape(xshape), dw, dtok
 
 
 def linear_with_token(x, weight, xtoken):
@@ -786,8 +792,7 @@ def linear_with_token(x, weight, xtoken):
     are not the own kernels' (the token chain then simply ends: consumers fall back to reducing their rows)."""
     x = _act(x)
     rows, n_in, n_out = x.numel() // x.shape[-1], x.shape[-1], weight.shape[0]
-    if (xtoken is not None and x.dtype == torch.bfloat16 and x.is_cuda and weight.dtype == torch.float32
-            and _tn_ok(rows, n_out, n_in) and _tn_ok(rows, n_in, n_out)):
+    if xtoken is not None and weight.dtype == torch.float32 and _route(x, rows, n_out, n_in) == OWN_BF16:
         return _LinearTokenFn.apply(x, weight, xtoken)
     return linear(x, weight), None
 
@@ -966,13 +971,9 @@ class _LayerNormFn(torch.autograd.Function):
 RESIDUAL_F32 = os.environ.get('LAVILA_RESIDUAL_F32', '0') == '1'
 
 
-def _gemm_input_dtype():
-    """dtype a LayerNorm output takes when it feeds GEMMs: the autocast dtype, or None (= leave as is)."""
-    return autocast_dtype()
-
-
 def _narrow(h):
-    lp = _gemm_input_dtype()
+    """A LayerNorm output that feeds GEMMs takes the autocast dtype (none: it is left as it is)."""
+    lp = autocast_dtype()
     return h.to(lp) if (lp is not None and h.dtype == torch.float32) else h
 
 
@@ -980,7 +981,7 @@ def _mixed_ln(x, y=None):
     """Does this LayerNorm site take the mixed kernels? A float32 stream x, a bf16 branch y (if any), and a consumer that
     wants bf16 rows."""
     return (x.dtype == torch.float32 and x.is_cuda and (y is None or y.dtype == torch.bfloat16)
-            and _gemm_input_dtype() == torch.bfloat16)
+            and autocast_dtype() == torch.bfloat16)
 
 
 def layer_norm(x, weight, bias, eps, stream=False, recipe=False):
@@ -1093,8 +1094,7 @@ def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=N
     x, res = _act(x), lowp(res)
     rows = x.numel() // x.shape[-1]
     n_out, n_in = weight.shape
-    if not (RESIDUAL_EPILOGUE and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and x.is_cuda
-            and _tn_ok(rows, n_out, n_in) and _tn_ok(rows, n_in, n_out)):
+    if not (RESIDUAL_EPILOGUE and res.dtype == torch.bfloat16 and _route(x, rows, n_out, n_in) == OWN_BF16):
         return None
     if xtoken is not None and weight.dtype != torch.float32:
         xtoken = None
@@ -1111,26 +1111,14 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, rec=None, act=ACT_QUICKGELU):
-        x2 = x.reshape(-1, x.shape[-1])
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
         res2 = res.reshape(-1, res.shape[-1])
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
-        ctx.f32 = False
-        sel = ctx.sel = ln is not None       # selective recompute, as in _MlpFn: keep u, neither x nor a
-        w1b, w1t = weight_copies(w1)
-        w2b, w2t = weight_copies(w2)
-        ctx.act = act
-        keep_u, keep_deriv, _ = _mlp_epilogues(act)
-        a, u = linear_tn_raw(x2, w1b, _f32(b1), keep_u if sel else keep_deriv)
-        s = linear_tn_raw(a, w2b, _f32(b2), C.EPI_BIAS_RESIDUAL, aux_in=res2)
+        s, saved = _mlp_forward(ctx, x, w1, b1, w2, ln, act, b2, res2)      # bf16 (the caller's condition)
         g, b = _f32(gamma), _f32(beta)
         h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
         if rec is not None:
             rec.fill(s, None, None, g, b, mean, rstd)
-        if sel:
-            ctx.save_for_backward(*ln.saved(), u, w1t, w2t, s, g, mean, rstd)
-        else:
-            ctx.save_for_backward(x2, u, a, w1t, w2t, s, g, mean, rstd)
+        ctx.save_for_backward(*saved, s, g, mean, rstd)
         ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype, gamma.dtype,
                     beta.dtype, x.shape)
         return s.reshape(res.shape), h.reshape(res.shape)
@@ -1159,10 +1147,7 @@ def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, r
     mlp_quickgelu); recipe: see layer_norm; act: ACT_QUICKGELU or ACT_GELU (see mlp)."""
     _mlp_epilogues(act)
     x, res = _act(x), lowp(res)
-    rows = x.numel() // x.shape[-1]
-    if not (RESIDUAL_EPILOGUE and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and x.is_cuda
-            and b1 is not None and _tn_ok(rows, w1.shape[0], w1.shape[1]) and _tn_ok(rows, w1.shape[1], w1.shape[0])
-            and _tn_ok(rows, w2.shape[0], w2.shape[1]) and _tn_ok(rows, w2.shape[1], w2.shape[0])):
+    if not (RESIDUAL_EPILOGUE and x.dtype == torch.bfloat16 and res.dtype == torch.bfloat16 and _mlp_fused_ok(x, w1, b1, w2)):
         return None
     rec = LnRecipe() if recipe else None
     s, h = _MlpResidualLayerNormFn.apply(x, w1, b1, w2, b2, res, gamma, beta, eps, _ln_for(ln, x), rec, act)

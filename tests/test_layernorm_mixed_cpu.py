@@ -76,9 +76,9 @@ def test_mixed_path_needs_a_float32_stream_a_bf16_branch_and_a_bf16_consumer(mon
         def __init__(self, dtype):
             self.dtype = dtype
     f32, bf16 = Cuda(torch.float32), Cuda(torch.bfloat16)
-    monkeypatch.setattr(ops, '_gemm_input_dtype', lambda: torch.bfloat16)
+    monkeypatch.setattr(ops, 'autocast_dtype', lambda: torch.bfloat16)
     assert ops._mixed_ln(f32) and ops._mixed_ln(f32, bf16)
     assert not ops._mixed_ln(bf16) and not ops._mixed_ln(f32, f32) and not ops._mixed_ln(bf16, bf16)
     assert not ops._mixed_ln(torch.zeros(2, 8))                  # a host tensor
-    monkeypatch.setattr(ops, '_gemm_input_dtype', lambda: None)  # no autocast: a true float32 run
+    monkeypatch.setattr(ops, 'autocast_dtype', lambda: None)  # no autocast: a true float32 run
     assert not ops._mixed_ln(f32) and not ops._mixed_ln(f32, bf16)
