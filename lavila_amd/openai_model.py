@@ -16,9 +16,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-import torch.utils.checkpoint as checkpoint
 
 from . import ops
+from .chain import checkpointed, close, cls_query_attention, compose, take_rows
 from .timesformer import LayerNorm, _like_caller, conv_patch_tokens
 
 
@@ -41,14 +41,6 @@ class _SelfAttentionParams(nn.Module):
         self.out_proj = nn.Linear(d_model, d_model)
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.constant_(self.out_proj.bias, 0.)
-
-
-def _take_rows(t, rows):
-    """The selected row of every sample of [B, L, W]: `rows` is a [B] int64 tensor (the EOT rows of the text tower) or the
-    int 0 (the cls rows of the image tower)."""
-    if isinstance(rows, int):
-        return t[:, rows].contiguous()
-    return t[torch.arange(t.shape[0], device=t.device), rows].contiguous()
 
 
 class ResidualAttentionBlock(nn.Module):
@@ -75,21 +67,15 @@ class ResidualAttentionBlock(nn.Module):
                 raise NotImplementedError('only the causal CLIP text mask (or no mask) is supported')
         self.attn_mask = attn_mask
 
-    def _open(self, res, pend, pend_bias):
-        """(x, ln_1(x)) with x = res + pend + pend_bias: the add of the block before rides in ln_1's kernel."""
-        l1 = self.ln_1
-        if pend is None:
-            return res, ops.layer_norm(res, l1.weight, l1.bias, l1.eps)
-        return ops.add_layer_norm(res, pend, pend_bias, l1.weight, l1.bias, l1.eps, keep_sum=True)
-
     def _mlp_pending(self, x1, h2):
         return x1, ops.mlp_quickgelu(h2, self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight), \
             self.mlp.c_proj.bias
 
     def chain(self, res, pend, pend_bias):
-        """Batch-major block on the fused residual chain (see SpaceTimeBlock.chain)."""
+        """Batch-major block on the fused residual chain (chain.py; see SpaceTimeBlock.chain): the add of the block before
+        rides in ln_1's kernel."""
         l2, at = self.ln_2, self.attn
-        x, h = self._open(res, pend, pend_bias)
+        x, h, _ = close(res, pend, pend_bias, self.ln_1)
         # the GEMM adds the in-proj bias; its gradient comes out of the attention backward (hence the detached copy)
         qkv = ops.linear(h, at.in_proj_weight, at.in_proj_bias.detach())
         tok = None
@@ -102,13 +88,7 @@ class ResidualAttentionBlock(nn.Module):
                                            want_token=True)
         # x + attn(ln_1(x)) (openai_model.py:199): the residual add rides in out_proj's GEMM epilogue when the shapes
         # are the MFMA GEMM's (ops.RESIDUAL_EPILOGUE), ln_2 reads the sum
-        fused = ops.linear_residual_layer_norm(o, at.out_proj.weight, at.out_proj.bias, x, l2.weight, l2.bias, l2.eps,
-                                               xtoken=tok)
-        if fused is not None:
-            x1, h2 = fused
-        else:
-            y = ops.linear(o, at.out_proj.weight)
-            x1, h2 = ops.add_layer_norm(x, y, at.out_proj.bias, l2.weight, l2.bias, l2.eps, keep_sum=True)
+        x1, h2 = ops.linear_add_layer_norm(o, at.out_proj.weight, at.out_proj.bias, x, l2.weight, l2.bias, l2.eps, xtoken=tok)
         return self._mlp_pending(x1, h2)
 
     def chain_rows(self, res, pend, pend_bias, rows):
@@ -119,29 +99,22 @@ class ResidualAttentionBlock(nn.Module):
         No mask (image tower; `rows` must be 0, the cls row, openai_model.py:265): the k | v thirds of the in-proj run on
         every token, the q third, the attention (lvl_cls_attn_*: one query per head), the output projection, ln_2 and the
         MLP on the B cls rows."""
-        l2, at = self.ln_2, self.attn
+        at = self.attn
         if self.attn_mask is None and not (isinstance(rows, int) and rows == 0):
             raise NotImplementedError('unmasked ResidualAttentionBlock.chain_rows: only the cls row (rows=0)')
-        x, h = self._open(res, pend, pend_bias)
+        x, h, _ = close(res, pend, pend_bias, self.ln_1)
         if self.attn_mask is not None:
             o = ops.causal_attention(ops.linear(h, at.in_proj_weight, at.in_proj_bias.detach()), at.num_heads,
                                      bias=at.in_proj_bias)
-            o_rows = _take_rows(o, rows)
+            o_rows = take_rows(o, rows)
         else:
-            D = h.shape[-1]
-            w, bias = at.in_proj_weight, at.in_proj_bias.detach()
-            kv = ops.linear(h, w[D:], bias[D:])                                      # [B, L, 2D]
-            q = ops.linear(h[:, 0].contiguous(), w[:D], bias[:D])                    # [B, D]
-            o_rows = ops.cls_attention(q, kv, at.num_heads, bias=at.in_proj_bias)    # [B, D]
-        y = ops.linear(o_rows, at.out_proj.weight)
-        x1, h2 = ops.add_layer_norm(_take_rows(x, rows), y, at.out_proj.bias, l2.weight, l2.bias, l2.eps, keep_sum=True)
+            o_rows = cls_query_attention(h, at.in_proj_weight, at.in_proj_bias, at.num_heads)      # [B, D]
+        x1, h2, _ = close(x, ops.linear(o_rows, at.out_proj.weight), at.out_proj.bias, self.ln_2, rows=rows)
         return self._mlp_pending(x1, h2)
 
     def forward(self, x: torch.Tensor, use_checkpoint=False):
         """Reference signature: x is [L, N, D] (openai_model.py:206-216)."""
-        xb = x.permute(1, 0, 2).contiguous()
-        x1, y, b = self.chain(xb, None, None)
-        return (x1 + y + b.to(y.dtype)).permute(1, 0, 2)
+        return compose(*self.chain(x.permute(1, 0, 2).contiguous(), None, None)).permute(1, 0, 2)
 
 
 class Transformer(nn.Module):
@@ -160,39 +133,24 @@ class Transformer(nn.Module):
         use_checkpoint: see ops.checkpoint_mode. 'selective' runs the plain path here: at 32-77 positions of width 512 the
         text tower's activations are about 1 % of the video tower's."""
         from .timesformer import CLS_ONLY_LAST_BLOCK
-        use_checkpoint = ops.checkpoint_mode(use_checkpoint) == 'block'
+        step = checkpointed if ops.checkpoint_mode(use_checkpoint) == 'block' else (lambda fn, *a: fn(*a))
         res, pend, pb = x.contiguous(), None, None
         last = len(self.resblocks) - 1
         for i, blk in enumerate(self.resblocks):
             if rows is not None and i == last and CLS_ONLY_LAST_BLOCK:      # only the selected rows leave the tower
-                if use_checkpoint:
-                    res, pend, pb = checkpoint.checkpoint(blk.chain_rows, res, pend, pb, rows, use_reentrant=False)
-                else:
-                    res, pend, pb = blk.chain_rows(res, pend, pb, rows)
-            elif use_checkpoint:
-                res, pend, pb = checkpoint.checkpoint(blk.chain, res, pend, pb, use_reentrant=False)
+                res, pend, pb = step(blk.chain_rows, res, pend, pb, rows)
             else:
-                res, pend, pb = blk.chain(res, pend, pb)
-        if rows is not None:
-            r = res if res.dim() == 2 else _take_rows(res, rows)
-            if pend is None:
-                return ops.layer_norm(r, final_ln.weight, final_ln.bias, final_ln.eps)
-            p = pend if pend.dim() == 2 else _take_rows(pend, rows)
-            return ops.add_layer_norm(r, p, pb, final_ln.weight, final_ln.bias, final_ln.eps, keep_sum=False)[1]
-        if final_ln is None:
-            return res if pend is None else res + pend + pb.to(pend.dtype)
-        if pend is None:
-            return ops.layer_norm(res, final_ln.weight, final_ln.bias, final_ln.eps)
-        return ops.add_layer_norm(res, pend, pb, final_ln.weight, final_ln.bias, final_ln.eps, keep_sum=False)[1]
+                res, pend, pb = step(blk.chain, res, pend, pb)
+        if rows is None and final_ln is None:
+            return compose(res, pend, pb)
+        return close(res, pend, pb, final_ln, keep_sum=False, rows=rows)[1]
 
     def forward(self, x: torch.Tensor, use_checkpoint=False):
         """Reference signature: [L, N, D] -> [L, N, D] (openai_model.py:226-232)."""
         res, pend, pb = x.permute(1, 0, 2).contiguous(), None, None
         for blk in self.resblocks:
             res, pend, pb = blk.chain(res, pend, pb)
-        if pend is not None:
-            res = res + pend + pb.to(pend.dtype)
-        return res.permute(1, 0, 2)
+        return compose(res, pend, pb).permute(1, 0, 2)
 
 
 class VisionTransformer(nn.Module):

@@ -1103,6 +1103,15 @@ def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=N
     return (s, _narrow(h), rec) if recipe else (s, _narrow(h))
 
 
+def linear_add_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=None, recipe=False, keep_sum=True):
+    """(s, h[, recipe]) = (res + Linear(x), LayerNorm(s)): linear_residual_layer_norm where it takes the configuration, else
+    the composed form -- the Linear without its bias, then add_layer_norm with it (keep_sum=False: s may then be None)."""
+    fused = linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=xtoken, recipe=recipe)
+    if fused is not None:
+        return fused
+    return add_layer_norm(res, linear(x, weight), lbias, gamma, beta, eps, keep_sum=keep_sum, recipe=recipe)
+
+
 class _MlpResidualLayerNormFn(torch.autograd.Function):
     """(s, h) = (res + fc2(act(fc1(x) + b1)) + b2, LayerNorm(s)): `x = x + mlp(norm2(x))` of one block and the first
     LayerNorm of the NEXT consumer (timesformer.py:196 / 183; openai_model.py:200 / 199) -- _MlpFn with the residual

@@ -17,9 +17,9 @@ from functools import partial
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-import torch.utils.checkpoint as checkpoint
 
 from . import ops
+from .chain import PendingMlp, ScaledBranch, checkpointed, close, cls_query_attention, compose, triple
 
 
 # LAVILA_CLS_LAST=0 computes the whole last block as the reference does (A/B and debugging)
@@ -254,54 +254,6 @@ class VarAttention(nn.Module):
         return _like_caller(ops.linear(self.core(x, mode, frames, n), self.proj.weight, self.proj.bias), x)
 
 
-class PendingMlp:
-    """A block's `x1 + mlp(norm2(x1))` that has not been computed yet: with ops.RESIDUAL_EPILOGUE the MLP's second GEMM adds
-    the residual in its epilogue and the NEXT consumer's LayerNorm reads the sum, so the MLP is enqueued by that consumer
-    (ops.mlp_residual_layer_norm). Travels in the `pend` slot of the fused residual chain; the fc2 bias in `pend_bias`."""
-
-    __slots__ = ('h', 'mlp', 'ln')
-
-    def __init__(self, h, mlp, ln=None):
-        self.h, self.mlp, self.ln = h, mlp, ln      # ln: the ops.LnRecipe of h (selective recompute), or None
-
-    def materialize(self):
-        """The MLP branch as a tensor (fc2's bias still pending), for consumers that want the composed form."""
-        m = self.mlp
-        return ops.mlp(self.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.act_kind, ln=self.ln)
-
-
-class ScaledBranch:
-    """A branch output that is still to be added as `res + scale[sample] * (y + bias)`: the MLP branch of a block with
-    stochastic depth (timesformer.py:196). Travels in the `pend` slot of the fused residual chain like a tensor; whoever
-    closes the add (_close_pending, the final norm, SpaceTimeBlock.forward) does it with ops.scaled_add_layer_norm."""
-
-    __slots__ = ('y', 'scale')
-
-    def __init__(self, y, scale):
-        self.y, self.scale = y, scale       # scale: [B] float32 (DropPath.sample_scale)
-
-
-def _rows_per_sample(x):
-    return 1 if x.dim() == 2 else x.numel() // (x.shape[0] * x.shape[-1])
-
-
-def _close_pending(res, pend, pend_bias, norm, selective=False):
-    """(s, h) = (res + pend + pend_bias, norm(s)) for a tensor, a PendingMlp or a ScaledBranch in the `pend` slot. selective:
-    (s, h, recipe) with the ops.LnRecipe of h, for the Linear that consumes h; a PendingMlp's own recipe travels with it (a
-    scaled sum has no recipe: (s, h), and the Linear keeps h)."""
-    if isinstance(pend, ScaledBranch):
-        return ops.scaled_add_layer_norm(res, pend.y, pend_bias, pend.scale, _rows_per_sample(res), norm.weight, norm.bias,
-                                         norm.eps)
-    if isinstance(pend, PendingMlp):
-        m = pend.mlp
-        fused = ops.mlp_residual_layer_norm(pend.h, m.fc1.weight, m.fc1.bias, m.fc2.weight, pend_bias, res, norm.weight,
-                                            norm.bias, norm.eps, ln=pend.ln, recipe=selective, act=m.act_kind)
-        if fused is not None:
-            return fused
-        pend = pend.materialize()
-    return ops.add_layer_norm(res, pend, pend_bias, norm.weight, norm.bias, norm.eps, keep_sum=True, recipe=selective)
-
-
 def _video_checkpoint_mode(use_checkpoint):
     """ops.checkpoint_mode for the video tower: None, 'block' or 'selective'."""
     mode = ops.checkpoint_mode(use_checkpoint)
@@ -334,99 +286,84 @@ class SpaceTimeBlock(nn.Module):
         self.norm3 = norm_layer(dim)
         self.attention_style = attention_style
 
-    def _dropping(self):
-        """MLP dropout lives in this training forward: the branches are then materialised (own GEMMs, separate bias / drop
-        passes) instead of riding on the fused chain (timesformer.py:52-58,192-196)."""
-        return self.training and self.mlp.drop.p > 0.
-
     def _stochastic(self):
-        """Stochastic depth (and no MLP dropout) lives in this training forward: the block stays on the fused chain and its
-        two per-sample scaled adds run in the LayerNorm kernels that read them (ops.scaled_add_layer_norm)."""
-        return (self.training and isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0.
-                and not self._dropping())
+        """Stochastic depth lives in this training forward: the block stays on the fused chain and its two per-sample
+        scaled adds run in the LayerNorm kernels that read them (ops.scaled_add_layer_norm)."""
+        return self.training and isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0.
 
-    def _mlp_branch(self, h2):
-        """fc2(act(fc1(h2))) without fc2's bias, which stays pending."""
-        if self.mlp.act_kind is not None:
-            return ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind)
-        return ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight)
-
-    def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False, selective=False):
-        """One block on the fused residual chain.
-
-        The block input is x = res + pend + pend_bias (pend/pend_bias may be None); that add is fused into
-        norm3. Returns (x1, y, y_bias) with the block output = x1 + y + y_bias left *pending* so that the
-        next consumer (next block's norm3 or the final norm) fuses it too.
-        selective (use_checkpoint='selective'): the same kernels in the same order, but norm3 / norm1 / norm2's outputs and
-        the MLP hidden activation are not kept for backward: every LayerNorm hands out the recipe of its output
-        (ops.LnRecipe) and the Linear that consumes the output keeps that instead. A block that is dropping (stochastic
-        depth, MLP dropout) keeps every activation: with stochastic depth it runs the scaled adds below, with MLP
-        dropout its plain path."""
+    def _time_half(self, res, pend, pend_bias, frames, n_per_frame, recipe, sel):
+        """The first half of a block on the chain: x = res + pend + pend_bias closed into norm3, time attention, its
+        projection, norm1 of t = x + time_out. Returns (x, h1, r1): t is never stored; x is handed through so that its second
+        use, x + space_out, sends its gradient into norm1's backward kernel instead of a separate add.
+        recipe: handed to the close (a pending MLP of the block before then keeps neither its input nor its hidden
+        activation); sel: norm3's and norm1's outputs of THIS block are not kept either (r1: the ops.LnRecipe of h1)."""
         if self.attention_style != 'frozen-in-time':
             raise NotImplementedError
-        stoch = self._stochastic()
-        sel = bool(selective) and not self._dropping() and not stoch
-        n3, n1, n2 = self.norm3, self.norm1, self.norm2
-        r3 = r1 = r2 = None
-        if pend is None:
-            x = res
-            h3, *r3 = ops.layer_norm(x, n3.weight, n3.bias, n3.eps, recipe=True) if sel else \
-                (ops.layer_norm(x, n3.weight, n3.bias, n3.eps),)
-        else:
-            # (a pending MLP of the block before is closed here, in that block's mode: its recipe travels with it)
-            x, h3, *r3 = _close_pending(res, pend, pend_bias, n3, selective=sel)
-        r3 = r3[0] if r3 else None
-        ta, sa = self.timeattn, self.attn
-        tok_y = None
+        if self.training and self.mlp.drop.p > 0.:
+            raise NotImplementedError(f'SpaceTimeBlock on the fused residual chain has no MLP dropout: mlp.drop.p = '
+                                      f'{self.mlp.drop.p} must be 0 to train it (no constructor sets it: drop / drop_rate '
+                                      '!= 0 raise)')
+        x, h3, r3 = close(res, pend, pend_bias, self.norm3, recipe=recipe)
+        r3 = r3 if sel else None
+        ta, n1 = self.timeattn, self.norm1
         if hasattr(self, 'alpha_timeattn'):
             o_t = ta.core(h3, 'time', frames, n_per_frame, ln=r3)
-            y_t, b_t = torch.tanh(self.alpha_timeattn).to(o_t.dtype) * ops.linear(o_t, ta.proj.weight, ta.proj.bias), None
+            y_t = torch.tanh(self.alpha_timeattn).to(o_t.dtype) * ops.linear(o_t, ta.proj.weight, ta.proj.bias)
+            b_t = tok_y = None
         else:
             # column-sum tokens (ops.COLSUM_TOKENS): o_t -> projection -> fused add + norm1; the backward hands
             # sum_rows(d o_t) to the attention backward, which needs it for the v third of d(qkv bias)
             o_t, tok_o = ta.core(h3, 'time', frames, n_per_frame, want_token=True, ln=r3)
             (y_t, tok_y), b_t = ops.linear_with_token(o_t, ta.proj.weight, tok_o), ta.proj.bias
         del h3
-        # t = x + time_out is never stored; x is handed through so that its second use below sends its gradient into
-        # norm1's backward kernel instead of a separate add
-        x, h1, *r1 = ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y, recipe=sel)
-        r1 = r1[0] if r1 else None
+        return triple(ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y, recipe=sel))
+
+    def _mlp_pending(self, x1, h2, r2=None, defer=False, scale=None):
+        """(x1, y, fc2 bias): the block output x1 + y + bias with the MLP branch of h2 = norm2(x1) left pending -- for the
+        next consumer to enqueue (PendingMlp: `defer`, ops.RESIDUAL_EPILOGUE, a classified activation, bf16), computed by
+        the fused MLP kernels, or composed around an activation they do not know; under stochastic depth (scale: the
+        branch's per-sample factors) inside a ScaledBranch. fc2's bias stays pending in every form.
+        r2: the ops.LnRecipe of h2 (selective recompute)."""
+        m = self.mlp
+        if m.act_kind is None:
+            y = ops.linear(m.hidden(h2), m.fc2.weight)
+        elif (defer and scale is None and ops.RESIDUAL_EPILOGUE and h2.dtype == torch.bfloat16
+                and x1.dtype == torch.bfloat16):
+            y = PendingMlp(h2, m, r2)
+        else:
+            y = ops.mlp(h2, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.act_kind, ln=r2)
+        return x1, (y if scale is None else ScaledBranch(y, scale)), m.fc2.bias
+
+    def chain(self, res, pend, pend_bias, frames, n_per_frame, defer_mlp=False, selective=False):
+        """One block on the fused residual chain (chain.py).
+
+        The block input is x = res + pend + pend_bias (pend/pend_bias may be None); that add is fused into
+        norm3. Returns (x1, y, y_bias) with the block output = x1 + y + y_bias left *pending* so that the
+        next consumer (next block's norm3 or the final norm) fuses it too.
+        selective (use_checkpoint='selective'): the same kernels in the same order, but norm3 / norm1 / norm2's outputs and
+        the MLP hidden activation are not kept for backward: every LayerNorm hands out the recipe of its output
+        (ops.LnRecipe) and the Linear that consumes the output keeps that instead. A block with stochastic depth keeps every
+        activation and runs the scaled adds below."""
+        stoch = self._stochastic()
+        sel = bool(selective) and not stoch
+        # (a pending MLP of the block before is closed in THIS block's mode: its recipe travels with it)
+        x, h1, r1 = self._time_half(res, pend, pend_bias, frames, n_per_frame, recipe=sel, sel=sel)
+        sa, n2 = self.attn, self.norm2
         if stoch:
             # x1 = x + c_space * (proj(o_s) + bias) inside norm2's kernel, the MLP branch left pending with its own scale: the
-            # time branch above carries no drop path in the reference (timesformer.py:183-196). Masks in the reference's order.
+            # time branch carries no drop path in the reference (timesformer.py:183-196). Masks in the reference's order.
             c_s = self.drop_path.sample_scale(x.shape[0], x.device)
             c_m = self.drop_path.sample_scale(x.shape[0], x.device)
             o_s = sa.core(h1, 'space', frames, n_per_frame)
             del h1
-            x1, h2 = ops.scaled_add_layer_norm(x, ops.linear(o_s, sa.proj.weight), sa.proj.bias, c_s, _rows_per_sample(x),
-                                               n2.weight, n2.bias, n2.eps)
-            return x1, ScaledBranch(self._mlp_branch(h2), c_m), self.mlp.fc2.bias
-        fused = None
-        if not self._dropping():
-            # ops.RESIDUAL_EPILOGUE: x1 leaves the projection GEMM (residual epilogue), norm2 reads it
-            o_s, tok_s = sa.core(h1, 'space', frames, n_per_frame, want_token=True, ln=r1)
-            fused = ops.linear_residual_layer_norm(o_s, sa.proj.weight, sa.proj.bias, x, n2.weight, n2.bias, n2.eps,
-                                                   xtoken=tok_s, recipe=sel)
-        else:
-            o_s = sa.core(h1, 'space', frames, n_per_frame)
+            x1, h2, _ = close(x, ScaledBranch(ops.linear(o_s, sa.proj.weight), c_s), sa.proj.bias, n2)
+            return self._mlp_pending(x1, h2, scale=c_m)
+        # ops.RESIDUAL_EPILOGUE: x1 leaves the projection GEMM (residual epilogue), norm2 reads it
+        o_s, tok_s = sa.core(h1, 'space', frames, n_per_frame, want_token=True, ln=r1)
         del h1
-        if fused is not None:
-            x1, h2, *r2 = fused
-        else:
-            if self._dropping():
-                y_s, b_s = self.drop_path(ops.linear(o_s, sa.proj.weight, sa.proj.bias)), None
-            else:
-                y_s, b_s = ops.linear(o_s, sa.proj.weight), sa.proj.bias
-            x1, h2, *r2 = ops.add_layer_norm(x, y_s, b_s, n2.weight, n2.bias, n2.eps, keep_sum=True, recipe=sel)
-        r2 = r2[0] if r2 else None
-        if self._dropping():
-            return x1, self.drop_path(self.mlp(h2)), None
-        if self.mlp.act_kind is not None:
-            if defer_mlp and ops.RESIDUAL_EPILOGUE and h2.dtype == torch.bfloat16 and x1.dtype == torch.bfloat16:
-                return x1, PendingMlp(h2, self.mlp, r2), self.mlp.fc2.bias      # enqueued by the next consumer (_close_pending)
-            return (x1, ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind, ln=r2),
-                    self.mlp.fc2.bias)
-        return x1, ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight), self.mlp.fc2.bias
+        x1, h2, r2 = triple(ops.linear_add_layer_norm(o_s, sa.proj.weight, sa.proj.bias, x, n2.weight, n2.bias, n2.eps,
+                                                      xtoken=tok_s, recipe=sel))
+        return self._mlp_pending(x1, h2, r2, defer=defer_mlp)
 
     def chain_cls(self, res, pend, pend_bias, frames, n_per_frame, selective=False):
         """The LAST block when only the cls row of its output is read (`norm(x)[:, 0]`, timesformer.py:377): same
@@ -436,75 +373,30 @@ class SpaceTimeBlock(nn.Module):
         -- 2/3 of a block's flops -- run on the B cls rows only. Exact, like
         the caption trim of the text tower: the skipped rows feed nothing (their gradient is exactly zero in the
         reference, too). Returns (x1, y, y_bias) of the cls rows, [B, D] each.
-        selective: reaches _close_pending only (the pending MLP of the block before keeps neither its input nor its hidden
-        activation); this block's own LayerNorm outputs are kept (its MLP runs on B rows)."""
-        n3, n1, n2 = self.norm3, self.norm1, self.norm2
-        if pend is None:
-            x = res
-            h3 = ops.layer_norm(x, n3.weight, n3.bias, n3.eps)
-        else:
-            x, h3 = _close_pending(res, pend, pend_bias, n3, selective=selective)[:2]
-        ta, sa = self.timeattn, self.attn
-        tok_y = None
-        if hasattr(self, 'alpha_timeattn'):
-            o_t = ta.core(h3, 'time', frames, n_per_frame)
-            y_t, b_t = torch.tanh(self.alpha_timeattn).to(o_t.dtype) * ops.linear(o_t, ta.proj.weight, ta.proj.bias), None
-        else:
-            o_t, tok_o = ta.core(h3, 'time', frames, n_per_frame, want_token=True)
-            (y_t, tok_y), b_t = ops.linear_with_token(o_t, ta.proj.weight, tok_o), ta.proj.bias
-        x, h1 = ops.add_layer_norm_pass(x, y_t, b_t, n1.weight, n1.bias, n1.eps, ytoken=tok_y)
-        # space attention, cls query only: k | v of every token (the last two thirds of the qkv Linear), q of the cls rows
-        D = h1.shape[-1]
-        w, bias = sa.qkv.weight, sa.qkv.bias
-        bq, bkv = (None, None) if bias is None else (bias.detach()[:D], bias.detach()[D:])
-        kv = ops.linear(h1, w[D:], bkv)                                          # [B, T, 2D]
-        q = ops.linear(h1[:, 0].contiguous(), w[:D], bq)                         # [B, D]
-        o_cls = ops.cls_attention(q, kv, sa.num_heads, bias=bias)                # [B, D]
-        y_s = ops.linear(o_cls, sa.proj.weight)                                  # [B, D]
+        selective: reaches the close only, stochastic or not (the pending MLP of the block before keeps neither its input
+        nor its hidden activation); this block's own LayerNorm outputs are kept (its MLP runs on B rows)."""
+        x, h1, _ = self._time_half(res, pend, pend_bias, frames, n_per_frame, recipe=bool(selective), sel=False)
+        sa = self.attn
+        y_s = ops.linear(cls_query_attention(h1, sa.qkv.weight, sa.qkv.bias, sa.num_heads), sa.proj.weight)      # [B, D]
+        c_s = c_m = None
         if self._stochastic():
             # the two scaled adds of `chain` on the cls rows: one row per sample
             c_s = self.drop_path.sample_scale(x.shape[0], x.device)
             c_m = self.drop_path.sample_scale(x.shape[0], x.device)
-            x1, h2 = ops.scaled_add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, c_s, 1, n2.weight, n2.bias, n2.eps)
-            return x1, ScaledBranch(self._mlp_branch(h2), c_m), self.mlp.fc2.bias
-        x1, h2 = ops.add_layer_norm(x[:, 0].contiguous(), y_s, sa.proj.bias, n2.weight, n2.bias, n2.eps, keep_sum=True)
-        if self.mlp.act_kind is not None:
-            return (x1, ops.mlp(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.act_kind),
-                    self.mlp.fc2.bias)
-        return x1, ops.linear(self.mlp.hidden(h2), self.mlp.fc2.weight), self.mlp.fc2.bias
+        x1, h2, _ = close(x, y_s if c_s is None else ScaledBranch(y_s, c_s), sa.proj.bias, self.norm2, rows=0)
+        return self._mlp_pending(x1, h2, scale=c_m)
 
     def forward(self, x, einops_from_space, einops_to_space, einops_from_time, einops_to_time,
                 time_n, space_f, use_checkpoint=False):
         """Reference signature (timesformer.py:173-174); materialises the block output."""
         frames, n = int(space_f), int(time_n)
         mode = _video_checkpoint_mode(use_checkpoint)
-        if mode == 'block' and self._stochastic():
-            x1, y, b, c = checkpoint.checkpoint(_chain_flat, self.chain, x, None, None, None, frames, n, use_reentrant=False)
-            y = ScaledBranch(y, c)
-        elif mode == 'block':
-            x1, y, b = checkpoint.checkpoint(self.chain, x, None, None, frames, n, use_reentrant=False)
-        elif mode == 'selective':
-            x1, y, b = self.chain(x, None, None, frames, n, selective=True)
+        if mode == 'block':
+            x1, y, b = checkpointed(self.chain, x, None, None, frames, n)
         else:
-            x1, y, b = self.chain(x, None, None, frames, n)
-        if isinstance(y, ScaledBranch):
-            # the closing add through the scaled kernel; nothing reads its normalised rows here
-            n3 = self.norm3
-            out = ops.scaled_add_layer_norm(x1, y.y, b, y.scale, _rows_per_sample(x1), n3.weight.detach(), n3.bias.detach(),
-                                            n3.eps)[0]
-            return _like_caller(out, x)
-        return _like_caller(x1 + (y if b is None else y + b.to(y.dtype)), x)
-
-
-def _chain_flat(fn, res, pend, pend_b, pend_c, frames, n):
-    """`fn` (SpaceTimeBlock.chain / chain_cls) with a ScaledBranch taken apart into tensors on the way in and out: what
-    torch.utils.checkpoint carries across a block boundary. Returns (res, pend, pend_bias, pend_scale or None)."""
-    if pend_c is not None:
-        pend = ScaledBranch(pend, pend_c)
-    res, pend, pend_b = fn(res, pend, pend_b, frames, n)
-    if isinstance(pend, ScaledBranch):
-        return res, pend.y, pend_b, pend.scale
-    return res, pend, pend_b, None
+            x1, y, b = self.chain(x, None, None, frames, n, selective=mode == 'selective')
+        # (a scaled branch: the closing add through the scaled kernel; nothing reads its normalised rows here)
+        return _like_caller(compose(x1, y, b, norm_for_scaled=self.norm3, bias_first=True), x)
 
 
 class SpaceTimeTransformer(nn.Module):
@@ -617,56 +509,25 @@ class SpaceTimeTransformer(nn.Module):
         res, pend, pend_b = x, None, None
         hook = after_block
         last = len(self.blocks) - 1
-        # with stochastic depth in the tower no MLP waits for the next block: block checkpointing closes every add in the
-        # composed form, and the two modes then run the same kernels (equal to the bit under one seed)
+        # with stochastic depth in the tower no MLP waits for the next block in the plain step: block checkpointing closes
+        # every add in the composed form, and the two modes then run the same kernels (equal to the bit under one seed)
         stochastic = any(blk._stochastic() for blk in self.blocks)
         for i, blk in enumerate(self.blocks):
-            # the last block of a cls-pooled forward only has to produce its cls rows (SpaceTimeBlock.chain_cls)
-            fn = blk.chain_cls if (cls_at_last and i == last and CLS_ONLY_LAST_BLOCK and not blk._dropping()
-                                   and blk.attention_style == 'frozen-in-time') else blk.chain
+            # the last block of a cls-pooled forward only has to produce its cls rows (SpaceTimeBlock.chain_cls); any other
+            # but the last may leave its MLP to the next block's norm3 (ops.RESIDUAL_EPILOGUE: residual add in fc2's
+            # epilogue). 'selective': the plain step's kernels in the plain step's order; what is kept for backward differs
+            cls_only = cls_at_last and i == last and CLS_ONLY_LAST_BLOCK and blk.attention_style == 'frozen-in-time'
+            fn = blk.chain_cls if cls_only else blk.chain
+            how = {} if cls_only else {'defer_mlp': i != last and (mode == 'selective' or not stochastic)}
             if mode == 'block':
-                if isinstance(pend, PendingMlp):
-                    pend = pend.materialize()
-                if isinstance(pend, ScaledBranch) or blk._stochastic():
-                    y, c = (pend.y, pend.scale) if isinstance(pend, ScaledBranch) else (pend, None)
-                    res, pend, pend_b, c = checkpoint.checkpoint(_chain_flat, fn, res, y, pend_b, c, frames, n,
-                                                                 use_reentrant=False)
-                    if c is not None:
-                        pend = ScaledBranch(pend, c)
-                else:
-                    res, pend, pend_b = checkpoint.checkpoint(fn, res, pend, pend_b, frames, n, use_reentrant=False)
-            elif mode == 'selective':
-                # the plain step's kernels in the plain step's order; what is kept for backward differs (SpaceTimeBlock.chain)
-                if fn == blk.chain and i != last:
-                    res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True, selective=True)
-                else:
-                    res, pend, pend_b = fn(res, pend, pend_b, frames, n, selective=True)
-            elif fn == blk.chain and i != last and not stochastic:
-                # the block's MLP may wait for the next block's norm3 (ops.RESIDUAL_EPILOGUE: residual add in fc2's epilogue)
-                res, pend, pend_b = fn(res, pend, pend_b, frames, n, defer_mlp=True)
+                res, pend, pend_b = checkpointed(fn, res, pend, pend_b, frames, n)
             else:
-                res, pend, pend_b = fn(res, pend, pend_b, frames, n)
+                res, pend, pend_b = fn(res, pend, pend_b, frames, n, selective=mode == 'selective', **how)
             if hook is not None and i == hook[0]:
                 hook[1]()
-        nm = self.norm
-        if cls_at_last:
-            # only row 0 of every sample feeds the output: final residual add + LayerNorm on [B, D]
-            r0 = res if res.dim() == 2 else res[:, 0].contiguous()
-            if pend is None:
-                out = ops.layer_norm(r0, nm.weight, nm.bias, nm.eps)
-            elif isinstance(pend, ScaledBranch):
-                p0 = pend.y if pend.y.dim() == 2 else pend.y[:, 0].contiguous()
-                out = ops.scaled_add_layer_norm(r0, p0, pend_b, pend.scale, 1, nm.weight, nm.bias, nm.eps)[1]
-            else:
-                p0 = pend if pend.dim() == 2 else pend[:, 0].contiguous()
-                _, out = ops.add_layer_norm(r0, p0, pend_b, nm.weight, nm.bias, nm.eps, keep_sum=False)
-            return self.pre_logits(out)
-        if pend is None:
-            return ops.layer_norm(res, nm.weight, nm.bias, nm.eps)
-        if isinstance(pend, ScaledBranch):
-            return ops.scaled_add_layer_norm(res, pend.y, pend_b, pend.scale, _rows_per_sample(res), nm.weight, nm.bias,
-                                             nm.eps)[1]
-        return ops.add_layer_norm(res, pend, pend_b, nm.weight, nm.bias, nm.eps, keep_sum=False)[1]
+        # the final residual add + LayerNorm; cls_at_last: only row 0 of every sample feeds the output, [B, D]
+        out = close(res, pend, pend_b, self.norm, keep_sum=False, rows=0 if cls_at_last else None)[1]
+        return self.pre_logits(out) if cls_at_last else out
 
     def forward_features(self, x, use_checkpoint=False, cls_at_last=True):
         """Reference signature: x is [B, F, C, H, W] (timesformer.py:345-382; the narrator's entry with

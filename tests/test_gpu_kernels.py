@@ -596,7 +596,7 @@ def test_block_with_residual_epilogue_equals_the_composed_block():
 
 def test_tower_with_residual_epilogues_equals_the_composed_tower():
     """ops.RESIDUAL_EPILOGUE through a 3-block tower: the space projection's and (deferred to the next block's norm3:
-    timesformer.PendingMlp) the MLP's residual adds ride in GEMM epilogues. Same features and gradients as the composed
+    chain.PendingMlp) the MLP's residual adds ride in GEMM epilogues. Same features and gradients as the composed
     form up to the roundings that moved (the stream is rounded once per add instead of product-then-sum)."""
     import contextlib
     import io
