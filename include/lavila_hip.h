@@ -236,6 +236,9 @@ int lvl_divided_attn_fwd(const void* qkv, void* out, float* lse, float* ws, int 
 int lvl_divided_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
                          void* dqkv, float* ws, int B, int F, int N, int H, int mode, int dtype,
                          void* stream);
+/* Every attention entry point of this header (divided, causal, cls-only, rows / cross, pooler, decode, key-masked) is
+ * pinned by tests/test_gpu_attention_shift.py to finite and accurate results for any finite bf16 or f32 scores -- rows
+ * shifted by up to +-120 over key staircases, lse from below -89 to above +280 -- padded and hidden keys included. */
 
 /* host-side query: 1 if a bf16 call of this shape runs on the MFMA / register-tiled attention kernels (forward and
  * backward), 0 if it falls to the shape-generic kernels (any shape, correct, much slower). mode: LVL_ATTN_SPACE /
