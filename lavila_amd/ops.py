@@ -832,17 +832,57 @@ def linear(x, weight, bias=None, ln=None):
 # --------------------------------------------------------------------------------------------------
 # LayerNorm (optionally fused with residual + bias add)
 # --------------------------------------------------------------------------------------------------
-def layernorm_fwd_raw(x, x2, xbias, gamma, beta, eps, keep_sum):
+def _mixed_dtypes(x, x2, dy=None, dadd=None):
+    # the mixed entry points take no dtype tag: a tensor of another element size would be read past its end
+    for name, t, dt in (('x', x, torch.float32), ('x2', x2, torch.bfloat16), ('dy', dy, torch.bfloat16),
+                        ('dadd', dadd, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise TypeError(f'layernorm (mixed): {name} must be a contiguous {dt} tensor, got {t.dtype}')
+    for name, t in (('x2', x2), ('dy', dy), ('dadd', dadd)):
+        if t is not None and t.numel() != x.numel():
+            raise ValueError(f'layernorm (mixed): {name} has {t.numel()} elements, x has {x.numel()}')
+
+
+def _ln_fwd_launch(mixed, x, x2, xbias, gamma, beta, eps, keep_sum, flags=0):
+    """The one forward launch under layernorm_fwd_raw and layernorm_fwd_mixed_raw (their entry points take the same
+    arguments but the last, the dtype code or, mixed, the flags): checks, y (bf16 if mixed), the sum, the statistics, the call."""
     C.require_device(x, x2, xbias, gamma, beta)
+    if mixed:
+        _mixed_dtypes(x, x2)
+    name = 'lvl_layernorm_fwd_mixed' if mixed else 'lvl_layernorm_fwd'
     rows, cols = _rows_cols(x)
-    y = torch.empty_like(x)
+    y = torch.empty_like(x, dtype=torch.bfloat16 if mixed else x.dtype)
     s = torch.empty_like(x) if keep_sum else None
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    C.check(C.lib().lvl_layernorm_fwd(C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(beta), C.ptr(s),
-                                      C.ptr(y), C.ptr(mean), C.ptr(rstd), rows, cols, float(eps),
-                                      C.dtype_code(x), C.stream_ptr()), 'lvl_layernorm_fwd')
+    C.check(getattr(C.lib(), name)(C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(beta), C.ptr(s), C.ptr(y),
+                                   C.ptr(mean), C.ptr(rstd), rows, cols, float(eps), flags if mixed else C.dtype_code(x),
+                                   C.stream_ptr()), name)
     return y, s, mean, rstd
+
+
+def _ln_bwd_launch(mixed, dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_branch, flags=0):
+    """The one backward launch under layernorm_bwd_raw and layernorm_bwd_mixed_raw, as _ln_fwd_launch: (dx, dgamma, dbeta,
+    dxsum or None, the branch's own gradient -- dx_plain, or bf16 dx2 if mixed -- or None)."""
+    C.require_device(dy, x, x2, xbias, gamma, mean, rstd, dadd)
+    if mixed:
+        _mixed_dtypes(x, x2, dy, dadd)
+    name = 'lvl_layernorm_bwd_mixed' if mixed else 'lvl_layernorm_bwd'
+    rows, cols = _rows_cols(x)
+    dx = torch.empty_like(x)
+    dbranch = torch.empty_like(x, dtype=torch.bfloat16 if mixed else x.dtype) if want_branch else None
+    dgamma = torch.empty(cols, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(cols, dtype=torch.float32, device=x.device)
+    dxsum = torch.empty(cols, dtype=torch.float32, device=x.device) if want_dxsum else None
+    ws = C.workspace('layernorm_bwd', rows, cols, x.device)
+    C.check(getattr(C.lib(), name)(C.ptr(dy), C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(mean), C.ptr(rstd),
+                                   C.ptr(dadd), C.ptr(dx), C.ptr(dbranch), C.ptr(dgamma), C.ptr(dbeta), C.ptr(dxsum),
+                                   C.ptr(ws), rows, cols, flags if mixed else C.dtype_code(x), C.stream_ptr()), name)
+    return dx, dgamma, dbeta, dxsum, dbranch
+
+
+def layernorm_fwd_raw(x, x2, xbias, gamma, beta, eps, keep_sum):
+    return _ln_fwd_launch(False, x, x2, xbias, gamma, beta, eps, keep_sum)
 
 
 def layernorm_apply_raw(x, x2, xbias, gamma, beta, mean, rstd):
@@ -869,50 +909,17 @@ def quickgelu_apply_raw(u):
 
 
 def layernorm_bwd_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_plain=False):
-    """want_plain: also return the normalisation's own input gradient without dadd (dx = dx_plain + dadd)."""
-    C.require_device(dy, x, x2, xbias, gamma, mean, rstd, dadd)
-    rows, cols = _rows_cols(x)
-    dx = torch.empty_like(x)
-    dx_plain = torch.empty_like(x) if want_plain else None
-    dgamma = torch.empty(cols, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(cols, dtype=torch.float32, device=x.device)
-    dxsum = torch.empty(cols, dtype=torch.float32, device=x.device) if want_dxsum else None
-    ws = C.workspace('layernorm_bwd', rows, cols, x.device)
-    C.check(C.lib().lvl_layernorm_bwd(C.ptr(dy), C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(mean),
-                                      C.ptr(rstd), C.ptr(dadd), C.ptr(dx), C.ptr(dx_plain), C.ptr(dgamma),
-                                      C.ptr(dbeta), C.ptr(dxsum), C.ptr(ws), rows, cols, C.dtype_code(x),
-                                      C.stream_ptr()), 'lvl_layernorm_bwd')
-    if want_plain:
-        return dx, dgamma, dbeta, dxsum, dx_plain
-    return dx, dgamma, dbeta, dxsum
-
-
-def _mixed_dtypes(x, x2, dy=None, dadd=None):
-    # the mixed entry points take no dtype tag: a tensor of another element size would be read past its end
-    for name, t, dt in (('x', x, torch.float32), ('x2', x2, torch.bfloat16), ('dy', dy, torch.bfloat16),
-                        ('dadd', dadd, torch.float32)):
-        if t is not None and (t.dtype != dt or not t.is_contiguous()):
-            raise TypeError(f'layernorm (mixed): {name} must be a contiguous {dt} tensor, got {t.dtype}')
-    for name, t in (('x2', x2), ('dy', dy), ('dadd', dadd)):
-        if t is not None and t.numel() != x.numel():
-            raise ValueError(f'layernorm (mixed): {name} has {t.numel()} elements, x has {x.numel()}')
+    """(dx, dgamma, dbeta, dxsum): dx with dadd added, dxsum its column sums (want_dxsum). want_plain: a fifth value, the
+    normalisation's own input gradient without dadd (dx = dx_plain + dadd); dxsum then sums that one."""
+    out = _ln_bwd_launch(False, dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_plain)
+    return out if want_plain else out[:4]
 
 
 def layernorm_fwd_mixed_raw(x, x2, xbias, gamma, beta, eps, keep_sum, general=False):
     """One lvl_layernorm_fwd_mixed call: x float32 (the residual stream), x2 bf16 or None. Returns y in bf16, the sum in
     float32 (keep_sum) and the statistics: layernorm_fwd_raw on x and x2.float() with y rounded once, to the bit.
     general: the general kernel also where there is an exact-width one (they agree to the bit)."""
-    C.require_device(x, x2, xbias, gamma, beta)
-    _mixed_dtypes(x, x2)
-    rows, cols = _rows_cols(x)
-    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-    s = torch.empty_like(x) if keep_sum else None
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    C.check(C.lib().lvl_layernorm_fwd_mixed(C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(beta), C.ptr(s),
-                                            C.ptr(y), C.ptr(mean), C.ptr(rstd), rows, cols, float(eps),
-                                            C.LN_GENERAL if general else 0, C.stream_ptr()), 'lvl_layernorm_fwd_mixed')
-    return y, s, mean, rstd
+    return _ln_fwd_launch(True, x, x2, xbias, gamma, beta, eps, keep_sum, C.LN_GENERAL if general else 0)
 
 
 def layernorm_bwd_mixed_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_dx2=False, plain=False,
@@ -920,21 +927,52 @@ def layernorm_bwd_mixed_raw(dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsu
     """One lvl_layernorm_bwd_mixed call: dy bf16, x float32, x2 bf16 or None, dadd float32 or None. Returns
     (dx, dgamma, dbeta, dxsum, dx2): dx float32 (dadd added); dx2 (want_dx2 or plain) the branch gradient in bf16 -- dx
     rounded once, or with plain the gradient without dadd rounded once (dxsum then sums that one, in float32)."""
-    C.require_device(dy, x, x2, xbias, gamma, mean, rstd, dadd)
-    _mixed_dtypes(x, x2, dy, dadd)
-    rows, cols = _rows_cols(x)
-    dx = torch.empty_like(x)
-    dx2 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if (want_dx2 or plain) else None
-    dgamma = torch.empty(cols, dtype=torch.float32, device=x.device)
-    dbeta = torch.empty(cols, dtype=torch.float32, device=x.device)
-    dxsum = torch.empty(cols, dtype=torch.float32, device=x.device) if want_dxsum else None
-    ws = C.workspace('layernorm_bwd', rows, cols, x.device)
     flags = (C.LN_PLAIN if plain else 0) | (C.LN_GENERAL if general else 0)
-    C.check(C.lib().lvl_layernorm_bwd_mixed(C.ptr(dy), C.ptr(x), C.ptr(x2), C.ptr(xbias), C.ptr(gamma), C.ptr(mean),
-                                            C.ptr(rstd), C.ptr(dadd), C.ptr(dx), C.ptr(dx2), C.ptr(dgamma),
-                                            C.ptr(dbeta), C.ptr(dxsum), C.ptr(ws), rows, cols, flags,
-                                            C.stream_ptr()), 'lvl_layernorm_bwd_mixed')
-    return dx, dgamma, dbeta, dxsum, dx2
+    return _ln_bwd_launch(True, dy, x, x2, xbias, gamma, mean, rstd, dadd, want_dxsum, want_dx2 or plain, flags)
+
+
+# The forward and the backward of every LayerNorm Function below (DESIGN.md section 4, "The LayerNorm host layer"). Both reach
+# the kernels through the four launchers above by their module-level names, looked up at each call.
+def _ln_forward(x, x2, xbias, gamma, beta, eps, keep_sum, mixed=False, rec=None):
+    """h = LayerNorm(x + x2 + xbias) on the plain kernels or, mixed, on the lvl_layernorm_*_mixed pair (float32 x, bf16 x2 and
+    h). Returns (h, s, kept): s the sum (keep_sum, else None) and kept = (x, x2, xbias, gamma, mean, rstd), the tensors
+    _ln_backward runs on -- the kept sum as x with x2 = xbias = None if there is one, else the operands in the forward's
+    order. The recipe `rec` (an LnRecipe or None) is filled with those same operands: one rule for what rebuilds h and for
+    what its backward reads."""
+    x, x2 = x.contiguous(), (None if x2 is None else x2.contiguous())
+    xb, g, b = _f32(xbias), _f32(gamma), _f32(beta)
+    h, s, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(x, x2, xb, g, b, eps, keep_sum)
+    operands = (s, None, None) if keep_sum else (x, x2, xb)
+    if rec is not None:
+        rec.fill(*operands, g, b, mean, rstd)
+    return h, s, (*operands, g, mean, rstd)
+
+
+def _ln_backward(dh, kept, dadd, want_colsum, mixed=False, split=False, branch=True):
+    """(dx, dbranch, dgamma, dbeta, colsum) of _ln_forward from its `kept` tensors for the gradient dh of h. dadd: the
+    gradient that reaches the stream on another path (of the kept sum, or of the stream handed through), added to dx inside
+    the kernel. dbranch is the gradient of the branch x2 (+ xbias) and colsum (want_colsum) its column sums in float32:
+    without split dbranch is dx -- the same tensor on the plain kernels, dx rounded once to bf16 on the mixed ones; with split
+    it excludes dadd (the pass form when the stream's own gradient arrived). branch=False: there is no branch, dbranch is
+    not written. dgamma and dbeta are float32."""
+    x, x2, xbias, g, mean, rstd = kept
+    dh = dh.reshape(x.shape).contiguous()
+    dadd = None if dadd is None else dadd.reshape(x.shape).contiguous()
+    operands = (dh, x, x2, xbias, g, mean, rstd, dadd, want_colsum)
+    if mixed:
+        dx, dgamma, dbeta, colsum, dbranch = layernorm_bwd_mixed_raw(*operands, want_dx2=branch, plain=split)
+    elif split:
+        dx, dgamma, dbeta, colsum, dbranch = layernorm_bwd_raw(*operands, want_plain=True)
+    else:
+        dx, dgamma, dbeta, colsum = layernorm_bwd_raw(*operands)
+        dbranch = dx
+    return dx, dbranch, dgamma, dbeta, colsum
+
+
+def _param_grads(pdt, *grads):
+    """The float32 gradients the row kernels leave for parameters (dgamma, dbeta, a bias gradient that is a column sum) in
+    those parameters' dtypes pdt; None where there is no such parameter (its dtype is None) or no gradient."""
+    return tuple(None if (g is None or dt is None) else g.to(dt) for g, dt in zip(grads, pdt))
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -943,22 +981,15 @@ class _LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps, rec=None, mixed=False):
-        x = x.contiguous()
-        g, b = _f32(weight), _f32(bias)
-        y, _, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(x, None, None, g, b, eps, False)
-        ctx.save_for_backward(x, g, mean, rstd)
-        ctx.pdt = (weight.dtype, bias.dtype)
-        ctx.mixed = mixed
-        if rec is not None:
-            rec.fill(x, None, None, g, b, mean, rstd)
+        y, _, kept = _ln_forward(x, None, None, weight, bias, eps, False, mixed, rec)
+        ctx.save_for_backward(*kept)
+        ctx.pdt, ctx.mixed = (weight.dtype, bias.dtype), mixed
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, g, mean, rstd = ctx.saved_tensors
-        bwd = layernorm_bwd_mixed_raw if ctx.mixed else layernorm_bwd_raw
-        dx, dg, db = bwd(dy.contiguous(), x, None, None, g, mean, rstd, None, False)[:3]
-        return dx, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None
+        dx, _, dg, db, _ = _ln_backward(dy, ctx.saved_tensors, None, False, ctx.mixed, branch=False)
+        return (dx, *_param_grads(ctx.pdt, dg, db), None, None, None)
 
 
 # Residual stream dtype under autocast. Default: the autocast dtype (bf16) from the patch embedding to the final norm
@@ -1000,18 +1031,9 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, res, y, ybias, weight, bias, eps, keep_sum, rec=None, mixed=False):
-        res, y = res.contiguous(), y.contiguous()
-        yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
-        h, s, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(res, y, yb, g, b, eps, keep_sum)
-        if rec is not None:
-            rec.fill(*((s, None, None) if keep_sum else (res, y, yb)), g, b, mean, rstd)
-        if keep_sum:
-            ctx.save_for_backward(s, g, mean, rstd)
-        else:
-            ctx.save_for_backward(res, y, yb, g, mean, rstd)
-        ctx.keep_sum = keep_sum
-        ctx.mixed = mixed
-        ctx.has_ybias = ybias is not None
+        h, s, kept = _ln_forward(res, y, ybias, weight, bias, eps, keep_sum, mixed, rec)
+        ctx.save_for_backward(*kept)
+        ctx.keep_sum, ctx.mixed = keep_sum, mixed
         ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
         if keep_sum:
             return s, h
@@ -1021,19 +1043,11 @@ class _AddLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ds, dh):
-        if ctx.keep_sum:
-            s, g, mean, rstd = ctx.saved_tensors
-            operands = (s, None, None, g, mean, rstd, ds.contiguous() if ds is not None else None)
-        else:
-            res, y, yb, g, mean, rstd = ctx.saved_tensors
-            operands = (res, y, yb, g, mean, rstd, None)
-        if ctx.mixed:      # the branch's gradient is the stream's, rounded once by the kernel
-            dx, dg, db, dsum, dy = layernorm_bwd_mixed_raw(dh.contiguous(), *operands, ctx.has_ybias, want_dx2=True)
-        else:
-            dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), *operands, ctx.has_ybias)
-            dy = dx
-        dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
-        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, None, None, None
+        # ds: the gradient of the kept sum (the dummy has none); the branch's gradient is the stream's
+        dx, dy, dg, db, colsum = _ln_backward(dh, ctx.saved_tensors, ds if ctx.keep_sum else None, ctx.pdt[2] is not None,
+                                              ctx.mixed)
+        dg, db, dyb = _param_grads(ctx.pdt, dg, db, colsum)
+        return dx, dy, dyb, dg, db, None, None, None, None
 
 
 # Residual adds in GEMM epilogues (LVL_EPI_BIAS_RESIDUAL; LAVILA_RESIDUAL_EPILOGUE=0 restores the composed form): the space
@@ -1046,9 +1060,9 @@ RESIDUAL_EPILOGUE = os.environ.get('LAVILA_RESIDUAL_EPILOGUE', '1') != '0'
 class _LinearResidualLayerNormFn(torch.autograd.Function):
     """(s, h) = (res + x W^T + b, LayerNorm(s)): `x1 = x + attn(norm1(t)); h2 = norm2(x1)` of SpaceTimeBlock
     (timesformer.py:192-196) as one GEMM with the residual epilogue + one plain LayerNorm pass. Backward: the LayerNorm
-    backward kernel adds the stream's own gradient (dadd) and leaves ds, whose column sums are the bias gradient; ds is
-    the residual's gradient AND the GEMM's output gradient (input gradient: lvl_linear_tn on the transposed weight copy,
-    weight gradient: lvl_linear_wgrad)."""
+    backward kernel adds the stream's own gradient ds (the core's dadd) and leaves dsum, the gradient of the sum, whose
+    column sums (colsum) are the bias gradient; dsum is the residual's gradient AND the GEMM's output gradient (input
+    gradient: lvl_linear_tn on the transposed weight copy, weight gradient: lvl_linear_wgrad)."""
 
     @staticmethod
     def forward(ctx, x, weight, lbias, res, gamma, beta, eps, xtoken=None, rec=None):
@@ -1058,33 +1072,26 @@ class _LinearResidualLayerNormFn(torch.autograd.Function):
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
         w, wt = weight_copies(weight)
         s = linear_tn_raw(x2, w, _f32(lbias), C.EPI_BIAS_RESIDUAL, aux_in=res2)
-        g, b = _f32(gamma), _f32(beta)
-        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
-        if rec is not None:
-            rec.fill(s, None, None, g, b, mean, rstd)
+        h, _, kept = _ln_forward(s, None, None, gamma, beta, eps, False, rec=rec)
         ctx.has_token = xtoken is not None
-        ctx.save_for_backward(x2, wt, s, g, mean, rstd, *((weight,) if ctx.has_token else ()))
-        ctx.meta = (weight.dtype, None if lbias is None else lbias.dtype, gamma.dtype, beta.dtype, x.shape)
+        ctx.save_for_backward(x2, wt, *kept, *((weight,) if ctx.has_token else ()))
+        ctx.meta = (weight.dtype, (gamma.dtype, beta.dtype, None if lbias is None else lbias.dtype), x.shape)
         return s.reshape(res.shape), h.reshape(res.shape)
 
     @staticmethod
     def backward(ctx, ds, dh):
         saved = ctx.saved_tensors             # ONE access: torch.utils.checkpoint's unpack hook refuses a second one
-        x2, wt, s, g, mean, rstd = saved[:6]
-        wdt, bdt, gdt, betadt, xshape = ctx.meta
-        dh2 = dh.reshape(s.shape)
-        dadd = None if ds is None else ds.reshape(s.shape).contiguous()
+        x2, wt = saved[:2]
+        wdt, pdt, xshape = ctx.meta
         want_tok = ctx.has_token and ctx.needs_input_grad[7]
-        dsum, dg, dbeta, dcol = layernorm_bwd_raw(dh2.contiguous(), s, None, None, g, mean, rstd, dadd,
-                                                  bdt is not None or want_tok)
+        dsum, _, dg, dbeta, colsum = _ln_backward(dh, saved[2:8], ds, pdt[2] is not None or want_tok)
         with torch.autocast('cuda', enabled=False):
             dx = linear_tn_raw(dsum, wt, None, C.EPI_BIAS).reshape(xshape) if ctx.needs_input_grad[0] else None
             dw = _wgrad(dsum, x2, wdt) if ctx.needs_input_grad[1] else None
             # token rule: column sums of dx = (column sums of dsum) . W  (dx = dsum W)
-            dtok = vec_mat(dcol, saved[6]) if want_tok else None
-        db = dcol.to(bdt) if (bdt is not None and ctx.needs_input_grad[2]) else None
-        return (dx, dw, db, dsum.reshape(ds.shape if ds is not None else dh.shape), dg.to(gdt), dbeta.to(betadt), None,
-                dtok, None)
+            dtok = vec_mat(colsum, saved[8]) if want_tok else None
+        dg, dbeta, db = _param_grads(pdt, dg, dbeta, colsum if ctx.needs_input_grad[2] else None)
+        return dx, dw, db, dsum.reshape(ds.shape if ds is not None else dh.shape), dg, dbeta, None, dtok, None
 
 
 def linear_residual_layer_norm(x, weight, lbias, res, gamma, beta, eps, xtoken=None, recipe=False):
@@ -1116,38 +1123,34 @@ class _MlpResidualLayerNormFn(torch.autograd.Function):
     """(s, h) = (res + fc2(act(fc1(x) + b1)) + b2, LayerNorm(s)): `x = x + mlp(norm2(x))` of one block and the first
     LayerNorm of the NEXT consumer (timesformer.py:196 / 183; openai_model.py:200 / 199) -- _MlpFn with the residual
     epilogue on its second GEMM, then one plain LayerNorm pass. Backward = LayerNorm backward (adds the stream's own
-    gradient, leaves ds and its column sums = d b2), then _MlpFn's backward on ds."""
+    gradient ds, leaves dsum and its column sums = d b2), then _MlpFn's backward on dsum."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, rec=None, act=ACT_QUICKGELU):
         res2 = res.reshape(-1, res.shape[-1])
         res2 = res2 if res2.is_contiguous() else res2.contiguous()
         s, saved = _mlp_forward(ctx, x, w1, b1, w2, ln, act, b2, res2)      # bf16 (the caller's condition)
-        g, b = _f32(gamma), _f32(beta)
-        h, _, mean, rstd = layernorm_fwd_raw(s, None, None, g, b, eps, False)
-        if rec is not None:
-            rec.fill(s, None, None, g, b, mean, rstd)
-        ctx.save_for_backward(*saved, s, g, mean, rstd)
-        ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype, gamma.dtype,
-                    beta.dtype, x.shape)
+        h, _, kept = _ln_forward(s, None, None, gamma, beta, eps, False, rec=rec)
+        ctx.save_for_backward(*saved, *kept)
+        ctx.meta = (w1.dtype, None if b1 is None else b1.dtype, w2.dtype,
+                    (gamma.dtype, beta.dtype, None if b2 is None else b2.dtype), x.shape)
         return s.reshape(res.shape), h.reshape(res.shape)
 
     @staticmethod
     def backward(ctx, ds, dh):
-        kept = x2 = a = None
+        *mlp_kept, s, _, _, g, mean, rstd = ctx.saved_tensors
+        pdt = ctx.meta[3]
+        dsum, _, dg, dbeta, colsum = _ln_backward(dh, (s, None, None, g, mean, rstd), ds, pdt[2] is not None)
+        del ds, s             # the sum and the stream's own gradient are done with: released before the MLP's GEMMs
+        recipe = x2 = a = None
         if ctx.sel:
-            *kept, u, w1t, w2t, s, g, mean, rstd = ctx.saved_tensors
+            *recipe, u, w1t, w2t = mlp_kept
         else:
-            x2, u, a, w1t, w2t, s, g, mean, rstd = ctx.saved_tensors
-        w1dt, b1dt, w2dt, b2dt, gdt, betadt, xshape = ctx.meta
-        dadd = None if ds is None else ds.reshape(s.shape).contiguous()
-        dsum, dg, dbeta, dcol = layernorm_bwd_raw(dh.reshape(s.shape).contiguous(), s, None, None, g, mean, rstd, dadd,
-                                                  b2dt is not None)
-        del dadd, s
+            x2, u, a, w1t, w2t = mlp_kept
         with torch.autocast('cuda', enabled=False):
-            dx, dw1, db1, dw2 = _mlp_backward(ctx, dsum, x2, u, a, w1t, w2t, kept)
-        return (dx, dw1, db1, dw2, dcol.to(b2dt) if (b2dt is not None and ctx.needs_input_grad[4]) else None,
-                dsum.reshape(dh.shape), dg.to(gdt), dbeta.to(betadt), None, None, None, None)
+            dx, dw1, db1, dw2 = _mlp_backward(ctx, dsum, x2, u, a, w1t, w2t, recipe)
+        dg, dbeta, db2 = _param_grads(pdt, dg, dbeta, colsum if ctx.needs_input_grad[4] else None)
+        return dx, dw1, db1, dw2, db2, dsum.reshape(dh.shape), dg, dbeta, None, None, None, None
 
 
 def mlp_residual_layer_norm(x, w1, b1, w2, b2, res, gamma, beta, eps, ln=None, recipe=False, act=ACT_QUICKGELU):
@@ -1171,35 +1174,20 @@ class _AddLayerNormPassFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, res, y, ybias, weight, bias, eps, ytoken=None, rec=None, mixed=False):
-        res, y = res.contiguous(), y.contiguous()
-        yb, g, b = _f32(ybias), _f32(weight), _f32(bias)
-        h, _, mean, rstd = (layernorm_fwd_mixed_raw if mixed else layernorm_fwd_raw)(res, y, yb, g, b, eps, False)
-        if rec is not None:
-            rec.fill(res, y, yb, g, b, mean, rstd)
-        ctx.save_for_backward(res, y, yb, g, mean, rstd)
-        ctx.mixed = mixed
-        ctx.has_ybias = ybias is not None
-        ctx.has_token = ytoken is not None
+        h, _, kept = _ln_forward(res, y, ybias, weight, bias, eps, False, mixed, rec)
+        ctx.save_for_backward(*kept)
+        ctx.mixed, ctx.has_token = mixed, ytoken is not None
         ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
-        return res.view_as(res), h
+        return kept[0].view_as(kept[0]), h
 
     @staticmethod
     def backward(ctx, dres, dh):
-        res, y, yb, g, mean, rstd = ctx.saved_tensors
-        want_sum = ctx.has_ybias or (ctx.has_token and ctx.needs_input_grad[6])     # column sums of dy
-        if ctx.mixed:
-            dadd = None if dres is None else dres.contiguous()
-            dx, dg, db, dsum, dy = layernorm_bwd_mixed_raw(dh.contiguous(), res, y, yb, g, mean, rstd, dadd, want_sum,
-                                                           want_dx2=True, plain=dadd is not None)
-        elif dres is None:
-            dx, dg, db, dsum = layernorm_bwd_raw(dh.contiguous(), res, y, yb, g, mean, rstd, None, want_sum)
-            dy = dx
-        else:
-            dx, dg, db, dsum, dy = layernorm_bwd_raw(dh.contiguous(), res, y, yb, g, mean, rstd, dres.contiguous(),
-                                                     want_sum, want_plain=True)
-        dyb = dsum.to(ctx.pdt[2]) if ctx.has_ybias else None
-        dtok = dsum if (ctx.has_token and ctx.needs_input_grad[6]) else None      # token rule: sum_rows(dy) itself
-        return dx, dy, dyb, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, dtok, None, None
+        want_tok = ctx.has_token and ctx.needs_input_grad[6]
+        # dres: the gradient of the stream handed through; the branch's own gradient (and its column sums) leaves it out
+        dx, dy, dg, db, colsum = _ln_backward(dh, ctx.saved_tensors, dres, ctx.pdt[2] is not None or want_tok, ctx.mixed,
+                                              split=dres is not None)
+        dg, db, dyb = _param_grads(ctx.pdt, dg, db, colsum)
+        return dx, dy, dyb, dg, db, None, (colsum if want_tok else None), None, None      # token rule: sum_rows(dy) itself
 
 
 def add_layer_norm_pass(res, y, ybias, weight, bias, eps, ytoken=None, recipe=False):
@@ -1270,7 +1258,6 @@ class _ScaledAddLayerNormFn(torch.autograd.Function):
         h, s, mean, rstd = droppath_add_layernorm_fwd_raw(res, y, yb, c, rows_per_sample, g, b, eps)
         ctx.save_for_backward(s, g, mean, rstd, c)
         ctx.rps = int(rows_per_sample)
-        ctx.has_ybias = ybias is not None
         ctx.has_token = ytoken is not None
         ctx.pdt = (weight.dtype, bias.dtype, ybias.dtype if ybias is not None else None)
         ctx.set_materialize_grads(False)        # an unused s (the final norm) or h (a closing add) arrives as None
@@ -1285,9 +1272,9 @@ class _ScaledAddLayerNormFn(torch.autograd.Function):
         dh = torch.zeros_like(s) if dh is None else dh.contiguous()
         dres, dy, dg, db, dysum = droppath_add_layernorm_bwd_raw(dh, s, g, mean, rstd, c,
                                                                  None if ds is None else ds.contiguous(),
-                                                                 ctx.rps, ctx.has_ybias or want_tok)
-        dyb = dysum.to(ctx.pdt[2]) if ctx.has_ybias else None
-        return dres, dy, dyb, None, None, dg.to(ctx.pdt[0]), db.to(ctx.pdt[1]), None, (dysum if want_tok else None)
+                                                                 ctx.rps, ctx.pdt[2] is not None or want_tok)
+        dg, db, dyb = _param_grads(ctx.pdt, dg, db, dysum)
+        return dres, dy, dyb, None, None, dg, db, None, (dysum if want_tok else None)
 
 
 def scaled_add_layer_norm(res, y, ybias, scale, rows_per_sample, weight, bias, eps, ytoken=None):
@@ -1849,7 +1836,7 @@ class _DropoutAddLnFn(torch.autograd.Function):
     def backward(ctx, dh):
         s, g, mean, rstd = ctx.saved_tensors
         ds, dy, dgamma, dbeta, _ = add_ln_bwd_raw(dh.contiguous(), s, None, None, g, mean, rstd, None, ctx.drop[1:], ctx.drop[0])
-        return ds, dy, dgamma.to(ctx.pdt[0]), dbeta.to(ctx.pdt[1]), None, None, None, None, None
+        return (ds, dy, *_param_grads(ctx.pdt, dgamma, dbeta), None, None, None, None, None)
 
 
 def dropout_add_layer_norm(res, y, weight, bias, eps, row_index_stride, seed, site, p):
