@@ -7,9 +7,27 @@
 // output aside); the row statistics (log-sum-exp, diagonal, expectation, argmax) come out of one
 // streaming pass, and backward recomputes the logits from the gathered embeddings + gathered LSEs,
 // so no gradient collective is needed.
+#include "clip_row_state.h"
 #include "internal.h"
 
 namespace {
+
+// a_s[e] = k * A[gi][e]: the workgroup's own row, staged in LDS for the column sweep (visible after the barrier)
+template <typename T>
+__device__ __forceinline__ void stage_row(float* a_s, const T* A, int gi, int E, float k) {
+  for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = k * Elem<T>::load(A + (int64_t)gi * E + e);
+  __syncthreads();
+}
+
+// second half of both backwards: dst[e] = k * sum_j c[j] * Bm[j][e], the coefficient row c[G] resident in LDS
+template <typename T>
+__device__ __forceinline__ void contract_rows(float* dst, const float* c, const T* Bm, int G, int E, float k) {
+  for (int e = threadIdx.x; e < E; e += blockDim.x) {
+    float acc = 0.f;
+    for (int j = 0; j < G; ++j) acc = fmaf(c[j], Elem<T>::load(Bm + (int64_t)j * E + e), acc);
+    dst[e] = k * acc;
+  }
+}
 
 template <typename T>
 __device__ __forceinline__ float dot_row(const T* __restrict__ b, const float* __restrict__ a_s, int E) {
@@ -28,64 +46,28 @@ __global__ __launch_bounds__(256) void clip_fwd_kernel(const T* __restrict__ img
                                                        const float* __restrict__ scale_p, int B, int G, int E, int row0,
                                                        float* __restrict__ stats, int32_t* __restrict__ argmax,
                                                        float* __restrict__ logits) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // a_s[E] then reduction scratch [4*5]
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // a_s[E] then the 4 wave records
+  using State = RowState<1, 1>;
   float* a_s = smem;
   float* red = smem + E;
   const int i = blockIdx.x, dir = blockIdx.y, gi = row0 + i;
   const T* A = dir == 0 ? img_all : txt_all;
   const T* Bm = dir == 0 ? txt_all : img_all;
-  const float scale = *scale_p;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = scale * Elem<T>::load(A + (int64_t)gi * E + e);
-  __syncthreads();
+  stage_row(a_s, A, gi, E, *scale_p);
 
-  float m = -INFINITY, l = 0.f, ex = 0.f, best = -INFINITY, diag = 0.f;
-  int bi = 0x7fffffff;
+  State s;
   for (int j = threadIdx.x; j < G; j += blockDim.x) {
     const float z = dot_row(Bm + (int64_t)j * E, a_s, E);
     if (logits) logits[((int64_t)dir * B + i) * G + j] = z;
-    if (j == gi) diag = z;
-    if (z > best) { best = z; bi = j; }
-    const float mn = fmaxf(m, z);
-    const float al = __expf(m - mn), p = __expf(z - mn);
-    l = l * al + p;
-    ex = ex * al + p * z;
-    m = mn;
+    if (j == gi) s.dg[0] = z;
+    s.update(j, z, z, 0);
   }
-  // wave combine
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float M = wave_max(m);
-  const float sc = (m == -INFINITY) ? 0.f : __expf(m - M);
-  l = wave_sum(l * sc);
-  ex = wave_sum(ex * sc);
-  diag = wave_sum(diag);
-  const float wbest = wave_max(best);
-  int cand = (best == wbest) ? bi : 0x7fffffff;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-  if (lane == 0) {
-    red[wave * 5 + 0] = M; red[wave * 5 + 1] = l; red[wave * 5 + 2] = ex; red[wave * 5 + 3] = wbest;
-    red[wave * 5 + 4] = __int_as_float(cand);
-    red[20 + wave] = diag;
-  }
+  s.wave_reduce();
+  if ((threadIdx.x & 63) == 0) s.store(red + (threadIdx.x >> 6) * State::REC);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float MM = -INFINITY, bb = -INFINITY, dd = 0.f;
-    for (int w = 0; w < 4; ++w) { MM = fmaxf(MM, red[w * 5]); bb = fmaxf(bb, red[w * 5 + 3]); dd += red[20 + w]; }
-    float ll = 0.f, ee = 0.f;
-    int idx = 0x7fffffff;
-    for (int w = 0; w < 4; ++w) {
-      const float s2 = (red[w * 5] == -INFINITY) ? 0.f : __expf(red[w * 5] - MM);
-      ll += red[w * 5 + 1] * s2;
-      ee += red[w * 5 + 2] * s2;
-      if (red[w * 5 + 3] == bb) idx = min(idx, __float_as_int(red[w * 5 + 4]));
-    }
-    float* st = stats + ((int64_t)dir * B + i) * 4;
-    st[0] = MM + __logf(ll);     // log-sum-exp of the row
-    st[1] = dd;                   // diagonal (target) logit
-    st[2] = ee / ll;              // sum_j softmax_j * logit_j
-    st[3] = bb;                   // max logit
-    argmax[dir * B + i] = idx;
-  }
+  // stats row: {log-sum-exp, diagonal (target) logit, sum_j softmax_j * logit_j, max logit}
+  if (threadIdx.x == 0)
+    State::finish(red, State::REC, stats + ((int64_t)dir * B + i) * State::STATS, argmax + dir * B + i);
 }
 
 template <typename T>
@@ -102,8 +84,7 @@ __global__ __launch_bounds__(256) void clip_bwd_kernel(const T* __restrict__ img
   const T* A = dir == 0 ? img_all : txt_all;
   const T* Bm = dir == 0 ? txt_all : img_all;
   const float scale = *scale_p;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = scale * Elem<T>::load(A + (int64_t)gi * E + e);
-  __syncthreads();
+  stage_row(a_s, A, gi, E, scale);
   const float L_own = lse_all[(int64_t)dir * G + gi];
   const float* L_other = lse_all + (int64_t)(1 - dir) * G;
   for (int j = threadIdx.x; j < G; j += blockDim.x) {
@@ -116,11 +97,7 @@ __global__ __launch_bounds__(256) void clip_bwd_kernel(const T* __restrict__ img
   __syncthreads();
   float* dst = (dir == 0 ? dimg : dtxt) + (int64_t)i * E;
   const float k = coef * scale * (upstream_p ? *upstream_p : 1.0f);
-  for (int e = threadIdx.x; e < E; e += blockDim.x) {
-    float acc = 0.f;
-    for (int j = 0; j < G; ++j) acc = fmaf(c[j], Elem<T>::load(Bm + (int64_t)j * E + e), acc);
-    dst[e] = k * acc;
-  }
+  contract_rows(dst, c, Bm, G, E, k);
 }
 
 }  // namespace
@@ -176,17 +153,18 @@ __global__ __launch_bounds__(256) void ssl_fwd_kernel(const T* __restrict__ img_
                                                       const float* __restrict__ scales, int B, int G, int E, int row0,
                                                       float* __restrict__ stats, int32_t* __restrict__ argmax,
                                                       float* __restrict__ logits) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];   // a_s[E], red[4][8]
+  extern __shared__ __attribute__((aligned(16))) float smem[];   // a_s[E] then the 4 wave records
+  using State = RowState<3, 2>;
   float* a_s = smem;
   float* red = smem + E;
   const int i = blockIdx.x, dir = blockIdx.y, gi = row0 + i;
   const T* A = dir == 0 ? img_all : txt_all;
   const T* Bm = dir == 0 ? txt_all : img_all;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = Elem<T>::load(A + (int64_t)gi * E + e);
-  __syncthreads();
+  stage_row(a_s, A, gi, E, 1.f);
   const int ind_i = ind[gi] != 0;                                   // any non-zero indicator counts as 1
   const float sc0 = scales[ind_i], sc1 = scales[ind_i + 1];          // partner indicator 0 / 1
 
+  // State::update spelled out on plain locals: through the struct or any call this loop allocates 3-4 fewer SGPRs
   float m = -INFINITY, l = 0.f, ex[3] = {0.f, 0.f, 0.f}, best = -INFINITY, diag_z = 0.f, diag_l = 0.f;
   int bi = 0x7fffffff;
   for (int j = threadIdx.x; j < G; j += blockDim.x) {
@@ -204,44 +182,14 @@ __global__ __launch_bounds__(256) void ssl_fwd_kernel(const T* __restrict__ img_
     for (int k = 0; k < 3; ++k) ex[k] = ex[k] * al + (bucket == k ? p * zr : 0.f);
     m = mn;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float M = wave_max(m);
-  const float sc = (m == -INFINITY) ? 0.f : __expf(m - M);
-  l = wave_sum(l * sc);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) ex[k] = wave_sum(ex[k] * sc);
-  diag_z = wave_sum(diag_z);
-  diag_l = wave_sum(diag_l);
-  const float wbest = wave_max(best);
-  int cand = (best == wbest) ? bi : 0x7fffffff;
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-  if (lane == 0) {
-    float* r = red + wave * 9;
-    r[0] = M; r[1] = l; r[2] = ex[0]; r[3] = ex[1]; r[4] = ex[2]; r[5] = wbest; r[6] = __int_as_float(cand);
-    r[7] = diag_z; r[8] = diag_l;
-  }
+  State s{m, l, {ex[0], ex[1], ex[2]}, best, {diag_z, diag_l}, bi};
+  s.wave_reduce();
+  if ((threadIdx.x & 63) == 0) s.store(red + (threadIdx.x >> 6) * State::REC);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float MM = -INFINITY, bb = -INFINITY, dz = 0.f, dl = 0.f;
-    for (int w = 0; w < 4; ++w) { MM = fmaxf(MM, red[w * 9]); bb = fmaxf(bb, red[w * 9 + 5]); dz += red[w * 9 + 7]; dl += red[w * 9 + 8]; }
-    float ll = 0.f, ee[3] = {0.f, 0.f, 0.f};
-    int idx = 0x7fffffff;
-    for (int w = 0; w < 4; ++w) {
-      const float s2 = (red[w * 9] == -INFINITY) ? 0.f : __expf(red[w * 9] - MM);
-      ll += red[w * 9 + 1] * s2;
-      for (int k = 0; k < 3; ++k) ee[k] += red[w * 9 + 2 + k] * s2;
-      if (red[w * 9 + 5] == bb) idx = min(idx, __float_as_int(red[w * 9 + 6]));
-    }
-    float* st = stats + ((int64_t)dir * B + i) * 8;
-    st[0] = MM + __logf(ll);           // log-sum-exp of the row
-    st[1] = dl;                         // diagonal (target) logit
-    st[2] = ee[0] / ll; st[3] = ee[1] / ll; st[4] = ee[2] / ll;     // bucket expectations of the unscaled dot
-    st[5] = dz;                         // diagonal unscaled dot
-    st[6] = bb;                         // max logit
-    st[7] = 0.f;
-    argmax[dir * B + i] = idx;
-  }
+  // stats row: {log-sum-exp, diagonal (target) logit, the three bucket expectations of the unscaled dot, diagonal
+  // unscaled dot, max logit, 0}
+  if (threadIdx.x == 0)
+    State::finish(red, State::REC, stats + ((int64_t)dir * B + i) * State::STATS, argmax + dir * B + i);
 }
 
 template <typename T>
@@ -258,8 +206,7 @@ __global__ __launch_bounds__(256) void ssl_bwd_kernel(const T* __restrict__ img_
   const int i = blockIdx.x, dir = blockIdx.y, gi = row0 + i;
   const T* A = dir == 0 ? img_all : txt_all;
   const T* Bm = dir == 0 ? txt_all : img_all;
-  for (int e = threadIdx.x; e < E; e += blockDim.x) a_s[e] = Elem<T>::load(A + (int64_t)gi * E + e);
-  __syncthreads();
+  stage_row(a_s, A, gi, E, 1.f);
   const int ind_i = ind[gi] != 0;                                   // any non-zero indicator counts as 1
   const float sc0 = scales[ind_i], sc1 = scales[ind_i + 1];
   const float L_own = lse_all[(int64_t)dir * G + gi];
@@ -272,11 +219,7 @@ __global__ __launch_bounds__(256) void ssl_bwd_kernel(const T* __restrict__ img_
   __syncthreads();
   float* dst = (dir == 0 ? dimg : dtxt) + (int64_t)i * E;
   const float k = coef * (upstream_p ? *upstream_p : 1.0f);
-  for (int e = threadIdx.x; e < E; e += blockDim.x) {
-    float acc = 0.f;
-    for (int j = 0; j < G; ++j) acc = fmaf(c[j], Elem<T>::load(Bm + (int64_t)j * E + e), acc);
-    dst[e] = k * acc;
-  }
+  contract_rows(dst, c, Bm, G, E, k);
 }
 
 }  // namespace

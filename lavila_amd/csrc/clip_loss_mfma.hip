@@ -9,6 +9,7 @@
 // (the 1e-3 parity bar holds with two orders of margin) at bf16 matrix-core speed. The contraction is tiny
 // (2*B*G*E flop per direction); what matters is that no pass over a [B, G] tensor is ever made.
 #include "attn_mfma_common.h"
+#include "clip_row_state.h"
 #include "internal.h"
 
 namespace {
@@ -34,7 +35,8 @@ __global__ __launch_bounds__(256) void clip_fwd_mfma_kernel(const T* __restrict_
                                                             int row0, float* __restrict__ stats,
                                                             int32_t* __restrict__ argmax, float* __restrict__ logits) {
   constexpr int E = EK * 32;
-  __shared__ float red[4][16][6];
+  using State = RowState<1, 1>;
+  __shared__ float red[4][16][State::REC];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int i0 = blockIdx.x * 16, dir = blockIdx.y;
@@ -84,6 +86,7 @@ __global__ __launch_bounds__(256) void clip_fwd_mfma_kernel(const T* __restrict_
         const float z = acc[r];
         if (logits) logits[((size_t)dir * B + i) * G + j] = z;
         if (j == row0 + i) dg[r] = z;
+        // State::update spelled out, own HiLo: the struct here, or attn_mfma's Op2 / split8, changes VGPRs and waves / SIMD
         if (z > best[r]) { best[r] = z; bi[r] = j; }          // columns ascend per lane: first maximum kept
         const float mn = fmaxf(m[r], z);
         const float al = __expf(m[r] - mn), p = __expf(z - mn);
@@ -96,45 +99,16 @@ __global__ __launch_bounds__(256) void clip_fwd_mfma_kernel(const T* __restrict_
   // merge the 16 column lanes of each row, then the 4 waves
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
+    State s{m[r], l[r], {ex[r]}, best[r], {dg[r]}, bi[r]};
 #pragma unroll
-    for (int o = 1; o <= 8; o <<= 1) {
-      const float m2 = __shfl_xor(m[r], o, 64), l2 = __shfl_xor(l[r], o, 64), e2 = __shfl_xor(ex[r], o, 64);
-      const float b2 = __shfl_xor(best[r], o, 64), d2 = __shfl_xor(dg[r], o, 64);
-      const int i2 = __shfl_xor(bi[r], o, 64);
-      const float mn = fmaxf(m[r], m2);
-      const float s1 = m[r] == -INFINITY ? 0.f : __expf(m[r] - mn), s2 = m2 == -INFINITY ? 0.f : __expf(m2 - mn);
-      l[r] = l[r] * s1 + l2 * s2;
-      ex[r] = ex[r] * s1 + e2 * s2;
-      m[r] = mn;
-      if (b2 > best[r] || (b2 == best[r] && i2 < bi[r])) { best[r] = b2; bi[r] = i2; }
-      dg[r] += d2;
-    }
-    if (c == 0) {
-      float* q = red[wave][g * 4 + r];
-      q[0] = m[r]; q[1] = l[r]; q[2] = ex[r]; q[3] = best[r]; q[4] = __int_as_float(bi[r]); q[5] = dg[r];
-    }
+    for (int o = 1; o <= 8; o <<= 1) s.merge(s.shfl_xor(o));
+    if (c == 0) s.store(red[wave][g * 4 + r]);
   }
   __syncthreads();
   if (threadIdx.x < 16) {
     const int row = threadIdx.x, i = i0 + row;
-    if (i < B) {
-      float M = -INFINITY, bb = -INFINITY, dd = 0.f;
-      for (int w = 0; w < 4; ++w) { M = fmaxf(M, red[w][row][0]); bb = fmaxf(bb, red[w][row][3]); dd += red[w][row][5]; }
-      float ll = 0.f, ee = 0.f;
-      int idx = 0x7fffffff;
-      for (int w = 0; w < 4; ++w) {
-        const float s2 = red[w][row][0] == -INFINITY ? 0.f : __expf(red[w][row][0] - M);
-        ll += red[w][row][1] * s2;
-        ee += red[w][row][2] * s2;
-        if (red[w][row][3] == bb) idx = min(idx, __float_as_int(red[w][row][4]));
-      }
-      float* st = stats + ((size_t)dir * B + i) * 4;
-      st[0] = M + __logf(ll);
-      st[1] = dd;
-      st[2] = ee / ll;
-      st[3] = bb;
-      argmax[dir * B + i] = idx;
-    }
+    if (i < B)
+      State::finish(red[0][row], 16 * State::REC, stats + ((size_t)dir * B + i) * State::STATS, argmax + dir * B + i);
   }
 }
 

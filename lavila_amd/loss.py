@@ -20,6 +20,8 @@ Gradient convention (pinned by tests/golden/clip_loss_mul
 backward sums W identical copies; DDP's 1/W averaging restores the true gradient); with the default
 `gather_features` path it hands 1 x. Both are reproduced. d(loss)/d(logit_scale) is the full global
 derivative on every rank in both modes, as in the reference.
+
+What is gathered, in which dtype, and `row0` is written once, in `_Exchange` (tests/test_loss_exchange_cpu.py).
 """
 import torch
 import torch.distributed as dist
@@ -29,23 +31,46 @@ from . import ops
 from .distributed_utils import all_gather_rows
 
 
+class _Exchange:
+    """The batch exchange every loss below makes in forward: one rank-ordered gather of the local rows as [img | txt]
+    (`extra` given: as float32 [img | txt | extra], the per-row indicator / weight riding along as the last column), then
+    -- behind the slab kernels -- `gather_record`. W = 1 issues no collective. Holds B, E, G, W, row0 and img_all,
+    txt_all, extra_all ([G], float32 off the wire; the caller's own tensor on one rank)."""
+
+    def __init__(self, image_embed, text_embed, W, rank, extra=None):
+        B, E = image_embed.shape
+        # compute dtype: the embeddings' common dtype when the kernels take it, float32 otherwise
+        dt = image_embed.dtype if (image_embed.dtype == text_embed.dtype and
+                                   image_embed.dtype in (torch.float32, torch.bfloat16)) else torch.float32
+        img, txt = image_embed.detach().to(dt), text_embed.detach().to(dt)
+        if W > 1:
+            cols = [img, txt] if extra is None else [img.float(), txt.float(), extra.float()[:, None]]
+            both = all_gather_rows(torch.cat(cols, dim=1))                     # [G, 2E (+1)], rank-ordered
+            img_all, txt_all = both[:, :E].to(dt).contiguous(), both[:, E:2 * E].to(dt).contiguous()
+            extra = None if extra is None else both[:, 2 * E]
+        else:
+            img_all, txt_all = img.contiguous(), txt.contiguous()
+        self.B, self.E, self.G, self.W, self.row0 = B, E, img_all.shape[0], W, (rank * B if W > 1 else 0)
+        self.img_all, self.txt_all = img_all, txt_all
+        self.extra_all = None if extra is None else extra.contiguous()
+
+    def gather_record(self, part, lse=None):
+        """W > 1: one gather of this rank's [1, n] record [lse (2B) | part]. Returns the row LSEs of all ranks as [2, G]
+        (None without `lse`) and the ranks' partial sums [W, len(part)]."""
+        allp = all_gather_rows((part if lse is None else torch.cat([lse.reshape(-1), part]))[None])
+        if lse is None:
+            return None, allp
+        n = 2 * self.B
+        return allp[:, :n].reshape(self.W, 2, self.B).permute(1, 0, 2).reshape(2, self.G).contiguous(), allp[:, n:]
+
+
 class _ContrastiveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image_embed, text_embed, logit_scale, crit):
-        W, rank = crit.world_size, crit.rank
-        B, E = image_embed.shape
-        dt = image_embed.dtype if (image_embed.dtype == text_embed.dtype and
-                                   image_embed.dtype in (torch.float32, torch.bfloat16)) else torch.float32
-        img, txt = image_embed.detach().to(dt), text_embed.detach().to(dt)
+        x = _Exchange(image_embed, text_embed, crit.world_size, crit.rank)
+        B, G, W, row0, img_all, txt_all = x.B, x.G, x.W, x.row0, x.img_all, x.txt_all
         scale = logit_scale.detach().float().reshape(1).contiguous()
-        if W > 1:
-            both = all_gather_rows(torch.cat([img, txt], dim=1))           # [G, 2E], rank-ordered
-            img_all, txt_all = both[:, :E].contiguous(), both[:, E:].contiguous()
-        else:
-            img_all, txt_all = img.contiguous(), txt.contiguous()
-        G = img_all.shape[0]
-        row0 = rank * B if W > 1 else 0
 
         stats, argmax = crit._slab_forward(img_all, txt_all, scale, B, row0)   # [2,B,4] f32, [2,B] i32
         lse, diag, expect = stats[..., 0], stats[..., 1], stats[..., 2]
@@ -56,10 +81,8 @@ class _ContrastiveFn(torch.autograd.Function):
         # ITS rows of the two slabs -- exactly what _slab_forward produced -- and is not averaged over ranks
         local = bool(crit.local_loss) and W > 1 and not crit.use_vissl
         if W > 1 and (not local or crit.gather_with_grad):
-            packed = torch.cat([lse.reshape(-1), part])[None]                  # [1, 2B+3]
-            allp = all_gather_rows(packed)                                     # [W, 2B+3]
-            lse_all = allp[:, :2 * B].reshape(W, 2, B).permute(1, 0, 2).reshape(2, G).contiguous()
-            sums = allp[:, 2 * B:].sum(0)
+            lse_all, parts = x.gather_record(part, lse)                        # [1, 2B+3] per rank
+            sums = parts.sum(0)
         elif W > 1:                            # local rows only: the kernel reads nothing but the own entries
             lse_all = lse.new_zeros(2, G)
             lse_all[:, row0:row0 + B] = lse
@@ -147,19 +170,11 @@ class CLIPLoss(nn.Module):
     def debug_slabs(self, outputs):
         """Parity-test helper: this rank's scaled logits slabs [2,B,G] (f32), row predictions and labels
         (int64, global column indices) -- what loss.py:78-79,96-105,113 materialise."""
-        img, txt = outputs['image_embed'].detach(), outputs['text_embed'].detach()
-        B, E = img.shape
-        dt = img.dtype if img.dtype in (torch.float32, torch.bfloat16) and img.dtype == txt.dtype else torch.float32
-        img, txt = img.to(dt), txt.to(dt)
+        x = _Exchange(outputs['image_embed'], outputs['text_embed'], self.world_size, self.rank)
+        B, row0, img_all, txt_all = x.B, x.row0, x.img_all, x.txt_all
         scale = outputs['logit_scale'].detach().float().reshape(1).contiguous()
-        if self.world_size > 1:
-            both = all_gather_rows(torch.cat([img, txt], dim=1))
-            img_all, txt_all = both[:, :E].contiguous(), both[:, E:].contiguous()
-            row0 = self.rank * B
-        else:
-            img_all, txt_all, row0 = img.contiguous(), txt.contiguous(), 0
         _, argmax, logits = ops.clip_loss_fwd_raw(img_all, txt_all, scale, B, row0, want_logits=True)
-        labels = torch.arange(row0, row0 + B, device=img.device, dtype=torch.long)
+        labels = torch.arange(row0, row0 + B, device=img_all.device, dtype=torch.long)
         return {'logits': logits, 'pred': argmax.long(), 'labels': labels}
 
 
@@ -182,23 +197,12 @@ class _SSLContrastiveFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image_embed, text_embed, logit_scale, scale_pseudo, indicators, crit):
-        W, rank = crit.world_size, crit.rank
-        B, E = image_embed.shape
         dev = image_embed.device
-        dt = image_embed.dtype if (image_embed.dtype == text_embed.dtype and
-                                   image_embed.dtype in (torch.float32, torch.bfloat16)) else torch.float32
-        img, txt = image_embed.detach().to(dt), text_embed.detach().to(dt)
-        ind = indicators.detach().to(dev).reshape(-1)
+        x = _Exchange(image_embed, text_embed, crit.world_size, crit.rank, indicators.detach().to(dev).reshape(-1))
+        B, G, W, row0, img_all, txt_all = x.B, x.G, x.W, x.row0, x.img_all, x.txt_all
+        ind_all = (x.extra_all.round() if W > 1 else x.extra_all).to(torch.int32).contiguous()
         real, pseudo = logit_scale.detach().float().reshape(()), scale_pseudo.detach().float().reshape(())
         scales3 = torch.stack([pseudo, torch.sqrt(pseudo * real), real]).contiguous()
-        if W > 1:
-            both = all_gather_rows(torch.cat([img.float(), txt.float(), ind.float()[:, None]], dim=1))
-            img_all, txt_all = both[:, :E].to(dt).contiguous(), both[:, E:2 * E].to(dt).contiguous()
-            ind_all = both[:, 2 * E].round().to(torch.int32).contiguous()
-        else:
-            img_all, txt_all, ind_all = img.contiguous(), txt.contiguous(), ind.to(torch.int32).contiguous()
-        G = img_all.shape[0]
-        row0 = rank * B if W > 1 else 0
 
         stats, argmax = crit._slab_forward(img_all, txt_all, ind_all, scales3, B, row0)     # [2,B,8], [2,B]
         lse, diag_l, diag_z = stats[..., 0], stats[..., 1], stats[..., 5]
@@ -210,9 +214,8 @@ class _SSLContrastiveFn(torch.autograd.Function):
         part = torch.stack([(lse - diag_l).sum(), ds[0], ds[1], ds[2], ok.sum().float(),
                             (ok & (ind_loc == 1)).sum().float(), (ok & (ind_loc == 0)).sum().float()])
         if W > 1:
-            allp = all_gather_rows(torch.cat([lse.reshape(-1), part])[None])               # [W, 2B+7]
-            lse_all = allp[:, :2 * B].reshape(W, 2, B).permute(1, 0, 2).reshape(2, G).contiguous()
-            sums = allp[:, 2 * B:].sum(0)
+            lse_all, parts = x.gather_record(part, lse)                                    # [1, 2B+7] per rank
+            sums = parts.sum(0)
         else:
             lse_all, sums = lse.contiguous(), part
         num_gt = (ind_all == 1).sum().float()
@@ -315,30 +318,17 @@ class _MarginRankingFn(torch.autograd.Function):
         from .distributed_utils import is_distributed_training_run
         W = dist.get_world_size() if is_distributed_training_run() else 1
         rank = dist.get_rank() if W > 1 else 0
-        B, E = image_embed.shape
-        dt = image_embed.dtype if (image_embed.dtype == text_embed.dtype and
-                                   image_embed.dtype in (torch.float32, torch.bfloat16)) else torch.float32
-        img, txt = image_embed.detach().to(dt), text_embed.detach().to(dt)
-        w = None if weight is None else weight.detach().to(img.device).float().reshape(-1)
-        if w is not None and w.shape[0] != B:
-            raise ValueError(f'weight has {w.shape[0]} entries for {B} pairs')
-        if W > 1 and w is not None:
-            both = all_gather_rows(torch.cat([img.float(), txt.float(), w[:, None]], dim=1))      # [G, 2E+1]
-            img_all, txt_all = both[:, :E].to(dt).contiguous(), both[:, E:2 * E].to(dt).contiguous()
-            w_all = both[:, 2 * E].contiguous()
-        elif W > 1:
-            both = all_gather_rows(torch.cat([img, txt], dim=1))                                  # [G, 2E]
-            img_all, txt_all, w_all = both[:, :E].contiguous(), both[:, E:].contiguous(), None
-        else:
-            img_all, txt_all, w_all = img.contiguous(), txt.contiguous(), None if w is None else w.contiguous()
-        G = img_all.shape[0]
-        row0 = rank * B
+        w = None if weight is None else weight.detach().to(image_embed.device).float().reshape(-1)
+        if w is not None and w.shape[0] != image_embed.shape[0]:
+            raise ValueError(f'weight has {w.shape[0]} entries for {image_embed.shape[0]} pairs')
+        x = _Exchange(image_embed, text_embed, W, rank, w)
+        B, G, row0, img_all, txt_all, w_all = x.B, x.G, x.row0, x.img_all, x.txt_all, x.extra_all
         N = 2 * G * (G - 1) if crit.fix_norm else 2 * G * G
 
         prep = crit._slab_prepare(img_all, txt_all, w_all, crit.margin)                          # [7,G] f32
         hinge, _ = crit._slab_forward(img_all, txt_all, prep, B, row0, not crit.fix_norm)    # [2,B] f32, [2,B] i32
-        part = hinge.sum().reshape(1, 1)
-        total = all_gather_rows(part).sum() if W > 1 else part.sum()
+        part = hinge.sum().reshape(1)
+        total = x.gather_record(part)[1].sum() if W > 1 else part.sum()                      # [1, 1] per rank
         loss = total / N                                 # G = 1 with fix_norm: 0 / 0 = NaN, the reference's empty mean
         ctx.save_for_backward(img_all, txt_all, prep)
         ctx.cfg = (B, row0, W, N, crit, image_embed.dtype, text_embed.dtype)

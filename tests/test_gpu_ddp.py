@@ -268,8 +268,8 @@ def _rccl_worker(port, q):
         lo = O.clip_loss(oo['image_embed'], oo['text_embed'], oo['logit_scale'])['loss']
         res['loss'] = (ld['loss'].item(), lo.item())
         res['grads_finite'] = all(bool(torch.isfinite(p.grad).all()) for p in model.parameters())
-        # the two gathers of the sharded loss's multi-rank branch (lavila_amd/loss.py:_ContrastiveFn), as it issues them:
-        # [B, 2E] bf16 embeddings and the [1, 2B+3] f32 row-LSE / partial-sum record
+        # the two gathers of the sharded loss's multi-rank branch, as lavila_amd/loss.py:_Exchange (the one place that
+        # issues them) does for CLIPLoss: [B, 2E] bf16 embeddings and the [1, 2B+3] f32 row-LSE / partial-sum record
         both = torch.randn(5, 128, device=dev).bfloat16()
         rec = torch.randn(1, 13, device=dev)
         res['loss_gathers'] = bool(torch.equal(DU.all_gather_rows(both), both) and torch.equal(DU.all_gather_rows(rec), rec))
