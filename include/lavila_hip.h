@@ -32,7 +32,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: exactly the entry points declared here are exported. */
 #pragma GCC visibility push(default)
 
-enum { LVL_F32 = 0, LVL_BF16 = 1 };
+enum { LVL_F32 = 0, LVL_BF16 = 1, LVL_F16 = 2 /* lvl_clip_ingest's output only */ };
 enum { LVL_OK = 0, LVL_EINVAL = -22, LVL_ENOSYS = -38, LVL_EHIP = -5 };
 enum { LVL_ATTN_SPACE = 0, LVL_ATTN_TIME = 1, LVL_ATTN_CAUSAL = 2 /* lvl_attention_fast_path only */ };
 enum { LVL_EPI_BIAS = 0, LVL_EPI_BIAS_QUICKGELU = 1, LVL_EPI_QUICKGELU_BWD = 2, LVL_EPI_BIAS_RESIDUAL = 3,
@@ -185,6 +185,37 @@ int lvl_bias_quickgelu_bwd(const void* da, const void* u, const float* bias, voi
  * plain GEMM. H % P == 0, W % P == 0. */
 int lvl_patchify(const float* video, void* patches, int B, int C, int F, int H, int W, int P,
                  int frame_major, int dtype, void* stream);
+
+/* ---- clip ingest: decoded uint8 frames -> the model's input ---------------------------------------------
+ * Replaces the per-sample host transform of the reference drivers (main_pretrain.py:269-283: Permute([3,0,1,2]) ->
+ * RandomResizedCrop, or Resize + CenterCrop -> NormalizeVideo, on float frames holding the integers 0..255) and the
+ * float32 clip that crosses PCIe behind it; torchvision 0.11.2 semantics for tensors: bilinear, half-pixel centres,
+ * align_corners=False, NO antialiasing.
+ * frames: uint8, logical [B,F,H,W,3] (RGB, channel last), pixel stride 3 bytes; clip_stride / frame_stride / row_stride
+ *   are byte strides (row >= 3 W, frame >= one frame's extent, clip >= one clip's extent; no alignment is required and
+ *   offsets are 64-bit, so a clip may begin beyond 2^31 bytes).
+ * params: int32 [B,8] = {top, left, h, w, Ry, Rx, sy, sx} per sample (16-byte aligned): the region
+ *   [top, top+h) x [left, left+w) of every frame of clip b is resized to Ry x Rx and the S x S window at (sy, sx) of
+ *   that is taken. flip (nullable): int32 [B], non-zero mirrors the window along x. Per axis, in float32 with every
+ *   operation rounded on its own (n = region extent, R = resized extent, o = output index, sh = window offset):
+ *     scale = (float)n / (float)R;  s = max(scale * ((float)(o + sh) + 0.5f) - 0.5f, 0)
+ *     i0 = min((int)s, n-1);  i1 = min(i0+1, n-1);  lam = s - (float)i0
+ *     v = (1-lam_y) * ((1-lam_x) p00 + lam_x p01) + lam_y * ((1-lam_x) p10 + lam_x p11);  y = (v - mean_c) / std_c
+ *   (IEEE subtraction, correctly rounded division), stored round-to-nearest-even. The blocks live on the device, so the
+ *   library cannot refuse a malformed one: the kernel forces every block into the frame (memory safety only) and the host
+ *   layer (lavila_amd.ingest.validate_params) refuses it before the launch. Refused here (LVL_EINVAL): S odd or not a
+ *   multiple of P, P odd, overlapping strides, std <= 0, ld odd or below 3 P P, unknown dtype.
+ * lvl_clip_ingest: clip [B,3,F,S,S], dtype LVL_F32 / LVL_BF16 / LVL_F16.
+ * lvl_clip_ingest_patches: patches [B*F*(S/P)^2, ld], dtype LVL_F32 / LVL_BF16: bit for bit what lvl_patchify writes from
+ *   lvl_clip_ingest's float32 clip, in columns 0 .. 3 P P; columns 3 P P .. ld are written as zeros (ld = 640 gives the
+ *   14 x 14 towers' GEMM operand without a pad copy). Both share one device function per value. */
+int lvl_clip_ingest(const void* frames, const int32_t* params, const int32_t* flip, void* clip, int B, int F, int H, int W,
+                    int S, int64_t clip_stride, int64_t frame_stride, int64_t row_stride, float mean0, float mean1,
+                    float mean2, float std0, float std1, float std2, int dtype, void* stream);
+int lvl_clip_ingest_patches(const void* frames, const int32_t* params, const int32_t* flip, void* patches, int B, int F,
+                            int H, int W, int S, int P, int64_t ld, int64_t clip_stride, int64_t frame_stride,
+                            int64_t row_stride, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                            int dtype, void* stream);
 
 /* ---- token assembly: cls concat + positional/temporal embedding add --------------------------------
  * x[b,0,:] = cls + pos[0];  x[b,1+f*N+n,:] = pe[b,f*N+n,:] + pos[1+n] + temporal[f]

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib', 'liblavila_hip.so')
 
 LVL_F32, LVL_BF16 = 0, 1
+LVL_F16 = 2          # lvl_clip_ingest's output only
 ATTN_SPACE, ATTN_TIME = 0, 1
 # The epilogues of lvl_linear_tn (LVL_EPI_* of the header; csrc/gemm_tn_kernel.h holds the library's table):
 # name -> (code, two_out: writes aux_out, colsum: reads aux_in and leaves column sums, f32: exists in the f32-class mode).
@@ -56,6 +57,10 @@ SIGNATURES = {
     'lvl_bias_quickgelu_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'lvl_patchify': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_embed_tokens_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    # (frames u8, params i32 [B,8], flip i32 [B] | NULL, out, B, F, H, W, S, [P, ld,] clip / frame / row stride in bytes,
+    #  mean x3, std x3, dtype, stream)
+    'lvl_clip_ingest': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _L, _L, _L] + [_F] * 6 + [_I, _P]),
+    'lvl_clip_ingest_patches': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L] + [_F] * 6 + [_I, _P]),
     'lvl_divided_attn_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_divided_attn_bwd': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'lvl_attention_fast_path': (_I, [_I, _I, _I, _I]),

@@ -26,9 +26,12 @@ ARCH = 'gfx950'
 # instruction) but in the dependent chains of a two-waves-per-SIMD kernel they are slower than the scalar forms: the TN GEMM's
 # QuickGELU epilogues (+30 % in tools/probes/valu_gelu.hip) and the fused space-attention backward (-3.2 % without them);
 # LayerNorm forward (+20 % WITHOUT them), the time attention and the streaming kernels keep the default.
+# -ffp-contract=off for the clip ingest: its interpolation is specified operation by operation (include/lavila_hip.h) and has
+# to match the host restatement to the bit; a fused multiply-add rounds once where that rounds twice.
 _NO_SLP = ['-fno-slp-vectorize']
 EXTRA_FLAGS = {'attn_space_mfma.hip': ['-fno-honor-nans'], 'attn_space_stream.hip': ['-fno-honor-nans'],
-               'gemm_tn_mfma.hip': _NO_SLP, 'gemm_tn_gelu.hip': _NO_SLP, 'attn_space_bwd.hip': _NO_SLP}
+               'gemm_tn_mfma.hip': _NO_SLP, 'gemm_tn_gelu.hip': _NO_SLP, 'attn_space_bwd.hip': _NO_SLP,
+               'clip_ingest.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():

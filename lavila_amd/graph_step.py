@@ -57,6 +57,7 @@ from . import models as _models
 from . import narrator as _narrator
 from . import openai_model as _openai_model
 from . import ops
+from .ingest import refuse_pending
 
 _active = threading.local()
 
@@ -290,6 +291,7 @@ class GraphedTrainStep:
     def __call__(self, video, tokens, text_len=None):
         """One training iteration on (video, tokens) -- host or device tensors of the static shapes. `text_len`: a caller's
         own bound on the caption length (>= 1 + the largest EOT position), for token tensors already on the device."""
+        refuse_pending(video, 'GraphedTrainStep (its captured graph reads a static float clip)')
         if tuple(video.shape) != tuple(self.video.shape) or tuple(tokens.shape) != tuple(self.tokens.shape):
             raise ValueError(f'GraphedTrainStep was built for {tuple(self.video.shape)} / {tuple(self.tokens.shape)}, got '
                              f'{tuple(video.shape)} / {tuple(tokens.shape)} (a last, smaller batch runs eagerly)')

@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from . import _cabi as C
+from .ingest import PendingClip, refuse_pending
 
 
 def _f32(p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -1327,9 +1328,14 @@ def bias_quick_gelu(u, bias=None):
 # --------------------------------------------------------------------------------------------------
 # patch gather + token assembly
 # --------------------------------------------------------------------------------------------------
-def patchify(video: torch.Tensor, patch: int, dtype: torch.dtype, frame_major: bool = False) -> torch.Tensor:
+def patchify(video, patch: int, dtype: torch.dtype, frame_major: bool = False, ld=None) -> torch.Tensor:
     """[B,C,F,H,W] f32 (or, frame_major, [B,F,C,H,W]) -> [B, F*N, C*P*P]; both layouts are read in place (no gradient
-    w.r.t. pixels: the reference never needs one)."""
+    w.r.t. pixels: the reference never needs one). An ingest.PendingClip (uint8 frames + crop blocks, channel-major) goes to
+    the patch matrix in one kernel, with `ld` >= C*P*P columns per row, the ones behind C*P*P zero."""
+    if isinstance(video, PendingClip):
+        if frame_major:
+            refuse_pending(video, 'a frame-major ([B,F,C,H,W]) entry point')
+        return video.patches(patch, dtype, ld)
     video = video.detach()
     if video.dtype != torch.float32:
         video = video.float()          # fp16 clips of the --use-half eval recipes

@@ -155,6 +155,7 @@ class VideoPatchEmbed(nn.Module):
     def tokens_from_btchw(self, video):
         """[B,F,C,H,W] (what forward_features / forward receive, timesformer.py:79-84,345-348) -> [B, F*N, D]: the
         gather reads this layout in place as well (no permute().contiguous() round trip of the clip)."""
+        ops.refuse_pending(video, 'a frame-major ([B,F,C,H,W]) entry point (forward_features, VideoPatchEmbed.forward)')
         assert video.shape[1] <= self.num_frames
         return self._tokens(video, frame_major=True)
 
@@ -165,6 +166,7 @@ class VideoPatchEmbed(nn.Module):
 
     def forward(self, x):
         """Reference signature: x [B,F,C,H,W] -> [B*F, D, H/P, W/P] (timesformer.py:79-84)."""
+        ops.refuse_pending(x, 'VideoPatchEmbed.forward (frame-major, [B,F,C,H,W])')
         B, Fr, C, H, W = x.shape
         assert Fr <= self.num_frames
         tok = _like_caller(self.tokens_from_btchw(x), x, self.proj.weight)
@@ -180,15 +182,22 @@ def conv_patch_tokens(conv, video, patch, frame_major):
     [B,F,C,H,W] when frame_major) as the HIP patch gather + one GEMM against the weight viewed as [D, 3*P*P]:
     -> [B, F*N, D], rows (b, f, n)-major. Shared by VideoPatchEmbed and openai_model.VisionTransformer."""
     w = conv.weight
-    patches = ops.patchify(video, patch, _compute_dtype(w), frame_major=frame_major)
     w2 = w.reshape(w.shape[0], -1)
     k = w2.shape[1]
+    if isinstance(video, ops.PendingClip):
+        # uint8 frames straight to the GEMM operand: the 14 x 14 towers' rows are written 640 wide (zero columns behind
+        # 588), so the pad copy below is not paid
+        wide = k % 64 and video.is_cuda and w2.shape[0] % 256 == 0
+        patches = ops.patchify(video, patch, _compute_dtype(w), frame_major=frame_major, ld=k + (64 - k % 64 if wide else 0))
+    else:
+        patches = ops.patchify(video, patch, _compute_dtype(w), frame_major=frame_major)
     if k % 64 and patches.is_cuda and w2.shape[0] % 256 == 0:
         # 14 x 14 patches: 3*14*14 = 588 contraction elements. The MFMA GEMMs walk K in blocks of 64: zero columns up
         # to 640 on both operands (exact) keep the patch embedding of the L/14 towers on lvl_linear_tn /
         # lvl_linear_wgrad; the weight gradient comes back through the pad's slice
         pad = 64 - k % 64
-        patches = F.pad(patches, (0, pad))
+        if patches.shape[-1] == k:
+            patches = F.pad(patches, (0, pad))
         if torch.is_grad_enabled() and w.requires_grad:
             w2 = F.pad(w2, (0, pad))        # part of the autograd graph: one pad (and one cast) per training step
         else:
